@@ -15,13 +15,18 @@ itself (re-exec under torch.distributed.run on 127.0.0.1) -- --gpus is never sil
 
 Prints ONE JSON line on rank 0 (see the task contract), including
   roofline     -- the hs_eval kernel (the defect+Jacobian kernel of SURVEY.md 8(d)): algorithmic bytes per launch /
-                  HIP-event duration measured on the library's own stream inside the timed region;
+                  HIP-event duration measured on the library's own stream inside the timed region.
+A plain run does only that: set up, warm up, time --steps steps, print.  `--full` adds, after the timed region and not part of `value`:
+  download     -- the same steps once more without the download (what the download costs);
+  solver_options -- with --mu-init: the same steps at the library's default options;
   cpu_baseline -- the oracle's SciPy SLSQP path (the reference's NLPSolverType.SLSQP branch on restated callbacks)
                   timed on this box's host cores: one FULL converged solve at N=25 (measured) and a time-bounded sample
                   of the N=100 solve (iteration rate measured, solve rate extrapolated -- labelled so);
-  other_configs -- (N = 1, after the timed region, not part of `value`) the other BASELINE configs on one GPU and the headline
-                  workload through the host-buffer API solve_batch (numpy in, numpy out: the PCIe-inclusive rate),
-                  tools/bench_configs.py; --no-other-configs skips them.
+  other_configs -- (N = 1) the other BASELINE configs on one GPU and the headline workload through the host-buffer API
+                  solve_batch (numpy in, numpy out: the PCIe-inclusive rate), tools/bench_configs.py; --no-other-configs skips them;
+  other_scaling -- (N > 1) the other of weak / strong measured right after the line's own split; --no-other-scaling skips it.
+`--dump-outputs DIR` writes what the last timed step delivered to the host (z*, cost, status of every instance) as DIR/<name>.npy,
+float64; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -36,6 +41,23 @@ sys.path.insert(0, ROOT)
 
 ALG_BYTES_PER_EVAL = lambda N, ns, nu: 8 * ((2 * N + 1) * (ns + nu) + 16 + 2 * N * ns + N * (5 * ns * ns + 5 * ns * nu) + (2 * N + 1) * nu + 1)
 HBM_PEAK_GBPS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_BYTES_MAX = 64 << 20   # --dump-outputs: above this the rows are a fixed, seeded sample (rows.npy names them)
+
+
+def dump_outputs(path, res):
+  """--dump-outputs DIR: the host copies of the last timed step (z*, cost, status of every instance, in instance order) as DIR/<name>.npy,
+  float64.  When they exceed DUMP_BYTES_MAX, the same rows of each are kept: a sorted sample drawn by default_rng(0), listed in rows.npy."""
+  os.makedirs(path, exist_ok=True)
+  arrs = {k: np.asarray(res[k].cpu().numpy(), dtype=np.float64) for k in ("z", "cost", "status")}
+  n = arrs["z"].shape[0]
+  row_bytes = 8 * (arrs["z"].shape[1] + 3)          # z row + cost + status + its entry in rows.npy
+  if n * row_bytes > DUMP_BYTES_MAX:
+    rows = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_MAX // row_bytes, replace=False))
+    arrs = {k: v[rows] for k, v in arrs.items()}
+    arrs["rows"] = rows.astype(np.float64)
+  for k, v in arrs.items():
+    np.save(os.path.join(path, k + ".npy"), v)
+  return sorted(arrs)
 
 
 def build_workload(B, N, seed):
@@ -440,17 +462,22 @@ def run(a, rank, world, dev, make_engine):
   if rank == 0:
     last = host[(nstep[0] - 1) & 1]
     assert bool(torch.isfinite(last["z"]).all()) and int((last["status"] == 0).sum()) >= last_ok
-  # the same K steps once more WITHOUT the download (informative: what the download costs; not `value`)
-  fence()
-  t1 = time.perf_counter()
-  for _ in range(a.steps):
-    step(download=False)
-  fence()
-  dt_nodl = time.perf_counter() - t1
+    if getattr(a, "dump_outputs", None):
+      dump_outputs(a.dump_outputs, last)
+  full = bool(getattr(a, "full", False))
+  # --full: the same K steps once more WITHOUT the download (informative: what the download costs; not `value`)
+  dt_nodl = 0.0
+  if full:
+    fence()
+    t1 = time.perf_counter()
+    for _ in range(a.steps):
+      step(download=False)
+    fence()
+    dt_nodl = time.perf_counter() - t1
   # ... and once more at the library's default options when the measured loop ran with a workload-specific one (informative; not `value`)
   dt_lib = nconv_lib = 0.0
   tuned = mu_used is not None and mu_lib is not None and mu_used != mu_lib
-  if tuned:
+  if tuned and full:
     eng.set_mu_init(0.0)
     step()
     fence()
@@ -526,8 +553,8 @@ def run(a, rank, world, dev, make_engine):
     "converged_fraction": nconv_all / (a.steps * total),
     "download": {"what": "z*, cost, status of all instances -> pinned host buffers on rank 0, inside every timed step (side stream, double-buffered: "
                          "overlaps the next step's solve); SURVEY.md 8(d): the metric ends on host rank 0",
-                 "bytes_per_step": d2h_bytes, "value_without_download": nconv_all / dt_nodl, "ms_per_step_without_download": 1e3 * dt_nodl / a.steps,
-                 "primed_before_the_steps": prime_info},
+                 "bytes_per_step": d2h_bytes, "primed_before_the_steps": prime_info,
+                 **({"value_without_download": nconv_all / dt_nodl, "ms_per_step_without_download": 1e3 * dt_nodl / a.steps} if dt_nodl else {})},
     "solver_options": ({"mu_init": mu_used, "library_default_mu_init": mu_lib,
                         "why": "initial barrier parameter of the interior-point iteration (public field of myr_solve_opts, IPOPT's mu_init): 0.003 "
                                "saves about two iterations per solve on this workload, same tolerances, same converged fraction; it is NOT the "
@@ -561,7 +588,7 @@ def run(a, rank, world, dev, make_engine):
                                "unit": "TFLOP/s", "frac": (mfma_tf / FP64_MFMA_PEAK_TFLOPS) if mfma_tf else None,
                                "note": "the Riccati sweep is a chain of dependent 16x16x4 products, one wavefront per SIMD: low by construction (SURVEY.md 8(d))"}},
   }
-  if world == 1 and a.cpu_budget > 0 and cuda:
+  if full and world == 1 and a.cpu_budget > 0 and cuda:
     try:
       out["cpu_baseline"] = cpu_baseline(N, a.cpu_budget)
     except Exception as e:   # the oracle is test infrastructure: never let it break the measured line
@@ -569,7 +596,7 @@ def run(a, rank, world, dev, make_engine):
     twin = cpu_same_algorithm(z0h, lbh, ubh, N, T, B)
     if twin:
       out["cpu_same_algorithm"] = twin
-  if world == 1 and cuda and not getattr(a, "no_other_configs", False):
+  if full and world == 1 and cuda and not getattr(a, "no_other_configs", False):
     # the other BASELINE configs (3, 4, 5 at their per-GPU share and on one GPU, README:83's trapezoidal literal), a few solves
     # each AFTER the timed region: informative lines under the same driver clock, not part of `value`
     try:
@@ -627,18 +654,18 @@ def contract_line(out):
 
 
 def both_scalings(a, rank, world, dev, make_engine):
-  """The line of `--scaling` (weak by default: --batch instances per GPU) and, for N > 1, the OTHER split of the same workload measured in the same run
-  right after it (`other_scaling`): SURVEY.md 8(e) partitions ONE batch over the GPUs (strong: 4096 -> 512 per GPU at N = 8, where a launch is one
+  """The line of `--scaling` (weak by default: --batch instances per GPU) and, for N > 1 with --full, the OTHER split of the same workload measured in the
+  same run right after it (`other_scaling`): SURVEY.md 8(e) partitions ONE batch over the GPUs (strong: 4096 -> 512 per GPU at N = 8, where a launch is one
   solve long and the single-GPU rate at that size bounds the efficiency -- profiles/r05/projected_scaling.json holds the expectation), the contract's
   default keeps the work per GPU fixed.  Whoever reads a SCALE file gets both numbers under one clock."""
   import copy
   out = run(a, rank, world, dev, make_engine)
-  if world > 1 and not getattr(a, "no_other_scaling", False):
+  if getattr(a, "full", False) and world > 1 and not getattr(a, "no_other_scaling", False):
     b = copy.copy(a)
     b.scaling = "strong" if a.scaling == "weak" else "weak"
     if b.scaling == "weak":
       b.batch = max(1, a.batch // world)            # the per-GPU share of the strong line, held fixed
-    b.cpu_budget = 0; b.no_other_configs = True; b.warmup = max(1, min(a.warmup, 2))
+    b.cpu_budget = 0; b.no_other_configs = True; b.warmup = max(1, min(a.warmup, 2)); b.dump_outputs = None
     o2 = run(b, rank, world, dev, make_engine)
     if rank == 0 and out is not None and o2 is not None:
       out["other_scaling"] = {k: o2[k] for k in ("scaling", "value", "unit", "ms_per_step", "steps", "warmup", "converged_fraction") if k in o2}
@@ -664,10 +691,15 @@ def main():
   ap.add_argument("--intervals", type=int, default=100)
   ap.add_argument("--mu-init", type=float, default=0.0,
                   help="initial barrier parameter of the solves in the timed region (0 = the library default 0.1, which is what the headline is "
-                       "measured with; a non-zero value is named in the line and the same steps are timed at the default as well)")
-  ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work for the N=100 cpu_baseline sample (0 = skip)")
-  ap.add_argument("--no-other-scaling", action="store_true", help="N > 1: skip the second line (the other of weak / strong) measured after the first")
-  ap.add_argument("--no-other-configs", action="store_true", help="skip the informative solves of BASELINE configs 3/4/5 after the timed region")
+                       "measured with; a non-zero value is named in the line and, with --full, the same steps are timed at the default as well)")
+  ap.add_argument("--full", action="store_true",
+                  help="after the timed region also measure what the headline does not need: the steps without the download, the CPU baselines, "
+                       "the other BASELINE configs (N = 1) and the other scaling (N > 1)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write z*, cost and status of the last timed step as DIR/<name>.npy (float64, at most 64 MB: a seeded sample of rows above that)")
+  ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU work for the N=100 cpu_baseline sample (0 = skip)")
+  ap.add_argument("--no-other-scaling", action="store_true", help="--full, N > 1: skip the second line (the other of weak / strong) measured after the first")
+  ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the informative solves of BASELINE configs 3/4/5 after the timed region")
   ap.add_argument("--cpu-full", metavar="FILE", default=None,
                   help="measure the whole CPU baseline (one full N-interval SLSQP solve, ~9 min, + a trust-constr subsample) on this host, write FILE, exit")
   a = ap.parse_args()

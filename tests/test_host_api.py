@@ -201,7 +201,7 @@ def _both_worker(rank, world, port, q):
   import bench
   os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
   dist.init_process_group("gloo", rank=rank, world_size=world)
-  a = argparse.Namespace(gpus=world, steps=2, warmup=1, batch=8, scaling="weak", intervals=4, cpu_budget=0.0, no_other_configs=True)
+  a = argparse.Namespace(gpus=world, steps=2, warmup=1, batch=8, scaling="weak", intervals=4, cpu_budget=0.0, no_other_configs=True, full=True)
   _StubEngine.bad_x0 = float("nan")
   out = bench.both_scalings(a, rank, world, torch.device("cpu"), lambda N, T, dev, B: _StubEngine(N, T, dev, B))
   q.put((rank, out))
@@ -209,7 +209,7 @@ def _both_worker(rank, world, port, q):
 
 
 def test_bench_prints_the_strong_split_beside_the_weak_line_world2_gloo():
-  """N > 1: the contract's line (weak: --batch per GPU) carries the other split of the same batch (strong: --batch in total, SURVEY.md 8(e)'s
+  """N > 1 with --full: the contract's line (weak: --batch per GPU) carries the other split of the same batch (strong: --batch in total, SURVEY.md 8(e)'s
   partitioning) measured in the same run -- the driver's SCALE file then holds both under one clock."""
   import torch.multiprocessing as mp
   ctx = mp.get_context("spawn")
@@ -225,6 +225,45 @@ def test_bench_prints_the_strong_split_beside_the_weak_line_world2_gloo():
   o2 = out["other_scaling"]
   assert o2["scaling"] == "strong" and o2["global_batch"] == 8 and o2["per_gpu_batch"] == [4, 4]
   assert o2["unit"] == "solves/s" and o2["value"] > 0 and o2["steps"] == 2
+
+
+def test_bench_dumps_the_last_step_and_measures_extras_only_with_full(tmp_path):
+  """One rank, stub engine: --dump-outputs writes what the last timed step delivered to the host (z*, cost, status in instance order,
+  float64); a plain run times nothing after its steps, --full re-times them without the download."""
+  import argparse
+  import torch
+  import bench
+  z0 = bench.build_workload(5, 4, 2019)[1]
+  _StubEngine.bad_x0 = float(z0[3, 0])
+  mk = lambda N, T, dev, B: _StubEngine(N, T, dev, B)
+  a = argparse.Namespace(gpus=1, steps=3, warmup=1, batch=5, scaling="weak", intervals=4, cpu_budget=0.0, dump_outputs=str(tmp_path / "out"))
+  out = bench.run(a, 0, 1, torch.device("cpu"), mk)
+  assert out["steps"] == 3 and "value_without_download" not in out["download"]
+  d = {k: np.load(tmp_path / "out" / (k + ".npy")) for k in ("z", "cost", "status")}
+  assert sorted(os.listdir(tmp_path / "out")) == ["cost.npy", "status.npy", "z.npy"]
+  assert all(v.dtype == np.float64 for v in d.values())
+  assert np.array_equal(d["z"], z0) and np.array_equal(d["cost"], np.ones(5)) and np.array_equal(d["status"], [0, 0, 0, 1, 0])
+  a.full, a.dump_outputs = True, None
+  out = bench.run(a, 0, 1, torch.device("cpu"), mk)
+  assert out["download"]["value_without_download"] > 0 and out["download"]["ms_per_step_without_download"] > 0
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_of_rows_above_the_limit(tmp_path, monkeypatch):
+  import torch
+  import bench
+  n, w = 50, 7
+  res = {"z": torch.arange(n * w, dtype=torch.float64).reshape(n, w), "cost": torch.arange(n, dtype=torch.float64),
+         "status": (torch.arange(n) % 3).to(torch.int32)}
+  monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 20 * 8 * (w + 3))
+  assert bench.dump_outputs(str(tmp_path / "a"), res) == ["cost", "rows", "status", "z"]
+  bench.dump_outputs(str(tmp_path / "b"), res)
+  rows = np.load(tmp_path / "a" / "rows.npy")
+  assert len(rows) == 20 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+  r = rows.astype(int)
+  assert np.array_equal(np.load(tmp_path / "a" / "z.npy"), res["z"].numpy()[r])
+  assert np.array_equal(np.load(tmp_path / "a" / "cost.npy"), r.astype(np.float64))
+  assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), (r % 3).astype(np.float64))
+  assert sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES_MAX
 
 
 def test_gather_to_one_rank_gloo_world2():

@@ -58,7 +58,9 @@ def test_solver_cores_are_clean_under_asan_ubsan_with_poisoned_scratch():
     open(drv, "w").write(DRIVER)
     outs = []
     for poison in ("", "1"):
-      env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1", OMP_NUM_THREADS="4")
+      # the sanitizer runtime goes first; whatever the environment already preloads stays behind it
+      preload = ":".join(p for p in (asan, os.environ.get("LD_PRELOAD", "")) if p)
+      env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1", OMP_NUM_THREADS="4")
       env.pop("POISON", None)
       if poison:
         env["POISON"] = "1"

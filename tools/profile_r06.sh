@@ -4,7 +4,7 @@
 #   --kernel-trace --stats AND their PMC passes (counters of the final build for every number the documents quote); batch sweeps.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/prof_r06; rm -rf $OUT; mkdir -p $OUT
-python bench.py > $OUT/bench_n1_default.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench_n1_default.json 2> $OUT/bench.err
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python bench.py --cpu-budget 0 --no-other-configs > $OUT/bench_n1_under_rocprof.json 2> $OUT/stats.log
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/bench_n1_kernel_stats.csv 2>/dev/null
 pmc_passes() {      # $1 = sub-directory, rest = command
