@@ -1126,7 +1126,7 @@ struct HsFused {
   typedef double mfma_d4 __attribute__((ext_vector_type(4)));
   __device__ static int riccati_mfma(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
     using namespace detail;
-    const int lane = c.lane, N = c.N;
+    const int lane = c.lane, N = __builtin_amdgcn_readfirstlane(c.N);      // (wave-uniform: the loop over the stages is scalar control flow)
     const int g = lane >> 4, j = lane & 15;
     const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
     const int ycol = scol >= 0 ? scol : ((j == 12 || j == 13) ? NS + 1 : ((j == 8 || j == 9) ? NS + 2 : -1));
@@ -1175,6 +1175,7 @@ struct HsFused {
     for (int u = 0; u < PF; ++u) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+      __builtin_amdgcn_sched_barrier(0);      // (slot by slot, in ring order: the loop's first stage then waits for slot 0 alone, not for the youngest loads)
     }
     auto mid_part = [&](double n0, double n1, double Gm) -> mfma_d4 {
       n0 += dv0; n1 += dv1;
@@ -1210,96 +1211,120 @@ struct HsFused {
     mfma_d4 D1c = {0.0, 0.0, 0.0, 0.0}, Rmc = {0.0, 0.0, 0.0, 0.0};
 
 #endif
-    for (int kb = N - 1; kb >= 0; kb -= PF) {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int k = kb - u;
-        if (k < 0) break;
-        X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
-        const double G = in[u][2];
-        const double nn0 = in[(u + 1) % PF][3], nn1 = in[(u + 1) % PF][4], nGm = in[(u + 1) % PF][5];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-        const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
+    // one stage from ring slot u
+    auto stage = [&](const int u) {
+      X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
+      const double G = in[u][2];
+      const double nn0 = in[(u + 1) % PF][3], nn1 = in[(u + 1) % PF][4], nGm = in[(u + 1) % PF][5];
+      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
 #if MYR_SWEEP_CARRY
-        // (rows 8..15 of R~ are zero -- the A operand has no such rows -- and stay zero from stage to stage: the previous result IS the next C operand's
-        //  upper half, no zero fill)
-        mfma_d4 C1 = D1c;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-        D1c = D1;
+      // (rows 8..15 of R~ are zero -- the A operand has no such rows -- and stay zero from stage to stage: the previous result IS the next C operand's
+      //  upper half, no zero fill)
+      mfma_d4 C1 = D1c;
+      C1[0] = fma(sh0, f_she, X0 * f_keep);
+      C1[1] = fma(sh1, f_she, X1 * f_keep);
+      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+      D1c = D1;
 #else
-        mfma_d4 C1;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        C1[2] = 0.0; C1[3] = 0.0;
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+      mfma_d4 C1;
+      C1[0] = fma(sh0, f_she, X0 * f_keep);
+      C1[1] = fma(sh1, f_she, X1 * f_keep);
+      C1[2] = 0.0; C1[3] = 0.0;
+      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
 #endif
-        mfma_d4 C2;
-        C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
+      mfma_d4 C2;
+      C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
 #if MYR_SWEEP_CARRY >= 2
-        C2[3] += QmU;
+      C2[3] += QmU;
 #endif
-        const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-        // midpoint part of stage k-1 (independent of the recursion): issued HERE, so that its two dependent products run on
-        // the matrix pipe while the vector pipe waits for D2 and computes the gains -- behind D3 they delayed the next stage's D1
-        double m0 = nn0 + dv0, m1 = nn1 + dv1;
-        const double ms0 = W0::dpp_row_shr8(m0), ms1 = W0::dpp_row_shr8(m1);
+      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
+      // midpoint part of stage k-1 (independent of the recursion): issued HERE, so that its two dependent products run on
+      // the matrix pipe while the vector pipe waits for D2 and computes the gains -- behind D3 they delayed the next stage's D1
+      double m0 = nn0 + dv0, m1 = nn1 + dv1;
+      const double ms0 = W0::dpp_row_shr8(m0), ms1 = W0::dpp_row_shr8(m1);
 #if MYR_SWEEP_CARRY
-        mfma_d4 Cm = Rmc;
-        Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-        Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-        const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
-        Rmc = Rm;
+      mfma_d4 Cm = Rmc;
+      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
+      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
+      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
+      Rmc = Rm;
 #else
-        mfma_d4 Cm;
-        Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-        Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-        Cm[2] = 0.0; Cm[3] = 0.0;
-        const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
+      mfma_d4 Cm;
+      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
+      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
+      Cm[2] = 0.0; Cm[3] = 0.0;
+      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
 #endif
 #if MYR_SWEEP_CARRY >= 2
-        // (the control rows of R enter rows 12..15 of Q: added where Q is consumed -- QmU -- instead of through a C operand that is zero but for them)
-        Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-        QmU = Rm[1];
+      // (the control rows of R enter rows 12..15 of Q: added where Q is consumed -- QmU -- instead of through a C operand that is zero but for them)
+      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
+      QmU = Rm[1];
 #else
-        mfma_d4 Cq;
-        Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
-        Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
+      mfma_d4 Cq;
+      Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
+      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
 #endif
-        const double q00 = W0::rdlane(D2[3], 12), q10 = W0::rdlane(D2[2], 12), q11 = W0::rdlane(D2[2], 8);
-        const double det = fma(q00, q11, -(q10 * q10));
-        const double rdet = fast_rcp(det);
-        const double b0 = D2[3], b1 = D2[2];
-        double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
-        double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
-        // (the pivot test is wave-uniform -- the pivots come from v_readlane -- but the compiler sees per-lane values: decided in the
-        //  vector unit and, in the W > 1 kernels, made a SCALAR branch through readfirstlane, so that no matrix instruction of their sweep
-        //  sits inside an EXEC-masked region: v_mfma does not honour EXEC on this part, tools/dev/litmus/mfma_exec.hip)
-        const bool rare_ = !(q00 > reg_floor) || !(det > reg_floor * q00);
-        if (uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(rare_)) {                                       // rare
-          const double u00 = q00, u10 = q10, u11 = q11;
-          double d0 = u00;
-          if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
-          const double i0 = fast_rcp(d0);
-          const double l10 = u10 * i0;
-          double d1 = u11 - l10 * l10 * d0;
-          if (!(d1 > reg_floor)) { d1 = dmax(fabs(d1), reg_floor); ++nreg; }
-          if (uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(nreg > 0) && abort_u) return nreg;
-          const double i1 = fast_rcp(d1);
-          kk0 = b0; kk1 = b1;
-          kk1 -= l10 * kk0;
-          kk0 *= i0; kk1 *= i1;
-          kk0 -= l10 * kk1;
-        }
-        k_ptr[0] = kk0; k_ptr[k_str] = kk1;
-        k_ptr -= k_step;
-        const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
-        const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);
-        D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      const double q00 = W0::rdlane(D2[3], 12), q10 = W0::rdlane(D2[2], 12), q11 = W0::rdlane(D2[2], 8);
+      const double det = fma(q00, q11, -(q10 * q10));
+      const double rdet = fast_rcp(det);
+      const double b0 = D2[3], b1 = D2[2];
+      double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
+      double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
+      // (the pivot test is wave-uniform -- the pivots come from v_readlane -- but the compiler sees per-lane values: decided in the
+      //  vector unit and, in the W > 1 kernels, made a SCALAR branch through readfirstlane, so that no matrix instruction of their sweep
+      //  sits inside an EXEC-masked region: v_mfma does not honour EXEC on this part, tools/dev/litmus/mfma_exec.hip)
+      const bool rare_ = !(q00 > reg_floor) || !(det > reg_floor * q00);
+      if (uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(rare_)) {                                       // rare
+        const double u00 = q00, u10 = q10, u11 = q11;
+        double d0 = u00;
+        if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
+        const double i0 = fast_rcp(d0);
+        const double l10 = u10 * i0;
+        double d1 = u11 - l10 * l10 * d0;
+        if (!(d1 > reg_floor)) { d1 = dmax(fabs(d1), reg_floor); ++nreg; }
+        const double i1 = fast_rcp(d1);
+        kk0 = b0; kk1 = b1;
+        kk1 -= l10 * kk0;
+        kk0 *= i0; kk1 *= i1;
+        kk0 -= l10 * kk1;
+      }
+      k_ptr[0] = kk0; k_ptr[k_str] = kk1;
+      k_ptr -= k_step;
+      const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
+      const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);
+      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      // refill slot u (stage k - PF) only here, behind the pivot branch: the scheduler cannot lift the loads above D2, the last reader of
+      // the slot's G, so they land in the ring's own registers.  Issued in front of D2, they needed temporaries that the end of the stage
+      // copied into the ring -- a wait for this stage's own loads.
+#pragma unroll
+      for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+    };
+    // Whole groups of PF stages, then the remainder.  The ring only prefetches if a load lands in the register its stage reads it from:
+    // a stage test or an exit inside the group (per-lane values to the compiler) made every stage a branch region whose join copied the
+    // ring slots -- each copy a wait for the loads of the stage that issued them.  So the main loop has no stage test, the count of
+    // stages is wave-uniform (scalar loop control), and an abort of the pivot rule leaves the sweep at the start of the next group: the
+    // stages after the aborting one only write gains that the next rung rewrites (the caller looks at nothing but nreg > 0 of an aborted
+    // sweep).  (The test at the top of the loop, not behind the group: there the exit took the last slot's loads off the path that stays.)
+    // The first group runs in front of the loop: entered straight from the ring fill (no gain stores in between), the loop's first
+    // stage would have to assume fewer memory operations behind the ring's oldest loads than there are, and wait for younger ones.
+    auto group = [&]() {
+#pragma unroll
+      for (int u = 0; u < PF; ++u) stage(u);
+    };
+    int kb = N - 1;
+    if (kb >= PF - 1) {
+      group();
+      for (kb -= PF; kb >= PF - 1; kb -= PF) {
+        if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
+        group();
       }
     }
+#pragma unroll
+    for (int u = 0; u < PF - 1; ++u) {
+      if (kb - u < 0) break;
+      stage(u);
+    }
+    if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
     X0 = D3[0]; X1 = D3[1];
     const double T1 = D3[1], T2 = D3[2], T3 = D3[3];
     if (scol >= 0 && j != 5) {
@@ -1331,6 +1356,7 @@ struct HsFused {
   // 1 now multiplies nu_u).  Same pivot rule; no first point.
   __device__ static int riccati_chunk(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int k_lo, int k_hi, bool last, double* xo) {
     using namespace detail;
+    k_lo = __builtin_amdgcn_readfirstlane(k_lo); k_hi = __builtin_amdgcn_readfirstlane(k_hi);      // (wave-uniform: scalar loop control, riccati_mfma)
     static_assert(!TL || (NC == NS + 2 && NU == 1), "slot 7 takes the control's multiplier");
     const int lane = c.lane;
     const int g = lane >> 4, j = lane & 15;
@@ -1384,6 +1410,7 @@ struct HsFused {
     for (int u = 0; u < PF; ++u) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+      __builtin_amdgcn_sched_barrier(0);      // (slot by slot: riccati_mfma)
     }
     auto mid_part = [&](double n0, double n1, double Gm) -> mfma_d4 {
       n0 += dv0; n1 += dv1;
@@ -1418,88 +1445,102 @@ struct HsFused {
 #if MYR_SWEEP_CARRY
     mfma_d4 D1c = {0.0, 0.0, 0.0, 0.0}, Rmc = {0.0, 0.0, 0.0, 0.0};
 #endif
-    for (int kb = k_hi - 1; kb >= k_lo; kb -= PF) {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int k = kb - u;
-        if (k < k_lo) break;
-        X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
-        const double G = in[u][2];
-        const double nn0 = in[(u + 1) % PF][3], nn1 = in[(u + 1) % PF][4], nGm = in[(u + 1) % PF][5];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-        const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
+    // one stage from ring slot u; groups, remainder and the deferred abort as in riccati_mfma
+    auto stage = [&](const int u) {
+      X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
+      const double G = in[u][2];
+      const double nn0 = in[(u + 1) % PF][3], nn1 = in[(u + 1) % PF][4], nGm = in[(u + 1) % PF][5];
+      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
 #if MYR_SWEEP_CARRY
-        mfma_d4 C1 = D1c;      // (riccati_mfma: the zero upper half is inherited)
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-        D1c = D1;
+      mfma_d4 C1 = D1c;      // (riccati_mfma: the zero upper half is inherited)
+      C1[0] = fma(sh0, f_she, X0 * f_keep);
+      C1[1] = fma(sh1, f_she, X1 * f_keep);
+      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+      D1c = D1;
 #else
-        mfma_d4 C1;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        C1[2] = 0.0; C1[3] = 0.0;
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+      mfma_d4 C1;
+      C1[0] = fma(sh0, f_she, X0 * f_keep);
+      C1[1] = fma(sh1, f_she, X1 * f_keep);
+      C1[2] = 0.0; C1[3] = 0.0;
+      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
 #endif
-        mfma_d4 C2;
-        C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
+      mfma_d4 C2;
+      C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
 #if MYR_SWEEP_CARRY >= 2
-        C2[3] += QmU;
+      C2[3] += QmU;
 #endif
-        const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-        double m0 = nn0 + dv0, m1 = nn1 + dv1;
-        const double ms0 = W0::dpp_row_shr8(m0), ms1 = W0::dpp_row_shr8(m1);
+      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
+      double m0 = nn0 + dv0, m1 = nn1 + dv1;
+      const double ms0 = W0::dpp_row_shr8(m0), ms1 = W0::dpp_row_shr8(m1);
 #if MYR_SWEEP_CARRY
-        mfma_d4 Cm = Rmc;
-        Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-        Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-        const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
-        Rmc = Rm;
+      mfma_d4 Cm = Rmc;
+      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
+      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
+      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
+      Rmc = Rm;
 #else
-        mfma_d4 Cm;
-        Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-        Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-        Cm[2] = 0.0; Cm[3] = 0.0;
-        const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
+      mfma_d4 Cm;
+      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
+      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
+      Cm[2] = 0.0; Cm[3] = 0.0;
+      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
 #endif
 #if MYR_SWEEP_CARRY >= 2
-        Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-        QmU = Rm[1];
+      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
+      QmU = Rm[1];
 #else
-        mfma_d4 Cq;
-        Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
-        Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
+      mfma_d4 Cq;
+      Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
+      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
 #endif
-        const double q00 = W0::rdlane(D2[3], 12), q10 = W0::rdlane(D2[2], 12), q11 = W0::rdlane(D2[2], 8);
-        const double det = fma(q00, q11, -(q10 * q10));
-        const double rdet = fast_rcp(det);
-        const double b0 = D2[3], b1 = D2[2];
-        double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
-        double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
-        const bool rare_ = !(q00 > reg_floor) || !(det > reg_floor * q00);
-        if (uniform_if<true>(rare_)) {                                       // rare; a scalar branch (no matrix instruction inside an EXEC-masked region)
-          const double u00 = q00, u10 = q10, u11 = q11;
-          double d0 = u00;
-          if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
-          const double i0 = fast_rcp(d0);
-          const double l10 = u10 * i0;
-          double d1 = u11 - l10 * l10 * d0;
-          if (!(d1 > reg_floor)) { d1 = dmax(fabs(d1), reg_floor); ++nreg; }
-          if (uniform_if<true>(nreg > 0) && abort_u) return nreg;
-          const double i1 = fast_rcp(d1);
-          kk0 = b0; kk1 = b1;
-          kk1 -= l10 * kk0;
-          kk0 *= i0; kk1 *= i1;
-          kk0 -= l10 * kk1;
-        }
-        k_ptr[0] = kk0; k_ptr[k_str] = kk1;
-        k_ptr -= k_step;
-        const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
-        const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);
-        D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      const double q00 = W0::rdlane(D2[3], 12), q10 = W0::rdlane(D2[2], 12), q11 = W0::rdlane(D2[2], 8);
+      const double det = fma(q00, q11, -(q10 * q10));
+      const double rdet = fast_rcp(det);
+      const double b0 = D2[3], b1 = D2[2];
+      double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
+      double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
+      const bool rare_ = !(q00 > reg_floor) || !(det > reg_floor * q00);
+      if (uniform_if<true>(rare_)) {                                       // rare; a scalar branch (no matrix instruction inside an EXEC-masked region)
+        const double u00 = q00, u10 = q10, u11 = q11;
+        double d0 = u00;
+        if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
+        const double i0 = fast_rcp(d0);
+        const double l10 = u10 * i0;
+        double d1 = u11 - l10 * l10 * d0;
+        if (!(d1 > reg_floor)) { d1 = dmax(fabs(d1), reg_floor); ++nreg; }
+        const double i1 = fast_rcp(d1);
+        kk0 = b0; kk1 = b1;
+        kk1 -= l10 * kk0;
+        kk0 *= i0; kk1 *= i1;
+        kk0 -= l10 * kk1;
+      }
+      k_ptr[0] = kk0; k_ptr[k_str] = kk1;
+      k_ptr -= k_step;
+      const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
+      const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);
+      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_mfma)
+#pragma unroll
+      for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+    };
+    auto group = [&]() {
+#pragma unroll
+      for (int u = 0; u < PF; ++u) stage(u);
+    };
+    int kb = k_hi - 1;
+    if (kb - k_lo >= PF - 1) {
+      group();
+      for (kb -= PF; kb - k_lo >= PF - 1; kb -= PF) {
+        if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
+        group();
       }
     }
+#pragma unroll
+    for (int u = 0; u < PF - 1; ++u) {
+      if (kb - u < k_lo) break;
+      stage(u);
+    }
+    if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
     X0 = D3[0]; X1 = D3[1];
     const double T1 = D3[1], T2 = D3[2], T3 = D3[3];
     double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;      // T: rows nu_x (NS), then the row of nu_u
@@ -1528,7 +1569,7 @@ struct HsFused {
   __device__ static int riccati_mfma_trap(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
     using namespace detail;
     static_assert(!TRAP || NQ == 1, "one control");
-    const int lane = c.lane, N = c.N;
+    const int lane = c.lane, N = __builtin_amdgcn_readfirstlane(c.N);      // (wave-uniform: riccati_mfma)
     const int g = lane >> 4, j = lane & 15;
     const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
     const int ycol = scol >= 0 ? scol : ((j == 8 || j == 9) ? NW : -1);
@@ -1567,41 +1608,56 @@ struct HsFused {
     for (int u = 0; u < PF; ++u) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+      __builtin_amdgcn_sched_barrier(0);      // (slot by slot: riccati_mfma)
     }
     mfma_d4 D3 = {X0i, 0.0, 0.0, 0.0};
-    for (int kb = N - 1; kb >= 0; kb -= PF) {
+    // one stage from ring slot u; groups, remainder and the deferred abort as in riccati_mfma
+    auto stage = [&](const int u) {
+      const double X0 = D3[0] + (in[u][0] + dv0), X1 = fma(D3[1], f_x1, in[u][1] + dv1);
+      const double G = in[u][2];
+      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
+      mfma_d4 C1;
+      C1[0] = fma(sh0, f_she, X0 * f_keep);
+      C1[1] = fma(sh1, f_she, X1 * f_keep);
+      C1[2] = 0.0; C1[3] = 0.0;
+      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+      mfma_d4 C2;
+      C2[0] = 0.0; C2[1] = D3[1] * f_t1; C2[2] = fma(D3[2], f_t23, D1[1]); C2[3] = D3[3] * f_t23;
+      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
+      const double q11 = W0::rdlane(D2[2], 8);
+      double d = q11;
+      const bool rare_ = !(d > reg_floor);
+      if (uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(rare_)) {                                       // rare (same pivot rule as chol_reg); a scalar branch, see riccati_mfma
+        d = dmax(fabs(d), reg_floor); ++nreg;
+      }
+      const double kk = D2[2] * fast_rcp(d);
+      k_ptr[0] = kk;
+      k_ptr -= k_step;
+      const double A3 = D2[2] * f_a3;
+      const double B3 = g == 0 ? kk : 0.0;
+      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_mfma)
 #pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int k = kb - u;
-        if (k < 0) break;
-        const double X0 = D3[0] + (in[u][0] + dv0), X1 = fma(D3[1], f_x1, in[u][1] + dv1);
-        const double G = in[u][2];
+      for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+    };
+    auto group = [&]() {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-        const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
-        mfma_d4 C1;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        C1[2] = 0.0; C1[3] = 0.0;
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-        mfma_d4 C2;
-        C2[0] = 0.0; C2[1] = D3[1] * f_t1; C2[2] = fma(D3[2], f_t23, D1[1]); C2[3] = D3[3] * f_t23;
-        const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-        const double q11 = W0::rdlane(D2[2], 8);
-        double d = q11;
-        const bool rare_ = !(d > reg_floor);
-        if (uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(rare_)) {                                       // rare (same pivot rule as chol_reg); a scalar branch, see riccati_mfma
-          d = dmax(fabs(d), reg_floor); ++nreg;
-          if (abort_u) return nreg;
-        }
-        const double kk = D2[2] * fast_rcp(d);
-        k_ptr[0] = kk;
-        k_ptr -= k_step;
-        const double A3 = D2[2] * f_a3;
-        const double B3 = g == 0 ? kk : 0.0;
-        D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      for (int u = 0; u < PF; ++u) stage(u);
+    };
+    int kb = N - 1;
+    if (kb >= PF - 1) {
+      group();
+      for (kb -= PF; kb >= PF - 1; kb -= PF) {
+        if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
+        group();
       }
     }
+#pragma unroll
+    for (int u = 0; u < PF - 1; ++u) {
+      if (kb - u < 0) break;
+      stage(u);
+    }
+    if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
     const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
     if (scol >= 0 && j != 5) {
       if (rowx) c.sP[g * NW + scol] = X0;
@@ -2014,6 +2070,7 @@ struct HsFused {
   // The same for the trapezoidal scheme: riccati_mfma_trap over the stages [k_lo, k_hi) of one chunk (stage k ends at point k + 1; one eliminated control).
   __device__ static int riccati_chunk_trap(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int k_lo, int k_hi, bool last, double* xo) {
     using namespace detail;
+    k_lo = __builtin_amdgcn_readfirstlane(k_lo); k_hi = __builtin_amdgcn_readfirstlane(k_hi);      // (wave-uniform: scalar loop control, riccati_mfma)
     const int lane = c.lane;
     const int g = lane >> 4, j = lane & 15;
     const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
@@ -2054,41 +2111,56 @@ struct HsFused {
     for (int u = 0; u < PF; ++u) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+      __builtin_amdgcn_sched_barrier(0);      // (slot by slot: riccati_mfma)
     }
     mfma_d4 D3 = {X0i, X1i, 0.0, 0.0};
-    for (int kb = k_hi - 1; kb >= k_lo; kb -= PF) {
+    // one stage from ring slot u; groups, remainder and the deferred abort as in riccati_mfma
+    auto stage = [&](const int u) {
+      const double X0 = D3[0] + (in[u][0] + dv0), X1 = fma(D3[1], f_x1, in[u][1] + dv1);
+      const double G = in[u][2];
+      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
+      mfma_d4 C1;
+      C1[0] = fma(sh0, f_she, X0 * f_keep);
+      C1[1] = fma(sh1, f_she, X1 * f_keep);
+      C1[2] = 0.0; C1[3] = 0.0;
+      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+      mfma_d4 C2;
+      C2[0] = 0.0; C2[1] = D3[1] * f_t1; C2[2] = fma(D3[2], f_t23, D1[1]); C2[3] = D3[3] * f_t23;
+      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
+      const double q11 = W0::rdlane(D2[2], 8);
+      double d = q11;
+      const bool rare_ = !(d > reg_floor);
+      if (uniform_if<true>(rare_)) {
+        d = dmax(fabs(d), reg_floor); ++nreg;
+      }
+      const double kk = D2[2] * fast_rcp(d);
+      k_ptr[0] = kk;
+      k_ptr -= k_step;
+      const double A3 = D2[2] * f_a3;
+      const double B3 = g == 0 ? kk : 0.0;
+      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_mfma)
 #pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        const int k = kb - u;
-        if (k < k_lo) break;
-        const double X0 = D3[0] + (in[u][0] + dv0), X1 = fma(D3[1], f_x1, in[u][1] + dv1);
-        const double G = in[u][2];
+      for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
+    };
+    auto group = [&]() {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-        const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
-        mfma_d4 C1;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        C1[2] = 0.0; C1[3] = 0.0;
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-        mfma_d4 C2;
-        C2[0] = 0.0; C2[1] = D3[1] * f_t1; C2[2] = fma(D3[2], f_t23, D1[1]); C2[3] = D3[3] * f_t23;
-        const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-        const double q11 = W0::rdlane(D2[2], 8);
-        double d = q11;
-        const bool rare_ = !(d > reg_floor);
-        if (uniform_if<true>(rare_)) {
-          d = dmax(fabs(d), reg_floor); ++nreg;
-          if (abort_u) return nreg;
-        }
-        const double kk = D2[2] * fast_rcp(d);
-        k_ptr[0] = kk;
-        k_ptr -= k_step;
-        const double A3 = D2[2] * f_a3;
-        const double B3 = g == 0 ? kk : 0.0;
-        D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      for (int u = 0; u < PF; ++u) stage(u);
+    };
+    int kb = k_hi - 1;
+    if (kb - k_lo >= PF - 1) {
+      group();
+      for (kb -= PF; kb - k_lo >= PF - 1; kb -= PF) {
+        if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
+        group();
       }
     }
+#pragma unroll
+    for (int u = 0; u < PF - 1; ++u) {
+      if (kb - u < k_lo) break;
+      stage(u);
+    }
+    if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
     const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
     double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;
     if (scol >= 0 && j != 5) {
