@@ -31,10 +31,7 @@ namespace myriad {
 // it is a scalar branch (s_cbranch_scc), not an EXEC-masked region.  Used by the sweeps of the W > 1 kernels (inlined into a kernel whose
 // wavefronts take different paths; measured there: B = 256 / 512 kernel 2.95 / 3.10 ms against 3.01 / 3.15 ms); the sweep W = 1 calls as a
 // function keeps the per-lane form (all-or-none masks in uniform control flow, gated by the same tests: the scalar form costs it 1.6 %,
-// 14.55 against 14.33 ms -- profiles/r04/README.md).  -DMYR_SWEEP_UNIFORM=0 / 1 forces one form everywhere.
-#ifndef MYR_SWEEP_UNIFORM
-#define MYR_SWEEP_UNIFORM -1
-#endif
+// 14.55 against 14.33 ms -- profiles/r04/README.md; the switch that forced one form everywhere is in the history at 2373201).
 template <bool ON>
 __device__ inline bool uniform_if(bool c) {
   if constexpr (ON) return __builtin_amdgcn_readfirstlane((int)c) != 0;
@@ -138,36 +135,25 @@ struct HsFused {
   using D = HsSol<Sys>;
   static constexpr int NS = D::NS, NU = D::NU, NW = D::NW, NY = TRAP ? NS + 2 * NU : D::NY, NQ = TRAP ? NU : D::NQ, NC = D::NC, NY1 = NY + 1;
   static constexpr int QE = NQ - NU;
-  // Two-level sweep (round 6; -DMYR_TWO_LEVEL=0: round 5's form): the W wavefronts a trajectory owns each condense a CHUNK of N / W stages in parallel
-  // (riccati_chunk / riccati_chunk_trap), a small interface recursion joins the chunks (tl_join), see there.  Both collocation schemes on the hand-placed
+  // Two-level sweep (round 6; round 5's form is in the history at 2373201): the W wavefronts a trajectory owns each condense a CHUNK of N / W stages in parallel
+  // (riccati_tile<true> / riccati_tile_trap<true>), a small interface recursion joins the chunks (tl_join), see there.  Both collocation schemes on the hand-placed
   // tile (one control, NS <= 4).
-#ifndef MYR_EARLY_EXIT
-#define MYR_EARLY_EXIT 1       // (round 6) convergence tests and barrier update in front of the sweep in every kernel form (HsFused::solve): the converged iteration returns
-                               // without its sweep -- bit-identical results, 12.61 -> 12.45 ms per headline solve (tools/dev/exp/exp87.sh); 0: round 5's order
-#endif
-#ifndef MYR_SWEEP_CARRY
-#define MYR_SWEEP_CARRY 2      // (round 6) fewer operand moves in a sweep stage: 1 = C operands whose upper half is zero inherit it from the previous result instead of a zero
-                               // fill (bit-identical); 2 = also no C tuple for the midpoint product, its control rows are added where Q is consumed (last-bit differences, same
-                               // iteration counts): 788 -> 703 instructions per four stages, with the early exit 12.61 -> 12.25 ms per headline solve; 0: round 5's code
-#endif
-#ifndef MYR_TWO_LEVEL
-#define MYR_TWO_LEVEL 1
-#endif
-#ifndef MYR_TL_SPEC
-#define MYR_TL_SPEC 0           // 1: closed-form systems get a four-wavefront form for batches of at most one trajectory per CU -- two chunks x two rungs of the inertia
-                                // ladder at a time (HsFused::TLS).  Built and measured (tools/dev/exp/exp90.sh): the iterates of the two-wavefront form, bit for bit, and
-                                // B = 256 100.5 -> 103.7 k, B = 128 51.9 -> 53.3 k solves/s -- 3 % for 160 KB of code per system: off.
-#endif
+  // Decided in round 6, the other forms are in the history at 2373201:
+  //  * every kernel form runs the convergence tests and the barrier update in front of the sweep (HsFused::solve): the converged iteration returns without
+  //    its sweep -- bit-identical results, 12.61 -> 12.45 ms per headline solve;
+  //  * a sweep stage moves fewer operands: C operands whose upper half is zero inherit it from the previous result instead of a zero fill (bit-identical),
+  //    and the midpoint product has no C tuple, its control rows are added where Q is consumed (last-bit differences, same iteration counts): 788 -> 703
+  //    instructions per four stages, with the early exit 12.61 -> 12.25 ms per headline solve;
+  //  * a four-wavefront form of the closed-form systems for batches of at most one trajectory per CU (two chunks x two rungs of the inertia ladder at a
+  //    time) gave the iterates of the two-wavefront form, bit for bit, and B = 256 100.5 -> 103.7 k, B = 128 51.9 -> 53.3 k solves/s -- 3 % for 160 KB of
+  //    code per system: not in.  Four chunks instead measured equal to two (three sequential joins).
 #ifndef MYR_FWD_SEQ_NW
 #define MYR_FWD_SEQ_NW 7        // stages of at least this many knot variables run the forward phase's recursion sequentially (HsFused::FSEQ); 0: every system scans
-#endif
-#ifndef MYR_ZLU_GLOBAL_WIDE
-#define MYR_ZLU_GLOBAL_WIDE 1       // wide closed-form systems keep the bound multipliers in global scratch where that doubles the workgroups per CU (HsFused::ZLU_GLOBAL)
 #endif
 #ifndef MYR_TL_FLOOR
 #define MYR_TL_FLOOR 1e-10      // smallest pivot accepted in an interface's C = I + L^T M L (its eigenvalues lie in (0, ~1] when the reduced Hessian is positive definite)
 #endif
-  static constexpr bool TL = (MYR_TWO_LEVEL != 0) && W > 1 && (D::NU == 1 && D::NS <= 4);
+  static constexpr bool TL = W > 1 && NU == 1 && NS <= 4;
   static constexpr int MLAM = TRAP ? 1 : 2;        // multiplier blocks (NS each) per interval
   // Network dynamics (config 5, node_system.h): f, A, B of ALL points come from the matrix-core pass of node_mfma.h (MODE 1, every
   // wavefront of the workgroup takes every W-th tile of 16 points) into a global record the backward pass reads instead of calling
@@ -225,26 +211,18 @@ struct HsFused {
   static constexpr int XCH = 2 * W * NREC + 2 * W * NTOT + 2 * W * 2 * NS + W * NRED + 8;
   // sweep outputs in LDS: one block (P | pc | Tnu | Ku) per set; two-level form: one per chunk, the multiplier vector theta of every chunk (+ the chunks'
   // pivot counts), and per interface the four NW x NW maps of the join's forward pass
-  // TLS (closed-form systems, W = 4: batches of at most one trajectory per CU): TWO chunks and TWO rungs of the inertia ladder at a time -- wavefronts 0, 1
-  // sweep the chunks with delta, wavefronts 2, 3 the same chunks with the NEXT candidate (round 5's speculative rung on top of the two-level sweep: a failed
-  // rung costs a whole sweep + join, its successor is then already there; same sequence of candidates, first success wins).  Four chunks instead were
-  // measured equal to two (three sequential joins, tools/dev/exp/exp84.sh).
-  static constexpr bool TLS = TL && W == 4 && !NodeTraits<Sys>::mlp && (MYR_TL_SPEC != 0);
-  static constexpr int NCH = TLS ? 2 : W;       // chunks of a sweep
-  static constexpr int NGR = TLS ? 2 : 1;       // rungs swept side by side
-  static constexpr int NXB = TL ? NCH * NGR : (W > 1 ? 2 : 1);
-  static constexpr int TL_TH1 = NCH * NC, TL_JN1 = (NCH - 1) * 4 * NW * NW;      // per rung group: theta table; the interfaces' maps
-  static constexpr int TL_TH = TL ? NGR * TL_TH1 + NGR * (NCH + 1) + 2 : 0, TL_JN = TL ? NGR * TL_JN1 : 0;
+  static constexpr int NCH = W;                  // chunks of a sweep
+  static constexpr int NXB = TL ? NCH : (W > 1 ? 2 : 1);
+  static constexpr int TL_TH1 = NCH * NC, TL_JN1 = (NCH - 1) * 4 * NW * NW;      // theta table; the interfaces' maps
+  static constexpr int TL_TH = TL ? TL_TH1 + (NCH + 1) + 2 : 0, TL_JN = TL ? TL_JN1 : 0;
   __host__ __device__ static constexpr int lds_solver_doubles_z(int N, bool zlu_global) { return (zlu_global ? 2 : 4) * npoints(N) * NW + MLAM * N * NS + 6 * NW + XCH + NXB * EXCH + TL_TH + TL_JN + 8; }
   // Round 6: the same for the wide closed-form systems (at least MYR_FWD_SEQ_NW knot variables) in the forms whose LDS, with the multipliers resident, would
   // not let 4 / W workgroups onto a CU at the reference horizon of 100 intervals -- ROCKETLANDING's one-wavefront Hermite-Simpson form (65.6 -> 39.9 KB: four
   // per CU instead of two, 94.5 -> 65.0 ms per 4096 solves of 30 iterations), CARTPOLE's twin (192 -> 111 ms), ROCKETLANDING's twin (one-wavefront form
-  // 109 -> 64 KB, two-wavefront form 118 -> 73 KB: two per CU instead of one, 397 -> 205 ms); tools/dev/exp/exp97.sh.  -DMYR_ZLU_GLOBAL_WIDE=0: resident.
-#ifndef MYR_ZLU_FORCE
-#define MYR_ZLU_FORCE 0         // experiment (tools/dev/exp/exp110.sh): 1 = every one-wavefront closed-form kernel keeps the bound multipliers in scratch
-#endif
-  static constexpr bool ZLU_GLOBAL = (MLP && W == 2) || ((MYR_ZLU_FORCE != 0) && !MLP && W == 1) ||
-      ((MYR_ZLU_GLOBAL_WIDE != 0) && !MLP && (MYR_FWD_SEQ_NW > 0) && NW >= MYR_FWD_SEQ_NW && (long)lds_solver_doubles_z(100, false) * 8 > 40960L * W);
+  // 109 -> 64 KB, two-wavefront form 118 -> 73 KB: two per CU instead of one, 397 -> 205 ms).  (The headline kernel with its bound multipliers in scratch, to fit
+  // two workgroups per SIMD, lost: profiles/r06/README.md; that form and the resident form of the wide systems are in the history at 2373201.)
+  static constexpr bool ZLU_GLOBAL = (MLP && W == 2) ||
+      (!MLP && (MYR_FWD_SEQ_NW > 0) && NW >= MYR_FWD_SEQ_NW && (long)lds_solver_doubles_z(100, false) * 8 > 40960L * W);
   __host__ __device__ static int lds_solver_doubles(int N) { return lds_solver_doubles_z(N, ZLU_GLOBAL); }
   __host__ __device__ static int lds_doubles(int N) { return lds_solver_doubles(N) + (MLP ? npoints(N) * NS + NodeTraits<Sys>::lds_doubles : 0); }
   __host__ __device__ static size_t lds_bytes(int N) { return (size_t)lds_doubles(N) * 8; }
@@ -284,9 +262,6 @@ struct HsFused {
     c.kg = kg; c.sP = x; c.sPc = x + NW * NW; c.sTnu = c.sPc + NW * NC; c.sKu = c.sTnu + NS * NC;
   }
   __device__ static inline void wsync() {
-#ifdef MYR_WG_STRONG      // experiment: agent-scope fences around the workgroup barrier (s_waitcnt vmcnt(0) + L1 invalidate) when wavefronts share a trajectory
-    if constexpr (W > 1) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __syncthreads(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); return; }
-#endif
     __syncthreads();
   }
   // partial results of the W wavefronts -> the workgroup's (op: 0 sum, 1 max, 2 min); every wavefront ends with the same values
@@ -1122,25 +1097,44 @@ struct HsFused {
   }
 
   // ---- Riccati sweep on v_mfma_f64_16x16x4_f64: HsWave::riccati_mfma (tile slots, chaining, pivot rule: see there), reading
-  // the symmetric-packed point records; the prefetch ring reads PF stages below stage 0 into the padding in front of hr / st ----
+  // the symmetric-packed point records; the prefetch ring reads PF stages below stage 0 into the padding in front of hr / st.
+  // ONE body for the two uses of the tile.  CHUNK == false: the plain sweep over all N stages (k_lo_, k_hi_, last_, xo unused: the stage range
+  // is [0, N), `last` the constant true), results to sP | sPc | sTnu, then the first point.  CHUNK == true: level 1 of the two-level sweep,
+  // the stages [k_lo, k_hi) of ONE chunk.  What differs is loop-invariant setup and the epilogue; the ring fill, the stage, the groups and
+  // the deferred abort exist once. ----
+  // Two-level sweep: the recursion over the stages is sequential and, in one wavefront, issue-bound (profiles/r05/sweep_issue_bound.md); the W wavefronts a
+  // trajectory owns at small batch sizes can only share it if every wavefront starts somewhere.  Chunk c < W - 1 therefore starts at its end knot
+  // e from the terminal form  rho/2 |w_e|^2 + nu^T w_e  with the NW multipliers nu of the continuity condition w_e = w_a(chunk c + 1) as
+  // right-hand-side COLUMNS -- exactly what the tile already does for the pinned terminal states of the last stage (the nu_T columns; here every
+  // row is "pinned", and the control row's multiplier takes the slot of the mu column: the barrier parameter is known before the sweep, so the
+  // caller folds g0 + mu g1 into the "1" column -- tl_fold).  The last chunk is the plain sweep down to its first stage.  A chunk returns the
+  // symmetric form over (w_a ; theta_c), theta_c = (1, nu_u, nu_x):  P | pc | T  -- T row m = d/d nu_m of the chunk's value = the end knot w_e as an
+  // affine function of theta_c (the plain sweep's terminal-multiplier bookkeeping, with the control's row 7 kept as well) -- in ONE exchange block
+  // (the layout of sP | sPc | sTnu | sKu, the control's T row where sKu is); tl_join eliminates the multipliers.  Gains K | kc as before (kc column
+  // 1 now multiplies nu_u).  Same pivot rule; no first point.
   typedef double mfma_d4 __attribute__((ext_vector_type(4)));
-  __device__ static int riccati_mfma(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
+  template <bool CHUNK>
+  __device__ static int riccati_tile(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int k_lo_, int k_hi_, bool last_, double* xo) {
     using namespace detail;
-    const int lane = c.lane, N = __builtin_amdgcn_readfirstlane(c.N);      // (wave-uniform: the loop over the stages is scalar control flow)
+    // (wave-uniform: the loop over the stages is scalar control flow; the plain sweep sees the constants 0 and true, not operands)
+    const int k_lo = CHUNK ? __builtin_amdgcn_readfirstlane(k_lo_) : 0, k_hi = __builtin_amdgcn_readfirstlane(CHUNK ? k_hi_ : c.N);
+    const bool last = CHUNK ? last_ : true;
+    static_assert(!CHUNK || (NC == NS + 2 && NU == 1), "slot 7 takes the control's multiplier");
+    const int lane = c.lane;
     const int g = lane >> 4, j = lane & 15;
     const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
     const int ycol = scol >= 0 ? scol : ((j == 12 || j == 13) ? NS + 1 : ((j == 8 || j == 9) ? NS + 2 : -1));
     const int cc = j == 6 ? 0 : (j == 7 ? 1 : (j == 10 ? 2 : (j == 11 ? 3 : (j == 14 ? 4 : (j == 15 ? 5 : -1)))));
     const int rcc = (cc >= 0 && cc < NC) ? cc : -1;
     const bool rowx = g < NS;
-    const double* he = c.hr + (long)(2 * (N - 1) + 2) * HR_N;
+    const double* he = c.hr + (long)(2 * (k_hi - 1) + 2) * HR_N;
     const double* hm = he - HR_N;
-    const double* st = c.st + (long)(N - 1) * SG_N;
+    const double* st = c.st + (long)(k_hi - 1) * SG_N;
     auto hsel = [&](const double* rec, int row, bool on) -> const double* {
       if (!on) return c.zr;
       if (scol >= 0) return rec + HR_H + (scol <= row ? scol * NW - scol * (scol - 1) / 2 + (row - scol) : row * NW - row * (row - 1) / 2 + (scol - row));
-      if (rcc == 0) return rec + HR_G0 + row;
-      if (rcc == 1) return rec + HR_G1 + row;
+      if (rcc == 0) return rec + HR_G0 + row;      // (a chunk: g0 + mu g1, folded by the caller)
+      if constexpr (!CHUNK) { if (rcc == 1) return rec + HR_G1 + row; }
       return c.zr;
     };
     auto gsel = [&](int off) -> const double* {
@@ -1153,23 +1147,27 @@ struct HsFused {
     long stp[6];
 #pragma unroll
     for (int q = 0; q < 6; ++q) stp[q] = (ptr[q] == c.zr) ? 0 : ((q == 2 || q == 5) ? (long)SG_N : 2L * HR_N);
-    const bool pinr = rowx && c.term_pinned[rowx ? g : 0];
-    double X0 = (pinr && scol == g) ? o.rho_term - delta : ((pinr && rcc == 2 + g) ? 1.0 : 0.0), X1 = 0.0;
+    const bool pinr = rowx && (!last || c.term_pinned[rowx ? g : 0]);
+    // (a pinned terminal state takes no inertia correction: rho - delta, the stage adds delta back; an interface knot is an ordinary point whose
+    // Hessian record -- with its delta -- is added by the chunk's last stage on top of the terminal form rho)
+    const double rho0 = last ? o.rho_term - delta : o.rho_term;
+    double X0 = (pinr && scol == g) ? rho0 : ((pinr && rcc == 2 + g) ? 1.0 : 0.0);
+    double X1 = (!last && g < 2) ? (scol == NS ? rho0 : (rcc == 1 ? 1.0 : 0.0)) : 0.0;
     const double dv0 = (rowx && scol == g) ? delta : 0.0, dv1 = (g < 2 && scol == NS) ? delta : 0.0;
     const double f_a1 = j < 6 ? 1.0 : 0.0;
     const double f_keep = rcc >= 0 ? 1.0 : 0.0;
     const double f_she = (j == 8 || j == 9) ? 1.0 : 0.0, f_shm = (j == 12 || j == 13) ? 1.0 : 0.0;
-    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = g == 2 ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;
-    const bool a3_on = g < 2 && (j < 6 || j == 10 || j == 11 || j == 14 || j == 15);
+    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = (CHUNK ? g >= 2 : g == 2) ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;      // (a chunk carries row 7 -- the control's multiplier -- like row 6)
+    const bool a3_on = g < 2 && (j < 6 || (CHUNK && j == 7) || j == 10 || j == 11 || j == 14 || j == 15);          // ... and takes the rank-2 update like the rows nu_x
     const double f_a3m = (a3_on && g == 0) ? -1.0 : 0.0, f_a3e = (a3_on && g == 1) ? -1.0 : 0.0;
     const int k_off = (g == 0 && scol >= 0 && j != 5) ? scol : ((g == 0 && rcc >= 0) ? NQ * NW + rcc : -1);
     const int k_str = k_off < 0 ? 1 : ((scol >= 0) ? NW : NC);
-    double* k_ptr = k_off >= 0 ? c.kg + (long)(N - 1) * KSTR + k_off : c.zr + ZR - 2;
+    double* k_ptr = k_off >= 0 ? c.kg + (long)(k_hi - 1) * KSTR + k_off : c.zr + ZR - 2;
     const long k_step = k_off >= 0 ? KSTR : 0;
     double reg_floor = o.reg_floor;
     asm volatile("" : "+v"(reg_floor));
     int nreg = 0;
-    const bool abort_u = uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(abort_on_reg);
+    const bool abort_u = uniform_if<(W > 1)>(abort_on_reg);
     double in[PF][6];
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
@@ -1177,19 +1175,6 @@ struct HsFused {
       for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
       __builtin_amdgcn_sched_barrier(0);      // (slot by slot, in ring order: the loop's first stage then waits for slot 0 alone, not for the youngest loads)
     }
-    auto mid_part = [&](double n0, double n1, double Gm) -> mfma_d4 {
-      n0 += dv0; n1 += dv1;
-      const double s0 = W0::dpp_row_shr8(n0), s1 = W0::dpp_row_shr8(n1);
-      mfma_d4 C;
-      C[0] = fma(s0, f_shm, n0 * f_keep);
-      C[1] = fma(s1, f_shm, n1 * f_keep);
-      C[2] = 0.0; C[3] = 0.0;
-      const mfma_d4 R = __builtin_amdgcn_mfma_f64_16x16x4f64(n0 * f_a1, Gm, C, 0, 0, 0);
-      mfma_d4 C2;
-      C2[0] = 0.0; C2[1] = 0.0; C2[2] = 0.0; C2[3] = R[1];
-      return __builtin_amdgcn_mfma_f64_16x16x4f64(Gm, R[0], C2, 0, 0, 0);
-    };
-#if MYR_SWEEP_CARRY >= 2
     double QmU = 0.0;
     mfma_d4 Qm;
     {
@@ -1203,21 +1188,14 @@ struct HsFused {
       Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(in[0][5], R[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
       QmU = R[1];
     }
-#else
-    mfma_d4 Qm = mid_part(in[0][3], in[0][4], in[0][5]);
-#endif
     mfma_d4 D3 = {X0, X1, 0.0, 0.0};
-#if MYR_SWEEP_CARRY
     mfma_d4 D1c = {0.0, 0.0, 0.0, 0.0}, Rmc = {0.0, 0.0, 0.0, 0.0};
-
-#endif
     // one stage from ring slot u
     auto stage = [&](const int u) {
       X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
       const double G = in[u][2];
       const double nn0 = in[(u + 1) % PF][3], nn1 = in[(u + 1) % PF][4], nGm = in[(u + 1) % PF][5];
       const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
-#if MYR_SWEEP_CARRY
       // (rows 8..15 of R~ are zero -- the A operand has no such rows -- and stay zero from stage to stage: the previous result IS the next C operand's
       //  upper half, no zero fill)
       mfma_d4 C1 = D1c;
@@ -1225,45 +1203,22 @@ struct HsFused {
       C1[1] = fma(sh1, f_she, X1 * f_keep);
       const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
       D1c = D1;
-#else
-      mfma_d4 C1;
-      C1[0] = fma(sh0, f_she, X0 * f_keep);
-      C1[1] = fma(sh1, f_she, X1 * f_keep);
-      C1[2] = 0.0; C1[3] = 0.0;
-      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-#endif
       mfma_d4 C2;
       C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
-#if MYR_SWEEP_CARRY >= 2
       C2[3] += QmU;
-#endif
       const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
       // midpoint part of stage k-1 (independent of the recursion): issued HERE, so that its two dependent products run on
       // the matrix pipe while the vector pipe waits for D2 and computes the gains -- behind D3 they delayed the next stage's D1
       double m0 = nn0 + dv0, m1 = nn1 + dv1;
       const double ms0 = W0::dpp_row_shr8(m0), ms1 = W0::dpp_row_shr8(m1);
-#if MYR_SWEEP_CARRY
       mfma_d4 Cm = Rmc;
       Cm[0] = fma(ms0, f_shm, m0 * f_keep);
       Cm[1] = fma(ms1, f_shm, m1 * f_keep);
       const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
       Rmc = Rm;
-#else
-      mfma_d4 Cm;
-      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-      Cm[2] = 0.0; Cm[3] = 0.0;
-      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
-#endif
-#if MYR_SWEEP_CARRY >= 2
       // (the control rows of R enter rows 12..15 of Q: added where Q is consumed -- QmU -- instead of through a C operand that is zero but for them)
       Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
       QmU = Rm[1];
-#else
-      mfma_d4 Cq;
-      Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
-      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
-#endif
       const double q00 = W0::rdlane(D2[3], 12), q10 = W0::rdlane(D2[2], 12), q11 = W0::rdlane(D2[2], 8);
       const double det = fma(q00, q11, -(q10 * q10));
       const double rdet = fast_rcp(det);
@@ -1274,7 +1229,7 @@ struct HsFused {
       //  vector unit and, in the W > 1 kernels, made a SCALAR branch through readfirstlane, so that no matrix instruction of their sweep
       //  sits inside an EXEC-masked region: v_mfma does not honour EXEC on this part, tools/dev/litmus/mfma_exec.hip)
       const bool rare_ = !(q00 > reg_floor) || !(det > reg_floor * q00);
-      if (uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(rare_)) {                                       // rare
+      if (uniform_if<(W > 1)>(rare_)) {                                       // rare
         const double u00 = q00, u10 = q10, u11 = q11;
         double d0 = u00;
         if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
@@ -1311,222 +1266,6 @@ struct HsFused {
 #pragma unroll
       for (int u = 0; u < PF; ++u) stage(u);
     };
-    int kb = N - 1;
-    if (kb >= PF - 1) {
-      group();
-      for (kb -= PF; kb >= PF - 1; kb -= PF) {
-        if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
-        group();
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < PF - 1; ++u) {
-      if (kb - u < 0) break;
-      stage(u);
-    }
-    if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
-    X0 = D3[0]; X1 = D3[1];
-    const double T1 = D3[1], T2 = D3[2], T3 = D3[3];
-    if (scol >= 0 && j != 5) {
-      if (rowx) c.sP[g * NW + scol] = X0;
-      if (g == 0) c.sP[NS * NW + scol] = X1;
-    }
-    if (rcc >= 0) {
-      if (rowx) c.sPc[g * NC + rcc] = X0;
-      if (g == 0) c.sPc[NS * NC + rcc] = X1;
-      if (g >= 2 && g - 2 < NS) c.sTnu[(g - 2) * NC + rcc] = T2;
-      if (g >= 2 && g < NS) c.sTnu[g * NC + rcc] = T3;
-    }
-    wave_sync<true>();
-    if (g == 2 && rcc >= 2) c.sTnu[(rcc - 2) * NC + 0] += T1;
-    wave_sync<true>();
-    return riccati_first_point(c, o, delta, nreg);
-  }
-
-  // ---- Two-level sweep, level 1: the stages [k_lo, k_hi) of ONE chunk on the tile of riccati_mfma -----------------------------------------
-  // The recursion over the stages is sequential and, in one wavefront, issue-bound (profiles/r05/sweep_issue_bound.md); the W wavefronts a
-  // trajectory owns at small batch sizes can only share it if every wavefront starts somewhere.  Chunk c < W - 1 therefore starts at its end knot
-  // e from the terminal form  rho/2 |w_e|^2 + nu^T w_e  with the NW multipliers nu of the continuity condition w_e = w_a(chunk c + 1) as
-  // right-hand-side COLUMNS -- exactly what the tile already does for the pinned terminal states of the last stage (the nu_T columns; here every
-  // row is "pinned", and the control row's multiplier takes the slot of the mu column: the barrier parameter is known before the sweep, so the
-  // caller folds g0 + mu g1 into the "1" column -- tl_fold).  The last chunk is the plain sweep down to its first stage.  A chunk returns the
-  // symmetric form over (w_a ; theta_c), theta_c = (1, nu_u, nu_x):  P | pc | T  -- T row m = d/d nu_m of the chunk's value = the end knot w_e as an
-  // affine function of theta_c (riccati_mfma's terminal-multiplier bookkeeping, with the control's row 7 kept as well) -- in ONE exchange block
-  // (the layout of sP | sPc | sTnu | sKu, the control's T row where sKu is); tl_join eliminates the multipliers.  Gains K | kc as before (kc column
-  // 1 now multiplies nu_u).  Same pivot rule; no first point.
-  __device__ static int riccati_chunk(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int k_lo, int k_hi, bool last, double* xo) {
-    using namespace detail;
-    k_lo = __builtin_amdgcn_readfirstlane(k_lo); k_hi = __builtin_amdgcn_readfirstlane(k_hi);      // (wave-uniform: scalar loop control, riccati_mfma)
-    static_assert(!TL || (NC == NS + 2 && NU == 1), "slot 7 takes the control's multiplier");
-    const int lane = c.lane;
-    const int g = lane >> 4, j = lane & 15;
-    const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
-    const int ycol = scol >= 0 ? scol : ((j == 12 || j == 13) ? NS + 1 : ((j == 8 || j == 9) ? NS + 2 : -1));
-    const int cc = j == 6 ? 0 : (j == 7 ? 1 : (j == 10 ? 2 : (j == 11 ? 3 : (j == 14 ? 4 : (j == 15 ? 5 : -1)))));
-    const int rcc = (cc >= 0 && cc < NC) ? cc : -1;
-    const bool rowx = g < NS;
-    const double* he = c.hr + (long)(2 * (k_hi - 1) + 2) * HR_N;
-    const double* hm = he - HR_N;
-    const double* st = c.st + (long)(k_hi - 1) * SG_N;
-    auto hsel = [&](const double* rec, int row, bool on) -> const double* {
-      if (!on) return c.zr;
-      if (scol >= 0) return rec + HR_H + (scol <= row ? scol * NW - scol * (scol - 1) / 2 + (row - scol) : row * NW - row * (row - 1) / 2 + (scol - row));
-      if (rcc == 0) return rec + HR_G0 + row;      // (g0 + mu g1: folded by the caller)
-      return c.zr;
-    };
-    auto gsel = [&](int off) -> const double* {
-      if (!rowx) return c.zr;
-      if (ycol >= 0) return st + off + g * NY1 + ycol;
-      if (rcc == 0) return st + off + g * NY1 + NY;
-      return c.zr;
-    };
-    const double* ptr[6] = {hsel(he, g, rowx), hsel(he, NS, g < 2), gsel(SG_GE), hsel(hm, g, rowx), hsel(hm, NS, g < 2), gsel(SG_GM)};
-    long stp[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) stp[q] = (ptr[q] == c.zr) ? 0 : ((q == 2 || q == 5) ? (long)SG_N : 2L * HR_N);
-    const bool pinr = rowx && (!last || c.term_pinned[rowx ? g : 0]);
-    // (a pinned terminal state takes no inertia correction: rho - delta, the stage adds delta back; an interface knot is an ordinary point whose
-    // Hessian record -- with its delta -- is added by the chunk's last stage on top of the terminal form rho)
-    const double rho0 = last ? o.rho_term - delta : o.rho_term;
-    double X0 = (pinr && scol == g) ? rho0 : ((pinr && rcc == 2 + g) ? 1.0 : 0.0);
-    double X1 = (!last && g < 2) ? (scol == NS ? rho0 : (rcc == 1 ? 1.0 : 0.0)) : 0.0;
-    const double dv0 = (rowx && scol == g) ? delta : 0.0, dv1 = (g < 2 && scol == NS) ? delta : 0.0;
-    const double f_a1 = j < 6 ? 1.0 : 0.0;
-    const double f_keep = rcc >= 0 ? 1.0 : 0.0;
-    const double f_she = (j == 8 || j == 9) ? 1.0 : 0.0, f_shm = (j == 12 || j == 13) ? 1.0 : 0.0;
-    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = g >= 2 ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;      // (row 7 -- the control's multiplier -- is carried like row 6)
-    const bool a3_on = g < 2 && (j < 6 || j == 7 || j == 10 || j == 11 || j == 14 || j == 15);          // ... and takes the rank-2 update like the rows nu_x
-    const double f_a3m = (a3_on && g == 0) ? -1.0 : 0.0, f_a3e = (a3_on && g == 1) ? -1.0 : 0.0;
-    const int k_off = (g == 0 && scol >= 0 && j != 5) ? scol : ((g == 0 && rcc >= 0) ? NQ * NW + rcc : -1);
-    const int k_str = k_off < 0 ? 1 : ((scol >= 0) ? NW : NC);
-    double* k_ptr = k_off >= 0 ? c.kg + (long)(k_hi - 1) * KSTR + k_off : c.zr + ZR - 2;
-    const long k_step = k_off >= 0 ? KSTR : 0;
-    double reg_floor = o.reg_floor;
-    asm volatile("" : "+v"(reg_floor));
-    int nreg = 0;
-    const bool abort_u = uniform_if<true>(abort_on_reg);
-    double in[PF][6];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-#pragma unroll
-      for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-      __builtin_amdgcn_sched_barrier(0);      // (slot by slot: riccati_mfma)
-    }
-    auto mid_part = [&](double n0, double n1, double Gm) -> mfma_d4 {
-      n0 += dv0; n1 += dv1;
-      const double s0 = W0::dpp_row_shr8(n0), s1 = W0::dpp_row_shr8(n1);
-      mfma_d4 C;
-      C[0] = fma(s0, f_shm, n0 * f_keep);
-      C[1] = fma(s1, f_shm, n1 * f_keep);
-      C[2] = 0.0; C[3] = 0.0;
-      const mfma_d4 R = __builtin_amdgcn_mfma_f64_16x16x4f64(n0 * f_a1, Gm, C, 0, 0, 0);
-      mfma_d4 C2;
-      C2[0] = 0.0; C2[1] = 0.0; C2[2] = 0.0; C2[3] = R[1];
-      return __builtin_amdgcn_mfma_f64_16x16x4f64(Gm, R[0], C2, 0, 0, 0);
-    };
-#if MYR_SWEEP_CARRY >= 2
-    double QmU = 0.0;
-    mfma_d4 Qm;
-    {
-      double n0 = in[0][3] + dv0, n1 = in[0][4] + dv1;
-      const double s0 = W0::dpp_row_shr8(n0), s1 = W0::dpp_row_shr8(n1);
-      mfma_d4 C;
-      C[0] = fma(s0, f_shm, n0 * f_keep);
-      C[1] = fma(s1, f_shm, n1 * f_keep);
-      C[2] = 0.0; C[3] = 0.0;
-      const mfma_d4 R = __builtin_amdgcn_mfma_f64_16x16x4f64(n0 * f_a1, in[0][5], C, 0, 0, 0);
-      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(in[0][5], R[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-      QmU = R[1];
-    }
-#else
-    mfma_d4 Qm = mid_part(in[0][3], in[0][4], in[0][5]);
-#endif
-    mfma_d4 D3 = {X0, X1, 0.0, 0.0};
-#if MYR_SWEEP_CARRY
-    mfma_d4 D1c = {0.0, 0.0, 0.0, 0.0}, Rmc = {0.0, 0.0, 0.0, 0.0};
-#endif
-    // one stage from ring slot u; groups, remainder and the deferred abort as in riccati_mfma
-    auto stage = [&](const int u) {
-      X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
-      const double G = in[u][2];
-      const double nn0 = in[(u + 1) % PF][3], nn1 = in[(u + 1) % PF][4], nGm = in[(u + 1) % PF][5];
-      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
-#if MYR_SWEEP_CARRY
-      mfma_d4 C1 = D1c;      // (riccati_mfma: the zero upper half is inherited)
-      C1[0] = fma(sh0, f_she, X0 * f_keep);
-      C1[1] = fma(sh1, f_she, X1 * f_keep);
-      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-      D1c = D1;
-#else
-      mfma_d4 C1;
-      C1[0] = fma(sh0, f_she, X0 * f_keep);
-      C1[1] = fma(sh1, f_she, X1 * f_keep);
-      C1[2] = 0.0; C1[3] = 0.0;
-      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-#endif
-      mfma_d4 C2;
-      C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
-#if MYR_SWEEP_CARRY >= 2
-      C2[3] += QmU;
-#endif
-      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-      double m0 = nn0 + dv0, m1 = nn1 + dv1;
-      const double ms0 = W0::dpp_row_shr8(m0), ms1 = W0::dpp_row_shr8(m1);
-#if MYR_SWEEP_CARRY
-      mfma_d4 Cm = Rmc;
-      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
-      Rmc = Rm;
-#else
-      mfma_d4 Cm;
-      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-      Cm[2] = 0.0; Cm[3] = 0.0;
-      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
-#endif
-#if MYR_SWEEP_CARRY >= 2
-      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-      QmU = Rm[1];
-#else
-      mfma_d4 Cq;
-      Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
-      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
-#endif
-      const double q00 = W0::rdlane(D2[3], 12), q10 = W0::rdlane(D2[2], 12), q11 = W0::rdlane(D2[2], 8);
-      const double det = fma(q00, q11, -(q10 * q10));
-      const double rdet = fast_rcp(det);
-      const double b0 = D2[3], b1 = D2[2];
-      double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
-      double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
-      const bool rare_ = !(q00 > reg_floor) || !(det > reg_floor * q00);
-      if (uniform_if<true>(rare_)) {                                       // rare; a scalar branch (no matrix instruction inside an EXEC-masked region)
-        const double u00 = q00, u10 = q10, u11 = q11;
-        double d0 = u00;
-        if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
-        const double i0 = fast_rcp(d0);
-        const double l10 = u10 * i0;
-        double d1 = u11 - l10 * l10 * d0;
-        if (!(d1 > reg_floor)) { d1 = dmax(fabs(d1), reg_floor); ++nreg; }
-        const double i1 = fast_rcp(d1);
-        kk0 = b0; kk1 = b1;
-        kk1 -= l10 * kk0;
-        kk0 *= i0; kk1 *= i1;
-        kk0 -= l10 * kk1;
-      }
-      k_ptr[0] = kk0; k_ptr[k_str] = kk1;
-      k_ptr -= k_step;
-      const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
-      const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);
-      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
-      // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_mfma)
-#pragma unroll
-      for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-    };
-    auto group = [&]() {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) stage(u);
-    };
     int kb = k_hi - 1;
     if (kb - k_lo >= PF - 1) {
       group();
@@ -1543,139 +1282,45 @@ struct HsFused {
     if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
     X0 = D3[0]; X1 = D3[1];
     const double T1 = D3[1], T2 = D3[2], T3 = D3[3];
-    double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;      // T: rows nu_x (NS), then the row of nu_u
-    if (scol >= 0 && j != 5) {
-      if (rowx) xP[g * NW + scol] = X0;
-      if (g == 0) xP[NS * NW + scol] = X1;
+    if constexpr (!CHUNK) {
+      if (scol >= 0 && j != 5) {
+        if (rowx) c.sP[g * NW + scol] = X0;
+        if (g == 0) c.sP[NS * NW + scol] = X1;
+      }
+      if (rcc >= 0) {
+        if (rowx) c.sPc[g * NC + rcc] = X0;
+        if (g == 0) c.sPc[NS * NC + rcc] = X1;
+        if (g >= 2 && g - 2 < NS) c.sTnu[(g - 2) * NC + rcc] = T2;
+        if (g >= 2 && g < NS) c.sTnu[g * NC + rcc] = T3;
+      }
+      wave_sync<true>();
+      if (g == 2 && rcc >= 2) c.sTnu[(rcc - 2) * NC + 0] += T1;
+      wave_sync<true>();
+      return riccati_first_point(c, o, delta, nreg);
+    } else {
+      double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;      // T: rows nu_x (NS), then the row of nu_u
+      if (scol >= 0 && j != 5) {
+        if (rowx) xP[g * NW + scol] = X0;
+        if (g == 0) xP[NS * NW + scol] = X1;
+      }
+      if (rcc >= 0) {
+        if (rowx) xPc[g * NC + rcc] = X0;
+        if (g == 0) xPc[NS * NC + rcc] = X1;
+        if (g >= 2 && g - 2 < NS) xT[(g - 2) * NC + rcc] = T2;
+        if (g >= 2 && g < NS) xT[g * NC + rcc] = T3;
+        if (g == 3) xT[NS * NC + rcc] = T1;
+      }
+      wave_sync<true>();
+      // the part of T[nu_m]["1"] that the products leave in row "1" (g^T pc', as in the plain sweep)
+      if (g == 2 && rcc >= 2) xT[(rcc - 2) * NC + 0] += T1;
+      if (g == 2 && rcc == 1) xT[NS * NC + 0] += T1;
+      wave_sync<true>();
+      return nreg;
     }
-    if (rcc >= 0) {
-      if (rowx) xPc[g * NC + rcc] = X0;
-      if (g == 0) xPc[NS * NC + rcc] = X1;
-      if (g >= 2 && g - 2 < NS) xT[(g - 2) * NC + rcc] = T2;
-      if (g >= 2 && g < NS) xT[g * NC + rcc] = T3;
-      if (g == 3) xT[NS * NC + rcc] = T1;
-    }
-    wave_sync<true>();
-    // the part of T[nu_m]["1"] that the products leave in row "1" (g^T pc', riccati_mfma)
-    if (g == 2 && rcc >= 2) xT[(rcc - 2) * NC + 0] += T1;
-    if (g == 2 && rcc == 1) xT[NS * NC + 0] += T1;
-    wave_sync<true>();
-    return nreg;
   }
 
-  // The same sweep for the trapezoidal scheme (HsWave::riccati_mfma_trap): y = (dx_s, du_s, du_e), ONE eliminated control per stage, no
-  // midpoint part -- three matrix instructions per stage, the single pivot Q[du_e][du_e] read from lane 8 of register 2; the end point
-  // of stage k is point k + 1.
-  __device__ static int riccati_mfma_trap(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
-    using namespace detail;
-    static_assert(!TRAP || NQ == 1, "one control");
-    const int lane = c.lane, N = __builtin_amdgcn_readfirstlane(c.N);      // (wave-uniform: riccati_mfma)
-    const int g = lane >> 4, j = lane & 15;
-    const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
-    const int ycol = scol >= 0 ? scol : ((j == 8 || j == 9) ? NW : -1);
-    const int cc = j == 6 ? 0 : (j == 7 ? 1 : (j == 10 ? 2 : (j == 11 ? 3 : (j == 14 ? 4 : (j == 15 ? 5 : -1)))));
-    const int rcc = (cc >= 0 && cc < NC) ? cc : -1;
-    const bool rowx = g < NS;
-    const double* he = c.hr + (long)N * HR_N;
-    const double* st = c.st + (long)(N - 1) * SG_N;
-    auto hsel = [&](int row, bool on) -> const double* {
-      if (!on) return c.zr;
-      if (scol >= 0) return he + HR_H + (scol <= row ? scol * NW - scol * (scol - 1) / 2 + (row - scol) : row * NW - row * (row - 1) / 2 + (scol - row));
-      if (rcc == 0) return he + HR_G0 + row;
-      if (rcc == 1) return he + HR_G1 + row;
-      return c.zr;
-    };
-    const double* ptr[3] = {hsel(g, rowx), hsel(NS, g < 2),
-                            !rowx ? c.zr : (ycol >= 0 ? st + SG_GE + g * NY1 + ycol : (rcc == 0 ? st + SG_GE + g * NY1 + NY : c.zr))};
-    long stp[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) stp[q] = (ptr[q] == c.zr) ? 0 : (q == 2 ? (long)SG_N : (long)HR_N);
-    const bool pinr = rowx && c.term_pinned[rowx ? g : 0];
-    const double X0i = (pinr && scol == g) ? o.rho_term - delta : ((pinr && rcc == 2 + g) ? 1.0 : 0.0);
-    const double dv0 = (rowx && scol == g) ? delta : 0.0, dv1 = (g < 2 && scol == NS) ? delta : 0.0;
-    const double f_a1 = j < 6 ? 1.0 : 0.0, f_keep = rcc >= 0 ? 1.0 : 0.0, f_she = (j == 8 || j == 9) ? 1.0 : 0.0;
-    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = g == 2 ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;
-    const double f_a3 = (g == 0 && (j < 6 || j == 10 || j == 11 || j == 14 || j == 15)) ? -1.0 : 0.0;
-    const int k_off = (g == 0 && scol >= 0 && j != 5) ? scol : ((g == 0 && rcc >= 0) ? NQ * NW + rcc : -1);
-    double* k_ptr = k_off >= 0 ? c.kg + (long)(N - 1) * KSTR + k_off : c.zr + ZR - 2;
-    const long k_step = k_off >= 0 ? KSTR : 0;
-    double reg_floor = o.reg_floor;
-    asm volatile("" : "+v"(reg_floor));
-    int nreg = 0;
-    const bool abort_u = uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(abort_on_reg);
-    double in[PF][3];
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-      __builtin_amdgcn_sched_barrier(0);      // (slot by slot: riccati_mfma)
-    }
-    mfma_d4 D3 = {X0i, 0.0, 0.0, 0.0};
-    // one stage from ring slot u; groups, remainder and the deferred abort as in riccati_mfma
-    auto stage = [&](const int u) {
-      const double X0 = D3[0] + (in[u][0] + dv0), X1 = fma(D3[1], f_x1, in[u][1] + dv1);
-      const double G = in[u][2];
-      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
-      mfma_d4 C1;
-      C1[0] = fma(sh0, f_she, X0 * f_keep);
-      C1[1] = fma(sh1, f_she, X1 * f_keep);
-      C1[2] = 0.0; C1[3] = 0.0;
-      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-      mfma_d4 C2;
-      C2[0] = 0.0; C2[1] = D3[1] * f_t1; C2[2] = fma(D3[2], f_t23, D1[1]); C2[3] = D3[3] * f_t23;
-      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-      const double q11 = W0::rdlane(D2[2], 8);
-      double d = q11;
-      const bool rare_ = !(d > reg_floor);
-      if (uniform_if<(MYR_SWEEP_UNIFORM < 0 ? (W > 1) : (MYR_SWEEP_UNIFORM != 0))>(rare_)) {                                       // rare (same pivot rule as chol_reg); a scalar branch, see riccati_mfma
-        d = dmax(fabs(d), reg_floor); ++nreg;
-      }
-      const double kk = D2[2] * fast_rcp(d);
-      k_ptr[0] = kk;
-      k_ptr -= k_step;
-      const double A3 = D2[2] * f_a3;
-      const double B3 = g == 0 ? kk : 0.0;
-      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
-      // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_mfma)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-    };
-    auto group = [&]() {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) stage(u);
-    };
-    int kb = N - 1;
-    if (kb >= PF - 1) {
-      group();
-      for (kb -= PF; kb >= PF - 1; kb -= PF) {
-        if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
-        group();
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < PF - 1; ++u) {
-      if (kb - u < 0) break;
-      stage(u);
-    }
-    if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
-    const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
-    if (scol >= 0 && j != 5) {
-      if (rowx) c.sP[g * NW + scol] = X0;
-      if (g == 0) c.sP[NS * NW + scol] = X1;
-    }
-    if (rcc >= 0) {
-      if (rowx) c.sPc[g * NC + rcc] = X0;
-      if (g == 0) c.sPc[NS * NC + rcc] = X1;
-      if (g >= 2 && g - 2 < NS) c.sTnu[(g - 2) * NC + rcc] = T2;
-      if (g >= 2 && g < NS) c.sTnu[g * NC + rcc] = T3;
-    }
-    wave_sync<true>();
-    if (g == 2 && rcc >= 2) c.sTnu[(rcc - 2) * NC + 0] += T1;
-    wave_sync<true>();
-    return riccati_first_point(c, o, delta, nreg);
-  }
   // ---- The sweep for WIDER stages on the matrix pipe (round 5): two controls (BEARPOPULATIONS, ROCKETLANDING: six states) and the elastic twins
-  // (nu + ns controls).  riccati_mfma above lives on one hand-placed 16x16 tile (NS <= 4, one control, the selector rows of G^ done by lane
+  // (nu + ns controls).  riccati_tile above lives on one hand-placed 16x16 tile (NS <= 4, one control, the selector rows of G^ done by lane
   // shifts); here a stage is a small block algebra over 16x16 tiles in the accumulator layout of v_mfma_f64_16x16x4_f64 (element (i,j) of a tile
   // in lane 16 (i%4) + j, register i/4), built on two facts about that layout:
   //   * register r of a tile M IS the B operand "rows 4r..4r+3 of M" and ALSO the A operand "columns 4r..4r+3 of M^T": for two tiles in this layout
@@ -1688,7 +1333,7 @@ struct HsFused {
   // The q are eliminated FOUR AT A TIME (one register of q rows): gather, 4x4 pivot block by v_readlane, per-lane L D L^T solve, Schur update of
   // every row that is still alive -- w, the later q, the bookkeeping rows -- by one matrix instruction per tile; the gains of a block then refer
   // to the later q as well, which a back-substitution over the blocks removes (v_readlane of the 4x4 coupling blocks, per-lane products).  No
-  // factor of the whole NQ x NQ block is ever held (136 + 16 doubles per lane for ROCKETLANDING's twin in the vector form).  As in riccati_mfma
+  // factor of the whole NQ x NQ block is ever held (136 + 16 doubles per lane for ROCKETLANDING's twin in the vector form).  As in riccati_tile
   // the dual bookkeeping rows (g^T pc' in row "1", -qc_q^T kc in rows nu_i) fall out of the same products as rows that are otherwise unused.
   // Same stage algebra, pivot order and rule, and outputs (gains K | kc per stage; P, pc, Tnu for the first point) as HsWave::riccati, whose
   // column-per-lane vector form these systems ran on up to round 4.  Matrix instructions per Hermite-Simpson stage (counted in the listings):
@@ -1702,7 +1347,7 @@ struct HsFused {
   static constexpr int G_REST = NC - G_FREE_LO - G_FREE_HI;   // right-hand sides in a tile behind the q
   static constexpr int G_CT = G_QT + 1 + (G_REST > 0 ? 1 : 0);
   static constexpr bool GEN_OK = NW <= 14 && NQ <= 16 && (G_BIG ? G_FREE_LO : G_FREE_LO + G_FREE_HI) >= 2 && G_FREE_HI >= 0 && G_REST <= 16;
-  static constexpr bool SUPPORTED = !GEN || GEN_OK;      // riccati_mfma / riccati_mfma_trap / riccati_mfma_gen
+  static constexpr bool SUPPORTED = !GEN || GEN_OK;      // riccati_tile / riccati_tile_trap / riccati_mfma_gen
   __host__ __device__ static constexpr int g_rhs_slot(int cc) {
     return cc < G_FREE_LO ? NW + cc : (cc - G_FREE_LO < G_FREE_HI ? G_QS + NQ + (cc - G_FREE_LO) : 16 * (G_QT + 1) + (cc - G_FREE_LO - G_FREE_HI));
   }
@@ -2001,7 +1646,7 @@ struct HsFused {
     wave_sync<true>();
     return riccati_first_point(c, o, delta, nreg);
   }
-  // The sweep is a function of its own (-DMYR_SWEEP_INLINE folds it back): its register allocation is then independent of the ~20 k
+  // The sweep is a function of its own: its register allocation is then independent of the ~20 k
   // instructions around it (the masks of the tile trick stay in VGPRs instead of being re-read from AGPRs every stage; the kernel
   // around it spills 120 values instead of 186).  Arguments by value -- the context itself must not escape into a call, or every pass
   // would find it in scratch (profiles/r03, experiment 1).  Measured: B=256 3.70 -> 3.56 ms, B=4096 15.5 -> 15.0 ms, B=512 (W = 2)
@@ -2016,61 +1661,47 @@ struct HsFused {
     HsSolveOpts o;
     o.reg_floor = a.reg_floor; o.rho_term = a.rho_term;
     if constexpr (GEN) return riccati_mfma_gen(c, o, a.delta, a.abort != 0);
-    else if constexpr (TRAP) return riccati_mfma_trap(c, o, a.delta, a.abort != 0);
-    else return riccati_mfma(c, o, a.delta, a.abort != 0);
-  }
-  __device__ __attribute__((always_inline)) static int sweep_inl(SwArgs a) {
-    Ctx c;
-    c.N = a.N; c.lane = a.lane; c.hr = (double*)a.hr; c.st = (double*)a.st; c.zr = (double*)a.zr;
-    use_set(c, (double*)a.kg, (double*)a.xs);
-#pragma unroll
-    for (int q = 0; q < NS; ++q) c.term_pinned[q] = ((a.pinned >> q) & 1) != 0;
-    HsSolveOpts o;
-    o.reg_floor = a.reg_floor; o.rho_term = a.rho_term;
-    if constexpr (GEN) return riccati_mfma_gen(c, o, a.delta, a.abort != 0);
-    else if constexpr (TRAP) return riccati_mfma_trap(c, o, a.delta, a.abort != 0);
-    else return riccati_mfma(c, o, a.delta, a.abort != 0);
+    else if constexpr (TRAP) return riccati_tile_trap<false>(c, o, a.delta, a.abort != 0, 0, 0, true, nullptr);
+    else return riccati_tile<false>(c, o, a.delta, a.abort != 0, 0, 0, true, nullptr);
   }
   __device__ static inline int sweep(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
-#ifndef MYR_SWEEP_INLINE
     // The sweep is a function of its own in every form (SwArgs: address-space-qualified pointers, a frame of its own; W > 1: called by wavefront 0 -- and
     // by wavefront 1 for the speculative rung -- under a branch on the wave-uniform wavefront index, a scalar branch).  History: round 3 had the index as a
     // per-lane value, the inlined sweep then sat inside an EXEC-masked region and results differed from handle to handle; round 4 made the index uniform
     // and kept W > 1 on the inlined form because call + speculative rung together still failed the fresh-handle gate; round 5 found why -- a spill in
     // front of a join block's EXEC restore, nothing to do with the call -- and holds every build with a listing scan and the
-    // register-fill gate.  -DMYR_SWEEP_CALL_W=0: round 4's form; -DMYR_W2_QUALIFIED: the inlined body on SwArgs (faults in some instantiations, exp9).
+    // register-fill gate.  -DMYR_SWEEP_CALL_W=0: round 4's inlined sweep for W > 1, the build's fallback for a translation unit the listing scan flags.
+    // (The sweep inlined in every form, and the inlined body on SwArgs -- it faulted in some instantiations -- are in the history at 2373201.)
 #if !defined(MYR_SWEEP_CALL_W) || MYR_SWEEP_CALL_W
-    constexpr bool CALL = true, QUAL = false;      // (the sweep is a call in every form since round 5; -DMYR_SWEEP_CALL_W=0: round 4's inlined sweep for W > 1)
-#elif defined(MYR_W2_QUALIFIED)
-    constexpr bool CALL = W == 1, QUAL = true;
+    constexpr bool CALL = true;
 #else
-    constexpr bool CALL = W == 1, QUAL = false;
+    constexpr bool CALL = W == 1;
 #endif
-    if constexpr (!CALL && !QUAL) {
+    if constexpr (!CALL) {
       if constexpr (GEN) return riccati_mfma_gen(c, o, delta, abort_on_reg);
-      else if constexpr (TRAP) return riccati_mfma_trap(c, o, delta, abort_on_reg);
-      else return riccati_mfma(c, o, delta, abort_on_reg);
-    }
-    SwArgs a;
-    a.hr = (nd_glb*)c.hr; a.st = (nd_glb*)c.st; a.zr = (nd_glb*)c.zr; a.kg = (nd_glb*)c.kg; a.xs = (nd_lds*)c.sP;
-    a.N = c.N; a.lane = c.lane; a.abort = abort_on_reg ? 1 : 0;
-    a.pinned = 0;
+      else if constexpr (TRAP) return riccati_tile_trap<false>(c, o, delta, abort_on_reg, 0, 0, true, nullptr);
+      else return riccati_tile<false>(c, o, delta, abort_on_reg, 0, 0, true, nullptr);
+    } else {
+      SwArgs a;
+      a.hr = (nd_glb*)c.hr; a.st = (nd_glb*)c.st; a.zr = (nd_glb*)c.zr; a.kg = (nd_glb*)c.kg; a.xs = (nd_lds*)c.sP;
+      a.N = c.N; a.lane = c.lane; a.abort = abort_on_reg ? 1 : 0;
+      a.pinned = 0;
 #pragma unroll
-    for (int q = 0; q < NS; ++q) a.pinned |= c.term_pinned[q] ? (1 << q) : 0;
-    a.reg_floor = o.reg_floor; a.rho_term = o.rho_term; a.delta = delta;
-    if constexpr (CALL) return sweep_call(a);
-    else return sweep_inl(a);
-#else
-    if constexpr (GEN) return riccati_mfma_gen(c, o, delta, abort_on_reg);
-    else if constexpr (TRAP) return riccati_mfma_trap(c, o, delta, abort_on_reg);
-    else return riccati_mfma(c, o, delta, abort_on_reg);
-#endif
+      for (int q = 0; q < NS; ++q) a.pinned |= c.term_pinned[q] ? (1 << q) : 0;
+      a.reg_floor = o.reg_floor; a.rho_term = o.rho_term; a.delta = delta;
+      return sweep_call(a);
+    }
   }
 
-  // The same for the trapezoidal scheme: riccati_mfma_trap over the stages [k_lo, k_hi) of one chunk (stage k ends at point k + 1; one eliminated control).
-  __device__ static int riccati_chunk_trap(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int k_lo, int k_hi, bool last, double* xo) {
+  // The same sweep for the trapezoidal scheme (HsWave::riccati_mfma_trap): y = (dx_s, du_s, du_e), ONE eliminated control per stage, no
+  // midpoint part -- three matrix instructions per stage, the single pivot Q[du_e][du_e] read from lane 8 of register 2; the end point
+  // of stage k is point k + 1.  CHUNK as in riccati_tile: the plain sweep, or the stages [k_lo, k_hi) of one chunk.
+  template <bool CHUNK>
+  __device__ static int riccati_tile_trap(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int k_lo_, int k_hi_, bool last_, double* xo) {
     using namespace detail;
-    k_lo = __builtin_amdgcn_readfirstlane(k_lo); k_hi = __builtin_amdgcn_readfirstlane(k_hi);      // (wave-uniform: scalar loop control, riccati_mfma)
+    static_assert(!TRAP || NQ == 1, "one control");
+    const int k_lo = CHUNK ? __builtin_amdgcn_readfirstlane(k_lo_) : 0, k_hi = __builtin_amdgcn_readfirstlane(CHUNK ? k_hi_ : c.N);      // (wave-uniform: riccati_tile)
+    const bool last = CHUNK ? last_ : true;
     const int lane = c.lane;
     const int g = lane >> 4, j = lane & 15;
     const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
@@ -2083,7 +1714,8 @@ struct HsFused {
     auto hsel = [&](int row, bool on) -> const double* {
       if (!on) return c.zr;
       if (scol >= 0) return he + HR_H + (scol <= row ? scol * NW - scol * (scol - 1) / 2 + (row - scol) : row * NW - row * (row - 1) / 2 + (scol - row));
-      if (rcc == 0) return he + HR_G0 + row;      // (g0 + mu g1: folded by the hessian pass / tl_fold)
+      if (rcc == 0) return he + HR_G0 + row;      // (a chunk: g0 + mu g1, folded by the hessian pass / tl_fold)
+      if constexpr (!CHUNK) { if (rcc == 1) return he + HR_G1 + row; }
       return c.zr;
     };
     const double* ptr[3] = {hsel(g, rowx), hsel(NS, g < 2),
@@ -2092,29 +1724,29 @@ struct HsFused {
 #pragma unroll
     for (int q = 0; q < 3; ++q) stp[q] = (ptr[q] == c.zr) ? 0 : (q == 2 ? (long)SG_N : (long)HR_N);
     const bool pinr = rowx && (!last || c.term_pinned[rowx ? g : 0]);
-    const double rho0 = last ? o.rho_term - delta : o.rho_term;      // (see riccati_chunk)
+    const double rho0 = last ? o.rho_term - delta : o.rho_term;      // (see riccati_tile)
     const double X0i = (pinr && scol == g) ? rho0 : ((pinr && rcc == 2 + g) ? 1.0 : 0.0);
     const double X1i = (!last && g < 2) ? (scol == NS ? rho0 : (rcc == 1 ? 1.0 : 0.0)) : 0.0;
     const double dv0 = (rowx && scol == g) ? delta : 0.0, dv1 = (g < 2 && scol == NS) ? delta : 0.0;
     const double f_a1 = j < 6 ? 1.0 : 0.0, f_keep = rcc >= 0 ? 1.0 : 0.0, f_she = (j == 8 || j == 9) ? 1.0 : 0.0;
-    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = g >= 2 ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;
-    const double f_a3 = (g == 0 && (j < 6 || j == 7 || j == 10 || j == 11 || j == 14 || j == 15)) ? -1.0 : 0.0;
+    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = (CHUNK ? g >= 2 : g == 2) ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;
+    const double f_a3 = (g == 0 && (j < 6 || (CHUNK && j == 7) || j == 10 || j == 11 || j == 14 || j == 15)) ? -1.0 : 0.0;
     const int k_off = (g == 0 && scol >= 0 && j != 5) ? scol : ((g == 0 && rcc >= 0) ? NQ * NW + rcc : -1);
     double* k_ptr = k_off >= 0 ? c.kg + (long)(k_hi - 1) * KSTR + k_off : c.zr + ZR - 2;
     const long k_step = k_off >= 0 ? KSTR : 0;
     double reg_floor = o.reg_floor;
     asm volatile("" : "+v"(reg_floor));
     int nreg = 0;
-    const bool abort_u = uniform_if<true>(abort_on_reg);
+    const bool abort_u = uniform_if<(W > 1)>(abort_on_reg);
     double in[PF][3];
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-      __builtin_amdgcn_sched_barrier(0);      // (slot by slot: riccati_mfma)
+      __builtin_amdgcn_sched_barrier(0);      // (slot by slot: riccati_tile)
     }
     mfma_d4 D3 = {X0i, X1i, 0.0, 0.0};
-    // one stage from ring slot u; groups, remainder and the deferred abort as in riccati_mfma
+    // one stage from ring slot u; groups, remainder and the deferred abort as in riccati_tile
     auto stage = [&](const int u) {
       const double X0 = D3[0] + (in[u][0] + dv0), X1 = fma(D3[1], f_x1, in[u][1] + dv1);
       const double G = in[u][2];
@@ -2130,7 +1762,7 @@ struct HsFused {
       const double q11 = W0::rdlane(D2[2], 8);
       double d = q11;
       const bool rare_ = !(d > reg_floor);
-      if (uniform_if<true>(rare_)) {
+      if (uniform_if<(W > 1)>(rare_)) {                                       // rare (same pivot rule as chol_reg); a scalar branch, see riccati_tile
         d = dmax(fabs(d), reg_floor); ++nreg;
       }
       const double kk = D2[2] * fast_rcp(d);
@@ -2139,7 +1771,7 @@ struct HsFused {
       const double A3 = D2[2] * f_a3;
       const double B3 = g == 0 ? kk : 0.0;
       D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
-      // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_mfma)
+      // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_tile)
 #pragma unroll
       for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
     };
@@ -2161,24 +1793,42 @@ struct HsFused {
       stage(u);
     }
     if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
-    const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
-    double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;
-    if (scol >= 0 && j != 5) {
-      if (rowx) xP[g * NW + scol] = X0;
-      if (g == 0) xP[NS * NW + scol] = X1;
+    if constexpr (!CHUNK) {
+      const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
+      if (scol >= 0 && j != 5) {
+        if (rowx) c.sP[g * NW + scol] = X0;
+        if (g == 0) c.sP[NS * NW + scol] = X1;
+      }
+      if (rcc >= 0) {
+        if (rowx) c.sPc[g * NC + rcc] = X0;
+        if (g == 0) c.sPc[NS * NC + rcc] = X1;
+        if (g >= 2 && g - 2 < NS) c.sTnu[(g - 2) * NC + rcc] = T2;
+        if (g >= 2 && g < NS) c.sTnu[g * NC + rcc] = T3;
+      }
+      wave_sync<true>();
+      if (g == 2 && rcc >= 2) c.sTnu[(rcc - 2) * NC + 0] += T1;
+      wave_sync<true>();
+      return riccati_first_point(c, o, delta, nreg);
+    } else {
+      const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
+      double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;
+      if (scol >= 0 && j != 5) {
+        if (rowx) xP[g * NW + scol] = X0;
+        if (g == 0) xP[NS * NW + scol] = X1;
+      }
+      if (rcc >= 0) {
+        if (rowx) xPc[g * NC + rcc] = X0;
+        if (g == 0) xPc[NS * NC + rcc] = X1;
+        if (g >= 2 && g - 2 < NS) xT[(g - 2) * NC + rcc] = T2;
+        if (g >= 2 && g < NS) xT[g * NC + rcc] = T3;
+        if (g == 3) xT[NS * NC + rcc] = T1;
+      }
+      wave_sync<true>();
+      if (g == 2 && rcc >= 2) xT[(rcc - 2) * NC + 0] += T1;
+      if (g == 2 && rcc == 1) xT[NS * NC + 0] += T1;
+      wave_sync<true>();
+      return nreg;
     }
-    if (rcc >= 0) {
-      if (rowx) xPc[g * NC + rcc] = X0;
-      if (g == 0) xPc[NS * NC + rcc] = X1;
-      if (g >= 2 && g - 2 < NS) xT[(g - 2) * NC + rcc] = T2;
-      if (g >= 2 && g < NS) xT[g * NC + rcc] = T3;
-      if (g == 3) xT[NS * NC + rcc] = T1;
-    }
-    wave_sync<true>();
-    if (g == 2 && rcc >= 2) xT[(rcc - 2) * NC + 0] += T1;
-    if (g == 2 && rcc == 1) xT[NS * NC + 0] += T1;
-    wave_sync<true>();
-    return nreg;
   }
 
   // ---- Two-level sweep: wrappers and level 2 ---------------------------------------------------------------------------------------------------
@@ -2197,13 +1847,13 @@ struct HsFused {
     for (int q = 0; q < NS; ++q) c.term_pinned[q] = ((a.pinned >> q) & 1) != 0;
     HsSolveOpts o;
     o.reg_floor = a.reg_floor; o.rho_term = a.rho_term;
-    if constexpr (TL && TRAP) return riccati_chunk_trap(c, o, a.delta, a.abort != 0, a.k_lo, a.k_hi, a.last != 0, (double*)a.xo);
-    else if constexpr (TL) return riccati_chunk(c, o, a.delta, a.abort != 0, a.k_lo, a.k_hi, a.last != 0, (double*)a.xo);
+    if constexpr (TL && TRAP) return riccati_tile_trap<true>(c, o, a.delta, a.abort != 0, a.k_lo, a.k_hi, a.last != 0, (double*)a.xo);
+    else if constexpr (TL) return riccati_tile<true>(c, o, a.delta, a.abort != 0, a.k_lo, a.k_hi, a.last != 0, (double*)a.xo);
     else return 0;
   }
-  __device__ static inline int sweep_chunk(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int ci, int grp = 0) {
+  __device__ static inline int sweep_chunk(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int ci) {
     SwArgsC a;
-    a.hr = (nd_glb*)c.hr; a.st = (nd_glb*)c.st; a.zr = (nd_glb*)c.zr; a.kg = (nd_glb*)(grp ? c.kgB : c.kgA); a.xo = (nd_lds*)(c.xA + (grp * NCH + ci) * EXCH);
+    a.hr = (nd_glb*)c.hr; a.st = (nd_glb*)c.st; a.zr = (nd_glb*)c.zr; a.kg = (nd_glb*)c.kgA; a.xo = (nd_lds*)(c.xA + ci * EXCH);
     a.lane = c.lane; a.abort = abort_on_reg ? 1 : 0;
     a.pinned = 0;
 #pragma unroll
@@ -2212,7 +1862,7 @@ struct HsFused {
     a.reg_floor = o.reg_floor; a.rho_term = o.rho_term; a.delta = delta;
     return chunk_call(a);
   }
-  // g0 + mu g1 -> the "1" column of every point record (the mu column's slot carries the control's continuity multiplier in riccati_chunk).  The
+  // g0 + mu g1 -> the "1" column of every point record (the mu column's slot carries the control's continuity multiplier in a chunk's sweep).  The
   // hessian pass writes it with the barrier parameter it knows; this pass adds dmu g1 in the iterations that change the parameter afterwards.
   __device__ static inline void tl_fold(Ctx& c, double mu) {
     // (uniform trip count, `live` gates the stores: a divergent loop ends in a join block, and this compiler has put spills in front of such a block's
@@ -2241,14 +1891,9 @@ struct HsFused {
   // and the reduced Hessian of the whole horizon is positive definite iff the chunks' pivots are positive AND every C is: its Cholesky pivots are
   // counted like the stages' (inertia correction).  tools/dev/twolevel/model.py is this algebra in numpy against the plain recursion.
   struct JnArgs { nd_lds *xb, *jn; int N, lane; double rho, floor_c; };
-#ifndef MYR_TL_JOIN_INLINE
-#define MYR_TL_JOIN_INLINE 0      // (as a function of its own the join saves and restores 189 callee-saved registers around 700 instructions of work; inlined it measures the same -- tools/dev/exp/exp88.sh: B = 512 180.6 k against 182.2 k -- so the validated form stays)
-#endif
-#if MYR_TL_JOIN_INLINE
-  __device__ __attribute__((always_inline)) static int tl_join(JnArgs a) {
-#else
+  // (as a function of its own the join saves and restores 189 callee-saved registers around 700 instructions of work; inlined it measured the same -- B = 512
+  // 180.6 k against 182.2 k -- so the validated form stays; the inlined one is in the history at 2373201)
   __device__ __attribute__((noinline)) static int tl_join(JnArgs a) {
-#endif
     using namespace detail;
     constexpr int NG = NS + 1, NCOL = NW + NG, NN = NW * NW;
     static_assert(NCOL == 2 * NW && NN <= 64, "stash layout; one element of an NW x NW product per lane");
@@ -2753,23 +2398,18 @@ struct HsFused {
     return detail::finite_(bar);
   }
 
-  // ---- the parallel passes as functions of their own (-DMYR_PASS_NOINLINE; measured SLOWER, off): the context travels BY VALUE (a copy
+  // ---- the parallel passes, inlined; as functions of their own (measured SLOWER; that form is in the history at 2373201) the context travels BY VALUE (a copy
   // on the stack; the caller's context does not escape), results come back by value.  Every pass then compiles without a single spill
   // (backward 256 + 176 registers, hessian 248, forward 256 + 78, trial 248) -- and the launch takes 17.9 instead of 14.8 ms (B=256: 3.96
   // against 3.58): the pointers arrive through scratch as per-lane values, so addresses are formed on the vector pipe and the LDS
   // accesses lose their address space.  Only the sweep, whose inputs are a dozen values, gains from a frame of its own. ----------------
-#ifdef MYR_PASS_NOINLINE
-#define MYR_PASS_ATTR __attribute__((noinline))
-#else
-#define MYR_PASS_ATTR inline
-#endif
   struct NuT { double v[NS]; };
-  __device__ MYR_PASS_ATTR static BOut backward_pass(Ctx c, Step stp, NuT nu) { BOut o; backward(c, stp, nu.v, o); return o; }
-  __device__ MYR_PASS_ATTR static double hessian_pass(Ctx c, double mu_fold) { double st; hessian(c, st, mu_fold); return st; }
+  __device__ inline static BOut backward_pass(Ctx c, Step stp, NuT nu) { BOut o; backward(c, stp, nu.v, o); return o; }
+  __device__ inline static double hessian_pass(Ctx c, double mu_fold) { double st; hessian(c, st, mu_fold); return st; }
   struct ThT { double v[NC]; };
-  __device__ MYR_PASS_ATTR static typename S::FwdOut forward_pass(Ctx c, HsSolveOpts o, double mu, ThT th) { typename S::FwdOut fo; forward(c, o, mu, th.v, fo); return fo; }
+  __device__ inline static typename S::FwdOut forward_pass(Ctx c, HsSolveOpts o, double mu, ThT th) { typename S::FwdOut fo; forward(c, o, mu, th.v, fo); return fo; }
   struct TrialOut { double f, bar, c1; bool ok; };
-  __device__ MYR_PASS_ATTR static TrialOut trial_pass(Ctx c, double alpha, double mu) { TrialOut t; t.ok = trial(c, alpha, mu, t.f, t.bar, t.c1); return t; }
+  __device__ inline static TrialOut trial_pass(Ctx c, double alpha, double mu) { TrialOut t; t.ok = trial(c, alpha, mu, t.f, t.bar, t.c1); return t; }
 
   // ---- start: the caller's point pushed inside its bounds (HsWave::init), into LDS; bound table ---------------------------------
   __device__ static void init(Ctx& c, const double* zg) {
@@ -2899,10 +2539,9 @@ struct HsFused {
         return d == 0.0 ? ((delta_last > 0.0) ? dmax(1e-8, delta_last / 3.0) : 1e-4) : d * ((delta_last > 0.0) ? 8.0 : 100.0);
       };
       // (Two-level sweep: the barrier parameter is folded into the sweep's "1" column, so the tests and the barrier update come BEFORE the sweep -- they
-      // depend on the two passes above only.  -DMYR_EARLY_EXIT=1 gives every form this order: the converged iteration then returns WITHOUT its sweep, one
-      // sweep in twenty-one of a headline solve, same bits.  Round 5's order -- the last iteration's sweep run and dropped -- is the default for the other forms.)
-      constexpr bool EARLY = TL || (MYR_EARLY_EXIT != 0);
-      if constexpr (EARLY) {
+      // depend on the two passes above only.  Every form has this order since round 6: the converged iteration then returns WITHOUT its sweep, one
+      // sweep in twenty-one of a headline solve, same bits.  Round 5's order -- the last iteration's sweep run and dropped -- is in the history at 2373201.)
+      {
         const int nm = MLAM * c.N * NS + p1.nm;
         const double sd = nm > 0 ? dmax(1.0, (sum_mult + p1.sm) / nm / 100.0) : 1.0;
         const double stat = stat_raw / sd, comp = p1.cmax / sd;
@@ -2929,7 +2568,7 @@ struct HsFused {
       constexpr bool SPEC = false;
 #endif
       if constexpr (TL) {
-        // Two-level sweep: every wavefront condenses its chunk of the horizon (riccati_chunk), wavefront 0 joins the chunks at their interfaces
+        // Two-level sweep: every wavefront condenses its chunk of the horizon (riccati_tile<true>), wavefront 0 joins the chunks at their interfaces
         // (tl_join) and eliminates the first point.  One rung of the inertia ladder = W chunk sweeps side by side + the join; a rung fails when a
         // stage pivot of any chunk, a pivot of an interface or the first point's is not positive.  (The speculative second rung of round 5 is gone:
         // wavefront 1 has its own chunk to sweep.)
@@ -2938,54 +2577,7 @@ struct HsFused {
           wsync();
         }
         MYR_PH(3)
-        if constexpr (TLS) {
-          // two chunks x two rungs: wavefront w sweeps chunk (w & 1) of rung group (w >> 1); wavefronts 0 and 2 join their group's chunks and eliminate the first point
-          for (int tr_ = 0; tr_ < 12; tr_ += 2) {
-            const double delta_b = next_delta(delta);
-            const bool abort_a = (tr_ < 11) && !(delta > 1e8), abort_b = (tr_ + 1 < 11) && !(delta_b > 1e8);
-            const int grp = c.wave >> 1, ci = c.wave & 1;
-            const double my_delta = grp ? delta_b : delta;
-            const bool my_abort = grp ? abort_b : abort_a;
-            double* cnt = c.sTh + NGR * TL_TH1 + grp * (NCH + 1);      // this group's pivot counts: the chunks', the join's
-            int nr = 0;
-            if (tl_edge(c.N, ci + 1) > tl_edge(c.N, ci)) nr = sweep_chunk(c, o, my_delta, my_abort, ci, grp);
-            cnt[ci] = (double)nr;
-            MYR_PH(13)
-            wsync();
-            MYR_PH(5)
-            const int nsg = __builtin_amdgcn_readfirstlane((int)cnt[0] + (int)cnt[1]);
-            if (ci == 0) {
-              int nj = 0;
-              if (nsg == 0 || !my_abort) {
-                Ctx cw = c;
-                use_set(cw, grp ? c.kgB : c.kgA, c.xA + grp * NCH * EXCH);
-                JnArgs ja;
-                ja.xb = (nd_lds*)(c.xA + grp * NCH * EXCH); ja.jn = (nd_lds*)(c.sJn + grp * TL_JN1); ja.N = c.N; ja.lane = c.lane; ja.rho = o.rho_term; ja.floor_c = MYR_TL_FLOOR;
-                nj = tl_join(ja);
-                nj = riccati_first_point(cw, o, my_delta, nj);
-              }
-              cnt[NCH] = (double)nj;
-            }
-            wsync();
-            const double* cn0 = c.sTh + NGR * TL_TH1;
-            const int na = __builtin_amdgcn_readfirstlane((int)cn0[0] + (int)cn0[1] + (int)cn0[NCH]);
-            const int nb = __builtin_amdgcn_readfirstlane((int)cn0[NCH + 1] + (int)cn0[NCH + 2] + (int)cn0[2 * NCH + 1]);
-            wsync();
-            MYR_PH(6)
-            nreg = na;
-            if (na == 0 || !abort_a) break;
-            delta = delta_b; nreg = nb;
-            if (nb == 0 || !abort_b) {        // the speculative rung stands: its gains, its first block and its interface maps become rung group 0's
-              for (int i = c.tid; i < c.N * KST; i += NT) c.kgA[i] = c.kgB[i];
-              for (int i = c.tid; i < EXCH; i += NT) c.xA[i] = c.xA[NCH * EXCH + i];
-              for (int i = c.tid; i < TL_JN1; i += NT) c.sJn[i] = c.sJn[TL_JN1 + i];
-              wsync();
-              break;
-            }
-            delta = next_delta(delta_b);
-          }
-        } else {
-        double* cnt = c.sTh + NGR * TL_TH1;         // pivot counts: the chunks', the join's
+        double* cnt = c.sTh + TL_TH1;         // pivot counts: the chunks', the join's
         for (int tr_ = 0; tr_ < 12; ++tr_) {
           const bool abort_on_reg = (tr_ < 11) && !(delta > 1e8);
           int nr = 0;
@@ -3023,7 +2615,6 @@ struct HsFused {
           MYR_PH(6)
           if (nreg == 0 || !abort_on_reg) break;
           delta = next_delta(delta);
-        }
         }
       } else
       if constexpr (SPEC) {
@@ -3082,23 +2673,6 @@ struct HsFused {
         printf("T b%d w%d it%d f=%.17g c1=%.17g cinf=%.17g stat=%.17g sm=%.17g lg=%.17g nreg=%d delta=%.9g mu=%.9g pen=%.9g\n", c.traj, c.wave, it,
                p1.f, p1.c1, p1.cinf, stat_raw, p1.sum_mult, p1.lg, nreg, delta, mu, pen);
 #endif
-      if constexpr (!EARLY) {
-        const int nm = MLAM * c.N * NS + p1.nm;
-        const double sd = nm > 0 ? dmax(1.0, (sum_mult + p1.sm) / nm / 100.0) : 1.0;
-        const double stat = stat_raw / sd, comp = p1.cmax / sd;
-        res.cost = p1.f; res.feas = cinf; res.stat = stat; res.compl_ = comp;
-        if (!(finite_(p1.f) && finite_(cinf) && finite_(stat_raw))) { res.status = 2; res.iters = it; return; }
-        if (cinf <= o.tol_feas && stat <= o.tol_stat && comp <= o.tol_compl) { res.status = 0; res.iters = it; return; }
-        if (it == o.max_iter) break;
-        for (int guard = 0; guard < 8; ++guard) {
-          const double cerr = (p1.cmin <= p1.cmax) ? dmax(fabs(p1.cmax - mu), fabs(p1.cmin - mu)) : 0.0;
-          const double emu = dmax(dmax(stat, cinf), cerr / sd);
-          if (emu <= o.kappa_eps * mu && mu > mu_min) {
-            const double nmu = dmax(mu_min, dmin(o.kappa_mu * mu, pow(mu, o.theta_mu)));
-            mu = nmu;
-          } else break;
-        }
-      }
       typename S::SweepOut so;
 #pragma unroll
       for (int i = 0; i < NS * NC; ++i) so.Tnu[i] = c.sTnu[i];
@@ -3177,11 +2751,9 @@ struct HsFused {
 
 // Persistent, one trajectory per wavefront (workgroup = one wavefront): every workgroup pulls trajectories from `ticket` until the
 // batch is done and owns ONE scratch block that it re-uses for all of them.
-#ifndef MYR_FUSED_OCC
-#define MYR_FUSED_OCC 1      // workgroups per SIMD the register allocation must allow (experiment, tools/dev/exp/exp109.sh: 2 = 256 registers per lane)
-#endif
+// (One workgroup per SIMD: at two -- 256 registers per lane -- the Hermite-Simpson kernel loses 55 %, profiles/r06/README.md.)
 template <class Sys, int NWAVES = 1, int SCHEME = 0>
-__global__ __launch_bounds__(64 * NWAVES, MYR_FUSED_OCC)
+__global__ __launch_bounds__(64 * NWAVES, 1)
 void hs_solve_fused_kernel(int B, int* ticket, HsSolveOpts o, VarScale vs, double* __restrict__ z, const double* __restrict__ lb,
                            const double* __restrict__ ub, double* lam, double* scratch, long scratch_stride,
                            const double* __restrict__ params, int params_stride, double* cost, int32_t* status,
@@ -3190,11 +2762,7 @@ void hs_solve_fused_kernel(int B, int* ticket, HsSolveOpts o, VarScale vs, doubl
   extern __shared__ __attribute__((aligned(16))) char smem_fused[];
   typename W::Ctx c;
   c.N = o.N; c.K = W::npoints(o.N); c.n = c.K * W::NW; c.lane = threadIdx.x & 63; c.tid = threadIdx.x;
-#ifdef MYR_WAVE_DIVERGENT       // (round 3's form: the compiler cannot see that the wavefront index is the same in every lane)
-  c.wave = threadIdx.x >> 6;
-#else
-  c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform BY CONSTRUCTION: `if (c.wave == 0)` is a scalar branch
-#endif
+  c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform BY CONSTRUCTION: `if (c.wave == 0)` is a scalar branch (round 3 had it per lane)
   c.h = o.h; c.h6 = o.h / 6.0; c.h8 = o.h / 8.0;
   // helper workgroups of the network kernel (NodeBoard): owners are workgroups 0..B-1, helper h of owner w is workgroup h B + w
   const bool coop = W::MLP && co.maxh > 0;

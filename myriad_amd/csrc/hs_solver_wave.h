@@ -236,17 +236,10 @@ struct HsWave {
   static constexpr int SG_GE = 0, SG_GM = SG_GE + NS * NY1, SG_LD = SG_GM + (TRAP ? 0 : NS * NY1), SG_LD0 = SG_LD + NS * NS,
                        SG_LI = SG_LD0 + NS, SG_LI0 = SG_LI + (TRAP ? 0 : NS * NS), SG_QM = SG_LI0 + (TRAP ? 0 : NS),
                        SG_QCM = SG_QM + (TRAP ? 0 : NY * NY),
-#if defined(MYR_RICCATI_VALU) || defined(MYR_RICCATI_CHECK)
-                       SG_N = SG_QCM + (TRAP ? 0 : NY * 2);
-#else     // the matrix-core sweep forms Qm | qcm itself: the record ends before them (CARTPOLE: 167 -> 104 doubles per stage)
+                       // the matrix-core sweep forms Qm | qcm itself: the record ends before them (CARTPOLE: 167 -> 104 doubles per stage)
                        SG_N = (NU == 1 && NS <= 4) ? SG_QM : SG_QCM + (TRAP ? 0 : NY * 2);
-#endif
   static constexpr int KST = NQ * NW + NQ * NC;   // K | kc per stage (global scratch)
-#ifdef MYR_RICCATI_CHECK
-  static constexpr bool OVERLAY_K = false;        // (the self-check addresses the gains as one flat array)
-#else
   static constexpr bool OVERLAY_K = KST <= SG_QM - SG_LD;
-#endif
   static constexpr int KSTR = OVERLAY_K ? SG_N : KST;   // stride of the gain records
   static constexpr int ZR = 2 * NY + 2;           // block of zeros (masked stage inputs of the Riccati lanes read it)
   static constexpr int PHI = NW * (NW + 1);       // closed-loop stage map Phi | phi per stage (LDS)
@@ -262,11 +255,7 @@ struct HsWave {
   }
   // LDS doubles: region R0 (adjoint M|v, later Phi|phi, later trial x|f), Pi, S, exchange
   __host__ __device__ static int r0_doubles(int N) {
-#if defined(MYR_RECUR_SEQ) || defined(MYR_RECUR_SEQ_FWD)
-    const int b = N * PHI;
-#else
     const int b = NodeTraits<Sys>::mlp ? 0 : N * PHI;     // (network systems: the closed-loop maps are not staged, see PHI_IN_LDS)
-#endif
     const int a = N * (NS * NS + NS), c = 2 * npoints(N) * NS;
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
   }
@@ -673,9 +662,8 @@ struct HsWave {
     c1o = wv_sum(c1); cinfo = wv_max(cinf);
   }
 
-  // adjoint recurrence Pi_{k-1} = M_k Pi_k + v_k, k = N-1 .. 0: lane r < NS owns row r of M|v (LDS, prefetched one
-  // stage ahead); Pi travels between lanes with v_readlane, so a stage is NS FMAs + NS readlanes and no barrier.
-#ifndef MYR_RECUR_SEQ
+  // adjoint recurrence Pi_{k-1} = M_k Pi_k + v_k, k = N-1 .. 0.  (The sequential forms of this and of the forward recursion -- a lane
+  // per row of the map, the vector passed between lanes with v_readlane -- are in the history at 2373201.)
   // Wave-scan form: the recurrence is affine, so the N dependent stages become a scan of map compositions, 64 stages at a
   // time (6 DPP rounds of an NS x NS product per block).  Lane j takes stage base + 63 - j, which turns the suffix scan
   // over the stages into the prefix scan over the lanes that the DPP idiom provides; lane j ends with Pi of its stage.
@@ -713,39 +701,6 @@ struct HsWave {
       for (int q = 0; q < NS; ++q) piS[q] = __shfl(lo[q], 63, 64);
     }
   }
-#else
-  __device__ static void adjoint_recur(Ctx& c, const double* nuT) {
-    // every row of 16 lanes repeats the computation of lanes 0..NS-1 (the broadcast below is per row); row 0 stores
-    const int lane = c.lane, l16 = lane & 15, r = l16 < NS ? l16 : 0;
-    constexpr int MV = NS * NS + NS, UB = 4;       // UB stages per batch of LDS reads: their latency is paid once per batch
-    double piq[NS], own = 0.0;
-#pragma unroll
-    for (int q = 0; q < NS; ++q) { piq[q] = c.term_pinned[q] ? nuT[q] : 0.0; own = (q == l16) ? piq[q] : own; }
-    for (int kb = c.N - 1; kb >= 0; kb -= UB) {
-      double row[UB][NS + 1];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int k = kb - u > 0 ? kb - u : 0;      // (stages below 0: a valid row, not used)
-        const double* M = c.r0 + (long)k * MV;
-#pragma unroll
-        for (int q = 0; q < NS; ++q) row[u][q] = M[r * NS + q];
-        row[u][NS] = M[NS * NS + r];
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int k = kb - u;
-        if (k < 0) break;
-        if (lane < NS) c.sPi[k * NS + lane] = own;
-        double v = row[u][NS];
-#pragma unroll
-        for (int q = 0; q < NS; ++q) v += row[u][q] * piq[q];
-        RowBcast<NS>::all(v, piq);        // lanes 0..NS-1 hold the rows: broadcast within each row of 16 lanes
-        own = v;
-      }
-    }
-  }
-
-#endif
 
   // ---- phase 3: lanes over intervals -- multipliers ------------------------------------------------------------
   __device__ static void intervals_lambda(Ctx& c, double& lam_inf, double& sum_mult) {
@@ -1130,9 +1085,6 @@ struct HsWave {
 #ifndef MYR_RICCATI_PF
 #define MYR_RICCATI_PF 4
 #endif
-#ifndef MYR_RICCATI_INLINE
-#define MYR_RICCATI_INLINE
-#endif
   static_assert(MYR_RICCATI_PF >= 2 && MYR_RICCATI_PF <= 8, "the prefetch ring needs two slots; PADF covers eight");
   static constexpr bool MFMA_RICCATI = (NU == 1 && NS <= 4);
   typedef double mfma_d4 __attribute__((ext_vector_type(4)));
@@ -1163,7 +1115,7 @@ struct HsWave {
                  : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
     return __hiloint2double(rhi, rlo);
   }
-  __device__ static MYR_RICCATI_INLINE int riccati_mfma(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
+  __device__ static int riccati_mfma(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
     static_assert(!TRAP, "Hermite-Simpson form");
     using namespace detail;
     const int lane = c.lane, N = c.N;
@@ -1250,12 +1202,6 @@ struct HsWave {
       for (int u = 0; u < PF; ++u) {
         const int k = kb - u;
         if (k < 0) break;
-#ifdef MYR_RICC_PROBE
-        unsigned long long tp[8]; tp[0] = __builtin_amdgcn_s_memtime();
-#define MYR_TP(i) tp[i] = __builtin_amdgcn_s_memtime();
-#else
-#define MYR_TP(i)
-#endif
         // (a) P' = P + H_e + delta I, pc' = pc + gbar_e
         X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
         const double G = in[u][2];
@@ -1270,12 +1216,10 @@ struct HsWave {
         C1[0] = fma(sh0, f_she, X0 * f_keep);
         C1[1] = fma(sh1, f_she, X1 * f_keep);
         C1[2] = 0.0; C1[3] = 0.0;
-        MYR_TP(1)
         const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
         // (c) [Q | qc] = Qm^ + Ge^^T R~  (selector row: the du_e rows take R~'s row du); rows 6, 10.. carry Tnu
         mfma_d4 C2;
         C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
-        MYR_TP(2)
         const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
         // (d) this column's gains [K | kc] = Qqq^-1 [Qqs | qc_q].  Pivots of the L D L^T of Qqq as in ldl_reg: d0 = q00,
         // d1 = q11 - q10^2 / q00 = det / q00, both required > reg_floor.  When they are (always, except inside the inertia
@@ -1283,15 +1227,8 @@ struct HsWave {
         // (product, fma, rcp + Newton, product) is a third of the factor-and-substitute one; the numerators do not depend
         // on it.
         const double q00 = rdlane(D2[3], 12), q10 = rdlane(D2[2], 12), q11 = rdlane(D2[2], 8);
-        MYR_TP(3)
-#ifdef MYR_RICC_PROBE
-        { double t_ = q00 + q10 + q11; asm volatile("" : "+v"(t_)); tp[7] = __builtin_amdgcn_s_memtime(); }
-#endif
         const double det = fma(q00, q11, -(q10 * q10));
         const double rdet = fast_rcp(det);
-#ifdef MYR_RICC_PROBE
-        unsigned long long tq; { double t_ = rdet; asm volatile("" : "+v"(t_)); tq = __builtin_amdgcn_s_memtime(); }
-#endif
         const double b0 = D2[3], b1 = D2[2];
         double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
         double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
@@ -1310,13 +1247,11 @@ struct HsWave {
           kk0 *= i0; kk1 *= i1;
           kk0 -= l10 * kk1;
         }
-        MYR_TP(4)
         k_ptr[0] = kk0; k_ptr[k_str] = kk1;                            // (lanes without a gain write a scratch slot)
         k_ptr -= k_step;
         // (e) [P | pc] = [Qss | qc_s] - Qsq [K | kc]; rows 10, 11, 14, 15: Tnu -= qc_q[:, nu]^T kc
         const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
         const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);     // (a select: groups 2, 3 may hold non-finite junk)
-        MYR_TP(5)
         D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
         // midpoint part of stage k-1, first product: independent of the recursion, both products run behind D3
         // while the next stage's operands are prepared
@@ -1331,13 +1266,6 @@ struct HsWave {
         mfma_d4 Cq;
         Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
         Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
-#ifdef MYR_RICC_PROBE
-        asm volatile("" : "+v"(D3));
-        tp[6] = __builtin_amdgcn_s_memtime();
-        if (blockIdx.x == 0 && lane == 0 && k >= N / 2 - 2 && k <= N / 2 + 1 && delta == 0.0)
-          printf("stage %d: top->D1 %llu  D1->D2 %llu  D2+mid->ldl %llu  [wait D2+readlane %llu  det+rcp %llu  gains %llu]  gains->D3 %llu  D3 issue %llu | total %llu\n", k,
-                 tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[7] - tp[3], tq - tp[7], tp[4] - tq, tp[5] - tp[4], tp[6] - tp[5], tp[6] - tp[0]);
-#endif
       }
     }
     X0 = D3[0]; X1 = D3[1];                                          // (X1 is read below in group 0 only)
@@ -1362,7 +1290,7 @@ struct HsWave {
   // The same sweep for the trapezoidal scheme: y = (dx_s, du_s, du_e), ONE eliminated control per stage, no midpoint part --
   // three MFMA per stage (R~, [Q|qc], the rank-1 update), the single pivot Q[du_e][du_e] read from lane 8 of register 2.
   // Slots as above (12, 13 unused); the end point of stage k is point k+1.
-  __device__ static MYR_RICCATI_INLINE int riccati_mfma_trap(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
+  __device__ static int riccati_mfma_trap(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
     using namespace detail;
     static_assert(NQ == 1, "one control");
     const int lane = c.lane, N = c.N;
@@ -1500,11 +1428,7 @@ struct HsWave {
   // Staged through LDS for the closed-form systems (computing the maps inside the scan phase costs them more in registers
   // than the LDS round trip: 195.6 k against 200.0 k solves/s on the bench); network systems compute them in the scan phase
   // and give the 24 KB back (PHI_IN_LDS: four wavefronts per workgroup instead of three).
-#if defined(MYR_RECUR_SEQ) || defined(MYR_RECUR_SEQ_FWD)
-  static constexpr bool PHI_IN_LDS = true;       // (the sequential form of the recursion reads the maps row by row from LDS)
-#else
   static constexpr bool PHI_IN_LDS = !MLP;
-#endif
   __device__ static void intervals_phi(Ctx& c, const double* th) {
     const int N = c.N;
     for (int k = c.lane; k < N; k += 64) {
@@ -1520,9 +1444,7 @@ struct HsWave {
     }
   }
 
-  // ---- phase 8b: forward recursion (sequential): lane r < NW owns row r of Phi|phi (prefetched one stage ahead),
-  // s travels between lanes with v_readlane; s_k -> LDS for phase 9.  No barrier inside the loop.
-#if !defined(MYR_RECUR_SEQ) && !defined(MYR_RECUR_SEQ_FWD)
+  // ---- phase 8b: forward recursion; s_k -> LDS for phase 9.
   // Wave-scan form (see adjoint_recur): prefix scan of the closed-loop maps, lane k ends with s_{k+1}.
   __device__ static void forward_recur(Ctx& c, const double* th) {
     const int lane = c.lane, N = c.N;
@@ -1578,42 +1500,6 @@ struct HsWave {
       for (int q = 0; q < NW; ++q) s0[q] = __shfl(sn[q], 63, 64);
     }
   }
-#else
-  __device__ static void forward_recur(Ctx& c, const double* th) {
-    // every row of 16 lanes repeats the computation of lanes 0..NW-1 (the broadcast below is per row); row 0 stores
-    const int lane = c.lane, N = c.N, l16 = lane & 15, r = l16 < NW ? l16 : 0;
-    constexpr int UB = 4;                          // stages per batch of LDS reads
-    double v = 0.0;
-    if (l16 >= NS && l16 < NW) {
-#pragma unroll
-      for (int cc = 0; cc < NC; ++cc) v -= c.sKu[(l16 - NS) * NC + cc] * th[cc];
-    }
-    double sq[NW];
-    RowBcast<NW>::all(v, sq);
-    if (lane < NW) c.sS[lane] = v;
-    for (int kb = 0; kb < N; kb += UB) {
-      double row[UB][NW + 1];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int k = kb + u < N ? kb + u : N - 1;
-        const double* P = c.r0 + (long)k * PHI + r * (NW + 1);
-#pragma unroll
-        for (int q = 0; q <= NW; ++q) row[u][q] = P[q];
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int k = kb + u;
-        if (k >= N) break;
-        v = row[u][NW];
-#pragma unroll
-        for (int q = 0; q < NW; ++q) v += row[u][q] * sq[q];
-        RowBcast<NW>::all(v, sq);
-        if (lane < NW) c.sS[(k + 1) * NW + lane] = v;
-      }
-    }
-  }
-
-#endif
 
   // ---- phase 9: lanes over intervals -- step for midpoint / end point variables ---------------------------------
   __device__ static void intervals_dz(Ctx& c, const double* th) {
@@ -1816,53 +1702,12 @@ struct HsWave {
       int nreg = 0;
       for (int tr_ = 0; tr_ < 12; ++tr_) {
         bool abort_on_reg = (tr_ < 11) && !(delta > 1e8);
-#if defined(MYR_RICCATI_VALU) || defined(MYR_RICCATI_CHECK)
-        intervals_qm(c, delta);
-#else
         if constexpr (!MFMA_RICCATI && !TRAP) intervals_qm(c, delta);   // the matrix-core sweep forms the midpoint terms itself
-#endif
         wsync();
         MYR_PH(5)
-#ifdef MYR_RICCATI_CHECK   // dev self-check: both forms on the same inputs, differences of every output printed
-        if constexpr (MFMA_RICCATI) {
-          const int nv = riccati(c, o, delta, abort_on_reg);
-          wsync();
-          const int nk = c.N * KST, nl = NW * NW + NW * NC + NS * NY1 + NS * NC + NU * NC;
-          for (int i = c.lane; i < nk; i += 64) c.r0[i] = c.kg[i];
-          for (int i = c.lane; i < nl; i += 64) c.r0[nk + i] = c.sP[i];
-          wsync();
-          for (int i = c.lane; i < nk; i += 64) c.kg[i] = -7.0;
-          wsync();
-          const int nm = riccati_mfma(c, o, delta, false);
-          wsync();
-          double dk = 0, dP = 0, dPc = 0, dT = 0, dKu = 0, mk = 0;
-          int worst = -1;
-          for (int i = c.lane; i < nk; i += 64) { const double d = fabs(c.r0[i] - c.kg[i]); if (d > dk) { dk = d; worst = i; } mk = dmax(mk, fabs(c.r0[i])); }
-          for (int i = c.lane; i < nl; i += 64) {
-            const double d = fabs(c.r0[nk + i] - c.sP[i]);
-            if (i < NW * NW) dP = dmax(dP, d);
-            else if (i < NW * NW + NW * NC) dPc = dmax(dPc, d);
-            else if (i < NW * NW + NW * NC + NS * NY1) ;
-            else if (i < NW * NW + NW * NC + NS * NY1 + NS * NC) dT = dmax(dT, d);
-            else dKu = dmax(dKu, d);
-          }
-          const double dkm = wv_max(dk);
-          const int wl = (dk == dkm) ? worst : -1;
-          const int wmax = -wv_isum(0) + (int)wv_max((double)wl);
-          dP = wv_max(dP); dPc = wv_max(dPc); dT = wv_max(dT); dKu = wv_max(dKu); mk = wv_max(mk);
-          if (c.lane == 0 && blockIdx.x == 0)
-            printf("ricc check it %d delta %.3g: nreg valu %d mfma %d | max|dK| %.3e (|K| %.3e, worst elem %d = stage %d field %d) dP %.3e dPc %.3e dTnu %.3e dKu %.3e\n",
-                   it, delta, nv, nm, dkm, mk, wmax, wmax / KST, wmax % KST, dP, dPc, dT, dKu);
-          nreg = nm;
-        } else nreg = riccati(c, o, delta, abort_on_reg);
-#else
-#ifndef MYR_RICCATI_VALU
         if constexpr (MFMA_RICCATI && TRAP) nreg = riccati_mfma_trap(c, o, delta, abort_on_reg);
         else if constexpr (MFMA_RICCATI) nreg = riccati_mfma(c, o, delta, abort_on_reg);
-        else
-#endif
-          nreg = riccati(c, o, delta, abort_on_reg);
-#endif
+        else nreg = riccati(c, o, delta, abort_on_reg);
         wsync();
         MYR_PH(6)
         if (nreg == 0) break;

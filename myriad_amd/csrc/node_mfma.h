@@ -86,10 +86,7 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
   // (Round 6: the weights of k-step ks + 1 are read BEFORE the four matrix instructions of k-step ks are issued, into registers of their own, and scheduling
   // barriers keep it that way.  The compiler's own order -- one ds_read2_b64 into one register quad, s_waitcnt lgkmcnt(0), two matrix instructions, 32 times --
   // exposed the LDS latency in front of every pair: a 64-instruction product took 9.6 k cycles for 4.1 k of matrix pipe, tools/dev/exp/exp104.sh.  Same
-  // operations in the same order: same bits.  -DMYR_NODE_PIPE=0: the old form.)
-#ifndef MYR_NODE_PIPE
-#define MYR_NODE_PIPE 1
-#endif
+  // operations in the same order: same bits, +0.5 %.  The compiler's-order form is in the history at 2373201.)
   template <bool BIAS>
   __device__ static inline void gemm_t(const nd_lds* wl, int g, int i, const nd4* in, nd4* out) {
     asm volatile("" ::: "memory");
@@ -98,7 +95,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
       for (int s = 0; s < 4; ++s) acc[mt][s] = BIAS ? wl[L_B2 + 16 * mt + 4 * s + g] : 0.0;
-#if MYR_NODE_PIPE
     double w[2][4];
     {
       const nd_lds* row = wl + L_W2 + g * LD2 + i;
@@ -117,16 +113,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
       for (int mt = 0; mt < 4; ++mt) acc[mt] = mm(w[ks & 1][mt], in[ks >> 2][ks & 3], acc[mt]);
       __builtin_amdgcn_sched_barrier(0);
     }
-#else
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const nd_lds* row = wl + L_W2 + (16 * t + 4 * s + g) * LD2 + i;
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[mt] = mm(row[16 * mt], in[t][s], acc[mt]);
-      }
-#endif
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) out[mt] = acc[mt];
   }
@@ -136,7 +122,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
     nd4 acc[4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) acc[nt] = nd4{0.0, 0.0, 0.0, 0.0};
-#if MYR_NODE_PIPE
     double w[2][4];
     {
       const nd_lds* col = wl + L_W2 + i * LD2 + g;
@@ -155,16 +140,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
       for (int nt = 0; nt < 4; ++nt) acc[nt] = mm(w[ks & 1][nt], in[ks >> 2][ks & 3], acc[nt]);
       __builtin_amdgcn_sched_barrier(0);
     }
-#else
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const nd_lds* col = wl + L_W2 + i * LD2 + 16 * t + 4 * s + g;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = mm(col[16 * nt * LD2], in[t][s], acc[nt]);
-      }
-#endif
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) out[nt] = acc[nt];
   }
@@ -275,7 +250,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
           for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int s = 0; s < 4; ++s) a1[mt][s] = wl[L_B1 + 16 * mt + 4 * s + g];
-#if MYR_NODE_PIPE
           double wa[4], wb[4];
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt) { wa[mt] = wl[L_W1 + g * H + 16 * mt + i]; wb[mt] = wl[L_W1 + (4 + g) * H + 16 * mt + i]; }
@@ -284,12 +258,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
           for (int mt = 0; mt < 4; ++mt) a1[mt] = mm(wa[mt], xg, a1[mt]);
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt) a1[mt] = mm(wb[mt], ug, a1[mt]);
-#else
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) a1[mt] = mm(wl[L_W1 + g * H + 16 * mt + i], xg, a1[mt]);
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) a1[mt] = mm(wl[L_W1 + (4 + g) * H + 16 * mt + i], ug, a1[mt]);
-#endif
 #pragma unroll
           for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -333,7 +301,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
           nd4 m[NW][2];
 #pragma unroll
           for (int c = 0; c < NW; ++c) { m[c][0] = nd4{0.0, 0.0, 0.0, 0.0}; m[c][1] = nd4{0.0, 0.0, 0.0, 0.0}; }
-#if MYR_NODE_PIPE
           // (the k-step's seven LDS values -- two weights of W2, five of W1 -- read one k-step ahead, as in gemm_t)
           double wq[2][2 + NW];
           {
@@ -362,23 +329,6 @@ struct NodeMfma64 {     // NS = 4, NU = 1, hidden (64, 64)
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-#else
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-              const int k = 16 * t + 4 * s + g;
-              const nd_lds* row = wl + L_W2 + k * LD2 + 32 * half + i;
-              const double w0 = row[0], w1 = row[16];
-              const double sp = h1[t][s] * (1.0 - h1[t][s]);
-#pragma unroll
-              for (int c = 0; c < NW; ++c) {
-                const double d = sp * wl[L_W1 + c * H + k];
-                m[c][0] = mm(w0, d, m[c][0]);
-                m[c][1] = mm(w1, d, m[c][1]);
-              }
-            }
-#endif
 #pragma unroll
           for (int q = 0; q < 2; ++q) {
             const int mt = 2 * half + q;

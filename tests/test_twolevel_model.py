@@ -1,4 +1,4 @@
-"""The interface algebra of the two-level Riccati sweep (hs_solver_fused.h: riccati_chunk / tl_join / tl_theta), restated in numpy
+"""The interface algebra of the two-level Riccati sweep (hs_solver_fused.h: riccati_tile<true> / tl_join / tl_theta), restated in numpy
 (tools/dev/twolevel/model.py), against the plain backward recursion on random staged QPs: same value form at the first point, same
 terminal multipliers, same states and controls -- for 2 and 4 chunks, chunks of unequal length, pinned and free terminal states,
 convex and (mildly) indefinite stage Hessians.  CPU only; the device kernels are held to the one-wavefront kernel in tests/test_gpu_*.py."""

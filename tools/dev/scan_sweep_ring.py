@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Listing gate for the prefetch ring of the Riccati sweeps (DESIGN.md sections 4 and 10.5).
 
-The sweeps (HsFused::riccati_mfma, riccati_chunk, riccati_mfma_trap, riccati_chunk_trap; compiled into the functions sweep_call and
+The sweeps (HsFused::riccati_tile, riccati_tile_trap, each as the plain sweep and as a chunk; compiled into the functions sweep_call and
 chunk_call) keep PF stages of point records in flight: a stage refills its ring slot with the records of the stage PF further down and
 reads the slot's other half (the midpoint records) PF - 1 stages after the refill.  That only hides the memory latency if the compiled
 stage loop
