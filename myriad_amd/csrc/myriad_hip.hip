@@ -68,8 +68,6 @@ static bool sys_info(int id, SysInfo* s) {
   return false;
 }
 
-struct myr_handle_s;
-static int device_cus_early(myr_handle_s* h);
 struct KTimer {
   hipEvent_t a = nullptr, b = nullptr;
   double sum_ms = 0.0;
@@ -127,6 +125,15 @@ struct myr_handle_s {
   unsigned long long stack_fill = 0;   // MYRIAD_STACK_FILL (tests / experiments): bit pattern left in the queue's private-segment memory before every solver launch
 };
 
+static int device_cus(myr_handle h) {
+  if (h->cus <= 0) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->cus = cus;
+    else h->cus = 256;
+  }
+  return h->cus;
+}
+
 // MYRIAD_STACK_FILL: what a kernel's spill slots and stack objects inherit.  The private segment ("scratch") of a queue is not cleared between
 // launches: a kernel that reads a stack slot before writing it gets what the previous kernel ON THIS QUEUE left there -- the same leftovers call after
 // call on one handle, something else on a fresh handle (new stream, new queue, new backing memory).  This kernel overwrites 4 KB of private memory per
@@ -155,8 +162,8 @@ static int stack_fill(myr_handle h) {
     if (sscanf(w, "%d:%d:%d", &bytes, &z0, &z1) == 3) {
       if (!h->ticket) HIPCHK(hipMalloc(&h->ticket, sizeof(int)));
       for (int rep = 0; rep < 3; ++rep) {
-        if (bytes == 528) hipLaunchKernelGGL((stack_fill_window_kernel<132>), dim3((unsigned)(device_cus_early(h) * 16)), dim3(64), 0, h->stream, z0, z1, (unsigned*)h->ticket);
-        else hipLaunchKernelGGL((stack_fill_window_kernel<512>), dim3((unsigned)(device_cus_early(h) * 16)), dim3(64), 0, h->stream, z0, z1, (unsigned*)h->ticket);
+        if (bytes == 528) hipLaunchKernelGGL((stack_fill_window_kernel<132>), dim3((unsigned)(device_cus(h) * 16)), dim3(64), 0, h->stream, z0, z1, (unsigned*)h->ticket);
+        else hipLaunchKernelGGL((stack_fill_window_kernel<512>), dim3((unsigned)(device_cus(h) * 16)), dim3(64), 0, h->stream, z0, z1, (unsigned*)h->ticket);
       }
       HIPCHK(hipGetLastError());
       return MYR_OK;
@@ -164,28 +171,17 @@ static int stack_fill(myr_handle h) {
   }
   if (h->reg_fill) {      // MYRIAD_REG_FILL: what the registers inherit (dbg_regfill.h)
     const unsigned rp = h->reg_fill == 1 ? 0x7ff40000u : (h->reg_fill == 3 ? 0x4415af1du : (h->reg_fill == 4 ? 0u : 0x3ff12345u));
-    for (int rep = 0; rep < 3; ++rep) hipLaunchKernelGGL(myriad::reg_fill_kernel, dim3((unsigned)(device_cus_early(h) * 16)), dim3(64), 0, h->stream, rp);
+    for (int rep = 0; rep < 3; ++rep) hipLaunchKernelGGL(myriad::reg_fill_kernel, dim3((unsigned)(device_cus(h) * 16)), dim3(64), 0, h->stream, rp);
     HIPCHK(hipGetLastError());
   }
   if (!h->stack_fill) return MYR_OK;
   if (!h->ticket) HIPCHK(hipMalloc(&h->ticket, sizeof(int)));
   const unsigned long long pat = h->stack_fill == 1 ? 0x7ff4000000000000ULL /* signalling NaN */ : (h->stack_fill == 3 ? 0x4415af1d78b58c40ULL /* 1e20 */ : (h->stack_fill == 4 ? 0ULL : 2ULL));
   for (int rep = 0; rep < 3; ++rep)
-    hipLaunchKernelGGL((stack_fill_kernel<512>), dim3((unsigned)(device_cus_early(h) * 16)), dim3(64), 0, h->stream, pat, rep, (unsigned long long*)h->ticket);
+    hipLaunchKernelGGL((stack_fill_kernel<512>), dim3((unsigned)(device_cus(h) * 16)), dim3(64), 0, h->stream, pat, rep, (unsigned long long*)h->ticket);
   HIPCHK(hipGetLastError());
   return MYR_OK;
 }
-
-static int device_cus(myr_handle h) {
-  if (h->cus <= 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->cus = cus;
-    else h->cus = 256;
-  }
-  return h->cus;
-}
-
-static int device_cus_early(myr_handle_s* h) { return device_cus(h); }
 
 // Workgroups of `kern` a CU keeps resident at this block size and dynamic-LDS size; sets the kernel's dynamic-LDS limit on the
 // way.  Asked of the runtime once per handle and configuration, not on every solve call.
@@ -204,6 +200,7 @@ static int kernel_blocks_per_cu(myr_handle h, const void* kern, int threads, siz
   return MYR_OK;
 }
 
+// every growing device buffer of a handle (sbuf, vbuf, dbuf, rbuf, fbuf, coop_buf): at least `need` bytes, contents not kept
 static int ensure_buf(void** buf, size_t* have, size_t need) {
   if (need <= *have) return MYR_OK;
   if (*buf) HIPCHK(hipFree(*buf));
@@ -213,13 +210,57 @@ static int ensure_buf(void** buf, size_t* have, size_t need) {
   return MYR_OK;
 }
 
-static int ensure_dbuf(myr_handle h, size_t bytes) {
-  if (bytes <= h->dbuf_bytes) return 0;
-  if (h->dbuf) HIPCHK(hipFree(h->dbuf));
-  h->dbuf = nullptr; h->dbuf_bytes = 0;
-  HIPCHK(hipMalloc(&h->dbuf, bytes));
-  h->dbuf_bytes = bytes;
-  return 0;
+// ---- the steps the launchers share -----------------------------------------------------------------------------------------
+// A timed launch on KTimer slot `k` (MYR_K_*): timed_begin -- the test fills, then the start event -- directly in front of the kernels,
+// timed_end behind them.  A launcher that has work between the stop event and the account calls the parts of timed_end itself.
+static int timed_begin(myr_handle h, int k) {
+  KTimer& kt = h->kt[k];
+  if (int rc_fill = stack_fill(h)) return rc_fill;
+  HIPCHK(hipEventRecord(kt.a, h->stream));
+  return MYR_OK;
+}
+static int timed_stop(myr_handle h, int k) {
+  KTimer& kt = h->kt[k];
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(kt.b, h->stream));
+  return MYR_OK;
+}
+static int timed_account(myr_handle h, int k) {      // (the stream has been synchronised)
+  KTimer& kt = h->kt[k];
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
+  kt.sum_ms += ms;
+  kt.launches += 1;
+  return MYR_OK;
+}
+static int timed_end(myr_handle h, int k) {
+  if (int rc = timed_stop(h, k)) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return timed_account(h, k);
+}
+
+// Persistent solver kernels: resident workgroups pull trajectories from a ticket counter, scratch belongs to the slot.
+// Slot stride in doubles: whole 256-byte lines, an ODD number of them, so that the slots rotate over the HBM channels
+static long slot_stride(long doubles) {
+  long stride = (doubles + 31) / 32 * 32;
+  if (((stride / 32) & 1) == 0) stride += 32;
+  return stride;
+}
+// the ticket: allocated once per handle, cleared on the stream in front of every launch
+static int reset_ticket(myr_handle h) {
+  if (!h->ticket) HIPCHK(hipMalloc(&h->ticket, sizeof(int)));
+  HIPCHK(hipMemsetAsync(h->ticket, 0, sizeof(int), h->stream));
+  return MYR_OK;
+}
+// slots of a launch before the cap at the batch size: MYRIAD_SOLVE_SLOTS, else what the device keeps resident -- per_cu workgroups on every CU
+// by the occupancy query (`guess` where that gave none), `per_group` slots in each
+static int default_slots(myr_handle h, int per_cu, int guess, int per_group = 1) {
+  return h->solve_slots > 0 ? h->solve_slots : (per_cu > 0 ? per_cu : guess) * device_cus(h) * per_group;
+}
+// myr_solve_plan's record of this launch: {form, wavefronts per trajectory, k1, phases, slots, helpers}
+static void set_plan(myr_handle h, int form, int waves, int k1, int phases, int slots, int helpers) {
+  const int32_t pl[8] = {form, waves, k1, phases, slots, helpers, 0, 0};
+  if (!h->plan_frozen) memcpy(h->plan, pl, sizeof(pl));      // (second starts re-launch on this handle: they leave the first attempt's record alone)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -237,7 +278,6 @@ static int launch_hs_eval(myr_handle h, int B, const double* z, const double* pa
   auto launched = [&](int w) { return nt_ ? (w == 1 ? 1 : (w == 8 ? 8 : 4)) : 4; };
   while (hs_eval_lds_bytes<Sys, SCHEME>(N, launched(wpt)) > 160 * 1024 && nt_ && wpt > 1) wpt = wpt == 8 ? 4 : 1;
   if (hs_eval_lds_bytes<Sys, SCHEME>(N, launched(wpt)) > 160 * 1024) return fail(MYR_E_CAPACITY, "hs_eval: intervals too large for the 160 KiB LDS record");
-  KTimer& kt = h->kt[MYR_K_EVAL];
   // the start event is recorded after the host-side attribute call, directly in front of the launch: the interval
   // between the two events is the kernel plus its dispatch, not host work
 #define MYR_EVAL_LAUNCH(W, NTV)                                                                                   \
@@ -248,8 +288,7 @@ static int launch_hs_eval(myr_handle h, int B, const double* z, const double* pa
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
       h->eval_attr_lds[(W == 1 ? 0 : (W == 4 ? 1 : 2)) + (NTV ? 3 : 0)] = 1;                                     \
     }                                                                                                             \
-    if (int rc_fill = stack_fill(h)) return rc_fill;                                                              \
-    HIPCHK(hipEventRecord(kt.a, h->stream));                                                                      \
+    if (int rc = timed_begin(h, MYR_K_EVAL)) return rc;                                                           \
     hipLaunchKernelGGL(kern, dim3(B), dim3(64 * W), lds, h->stream, N, hstep, z, params, pstride, f, g, c, j);    \
   }
   const bool nt = h->eval_nt != 0;
@@ -259,44 +298,22 @@ static int launch_hs_eval(myr_handle h, int B, const double* z, const double* pa
     default: if (nt) MYR_EVAL_LAUNCH(4, true) else MYR_EVAL_LAUNCH(4, false) break;
   }
 #undef MYR_EVAL_LAUNCH
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms;
-  kt.launches += 1;
-  return MYR_OK;
+  return timed_end(h, MYR_K_EVAL);
 }
 
 template <class Sys>
 static int launch_shoot_eval(myr_handle h, int B, const double* z, const double* params, int pstride,
                              double* f, double* g, double* c, double* j) {
   const int I = h->d.intervals, cpi = h->d.controls_per_interval, method = h->d.integration_method;
-  const size_t need = (size_t)B * (size_t)(cpi + 1) * Sys::NS * 8;
-  if (need > h->sbuf_bytes) {
-    if (h->sbuf) HIPCHK(hipFree(h->sbuf));
-    h->sbuf = nullptr; h->sbuf_bytes = 0;
-    HIPCHK(hipMalloc(&h->sbuf, need));
-    h->sbuf_bytes = need;
-  }
-  KTimer& kt = h->kt[MYR_K_EVAL];
-  if (int rc_fill = stack_fill(h)) return rc_fill;
-  HIPCHK(hipEventRecord(kt.a, h->stream));
+  if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, (size_t)B * (size_t)(cpi + 1) * Sys::NS * 8)) return rc;
+  if (int rc = timed_begin(h, MYR_K_EVAL)) return rc;
   if (method == MYR_INT_RK4)
     hipLaunchKernelGGL((shoot_eval_kernel<Sys, 2>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, I, cpi, method, h->d.T,
                        z, params, pstride, f, g, c, j, (double*)h->sbuf, (const double*)nullptr, 1);
   else
     hipLaunchKernelGGL((shoot_eval_kernel<Sys, 1>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, I, cpi, method, h->d.T,
                        z, params, pstride, f, g, c, j, (double*)h->sbuf, (const double*)nullptr, 1);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms;
-  kt.launches += 1;
-  return MYR_OK;
+  return timed_end(h, MYR_K_EVAL);
 }
 
 template <class Sys>
@@ -327,15 +344,17 @@ struct ProdArgs {
   double* out; int add_gradf;
   double *zio, *lamio; const double *lb, *ub; double eta_x, eta_v; int nsteps;   // exgd
 };
+struct SolveCall {      // one batch in device memory, as the solver launchers see it
+  int B; double* z; const double *lb, *ub, *params; int pstride; myr_solve_opts so;
+  double *lam, *cost; int32_t *status, *iters; double* kkt;      // each may be null
+};
 
 template <class Sys, int SCHEME>
 static int launch_products(myr_handle h, const ProdArgs& a) {
   const int N = h->d.intervals;
   const double hstep = h->d.T / N;
   using P = CollocProducts<Sys, SCHEME>;
-  KTimer& kt = h->kt[MYR_K_PROD];
-  if (int rc_fill = stack_fill(h)) return rc_fill;
-  HIPCHK(hipEventRecord(kt.a, h->stream));
+  if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
   if (a.op == PRODOP_EXGD) {
     const size_t lds = colloc_exgd_lds_bytes<Sys, SCHEME>(N);
     if (lds > 160 * 1024) return fail(MYR_E_CAPACITY, "myr_exgd: intervals too large for the LDS-resident iterate");
@@ -354,14 +373,7 @@ static int launch_products(myr_handle h, const ProdArgs& a) {
       hipLaunchKernelGGL((colloc_jvp_kernel<Sys, SCHEME>), dim3((unsigned)blocks), dim3(256), 0, h->stream, a.B, N, hstep, a.z, a.w,
                          a.params, a.pstride, a.out);
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms;
-  kt.launches += 1;
-  return MYR_OK;
+  return timed_end(h, MYR_K_PROD);
 }
 
 // shooting: J^T lam / grad L by the reverse sweep of shoot_eval_kernel seeded with lam, J v by forward tangents, and the
@@ -372,17 +384,10 @@ static int launch_shoot_products_m(myr_handle h, const ProdArgs& a) {
   const myr_dims& dm = h->dims;
   const size_t sweep = (size_t)a.B * (size_t)(cpi + 1) * Sys::NS * 8;
   const size_t extra = a.op == PRODOP_EXGD ? ((size_t)2 * a.B * dm.n + (size_t)a.B * dm.m) * 8 : 0;   // g, zbar, c
-  if (sweep + extra > h->sbuf_bytes) {
-    if (h->sbuf) HIPCHK(hipFree(h->sbuf));
-    h->sbuf = nullptr; h->sbuf_bytes = 0;
-    HIPCHK(hipMalloc(&h->sbuf, sweep + extra));
-    h->sbuf_bytes = sweep + extra;
-  }
+  if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, sweep + extra)) return rc;
   double* scr = (double*)h->sbuf;
   const dim3 grid((unsigned)((a.B + 63) / 64)), blk(64);
-  KTimer& kt = h->kt[MYR_K_PROD];
-  if (int rc_fill = stack_fill(h)) return rc_fill;
-  HIPCHK(hipEventRecord(kt.a, h->stream));
+  if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
   if (a.op == PRODOP_VJP) {
     hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, a.z, a.params, a.pstride,
                        (double*)nullptr, a.out, (double*)nullptr, (double*)nullptr, scr, a.w, a.add_gradf);
@@ -404,14 +409,7 @@ static int launch_shoot_products_m(myr_handle h, const ProdArgs& a) {
       hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, h->stream, tl, a.eta_v, (const double*)cbuf, a.lamio);
     }
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms;
-  kt.launches += 1;
-  return MYR_OK;
+  return timed_end(h, MYR_K_PROD);
 }
 
 template <class Sys>
@@ -524,21 +522,16 @@ static HsSolveOpts make_opts(myr_handle h, const myr_solve_opts& so) {
 }
 
 template <class Core, class Sys>
-static int launch_lane_solve(myr_handle h, int B, long nst, double* z, const double* lb, const double* ub, const double* params,
-                             int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                             int32_t* iters, double* kkt);
-#define MYR_SOLVE_ARGS myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params, int pstride, const myr_solve_opts& so, \
-                       double* lam, double* cost, int32_t* status, int32_t* iters, double* kkt
-#define MYR_SOLVE_ARG_TYPES myr_handle, int, double*, const double*, const double*, const double*, int, const myr_solve_opts&, double*, double*, int32_t*, int32_t*, double*
+static int launch_lane_solve(myr_handle h, const SolveCall& a, long nst);
 // the lane kernels of the collocation solvers as an entry point of their own (objects of their own in a split build: MYR_TU_PART 5, 6)
 template <class Sys, int SCHEME>
-int solve_lane_colloc_for_system(MYR_SOLVE_ARGS);
+int solve_lane_colloc_for_system(myr_handle h, const SolveCall& a);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
 #if MYR_TU_PART != 5
-extern template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(MYR_SOLVE_ARG_TYPES);
+extern template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, const SolveCall&);
 #endif
 #if MYR_TU_PART != 6
-extern template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(MYR_SOLVE_ARG_TYPES);
+extern template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, const SolveCall&);
 #endif
 #endif
 
@@ -573,37 +566,26 @@ static __global__ void park_scatter_kernel(int B, const int32_t* __restrict__ st
 // NWAVES wavefronts per trajectory: 1 for throughput (four trajectories per CU), 2 when the batch leaves CUs idle otherwise
 // (B <= 2 trajectories per CU: the parallel phases of an iteration take half the time, the launch lasts as long as one solve).
 template <class Sys, int NWAVES, int SCHEME>
-static int launch_hs_fused_w(myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params,
-                             int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                             int32_t* iters, double* kkt) {
+static int launch_hs_fused_w(myr_handle h, const SolveCall& a) {
   using W = HsFused<Sys, NWAVES, SCHEME>;
-  const int N = h->d.intervals;
+  const int N = h->d.intervals, B = a.B;
+  const myr_solve_opts& so = a.so;
   const size_t lds = W::lds_bytes(N);
   auto kern = hs_solve_fused_kernel<Sys, NWAVES, SCHEME>;
   int per_cu = 0;       // (attributes and occupancy once per handle and configuration, not per call)
   if (int rc = kernel_blocks_per_cu(h, reinterpret_cast<const void*>(kern), 64 * NWAVES, lds, &per_cu)) return rc;
-  int slots = h->solve_slots > 0 ? h->solve_slots : (per_cu > 0 ? per_cu : 4 / NWAVES) * device_cus(h);
-  const int slots_full = slots;
-  if (slots > B) slots = B;
-  long stride = (W::scratch_doubles(N) + 31) / 32 * 32;
-  if (((stride / 32) & 1) == 0) stride += 32;          // odd multiple of 256 B: rotate slots over HBM channels
+  const int slots_full = default_slots(h, per_cu, 4 / NWAVES);
+  const int slots = slots_full > B ? B : slots_full;
+  const long stride = slot_stride(W::scratch_doubles(N));
   const size_t need = (size_t)slots * (size_t)stride * 8;
-  if (need > h->sbuf_bytes) {
-    if (h->sbuf) HIPCHK(hipFree(h->sbuf));
-    h->sbuf = nullptr; h->sbuf_bytes = 0;
-    HIPCHK(hipMalloc(&h->sbuf, need));
-    h->sbuf_bytes = need;
-  }
-  if (!h->ticket) HIPCHK(hipMalloc(&h->ticket, sizeof(int)));
-  HIPCHK(hipMemsetAsync(h->ticket, 0, sizeof(int), h->stream));
+  if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, need)) return rc;
+  if (int rc = reset_ticket(h)) return rc;
   HsSolveOpts o = make_opts(h, so);
-  if (int rc = stack_fill(h)) return rc;
-  KTimer& kt = h->kt[MYR_K_SOLVE];
-  HIPCHK(hipEventRecord(kt.a, h->stream));
+  if (int rc = timed_begin(h, MYR_K_SOLVE)) return rc;
   h->last_solve_form = 1;
   if (getenv("MYRIAD_DEBUG_PTRS"))
     fprintf(stderr, "[myriad] fused W=%d N=%d B=%d slots=%d lds=%zu stride=%ld doubles: scratch [%p, %p) z %p lb %p ub %p lam %p ticket %p\n", NWAVES, N, B, slots, lds, stride,
-            h->sbuf, (char*)h->sbuf + need, (void*)z, (const void*)lb, (const void*)ub, (void*)lam, (void*)h->ticket);
+            h->sbuf, (char*)h->sbuf + need, (void*)a.z, (const void*)a.lb, (const void*)a.ub, (void*)a.lam, (void*)h->ticket);
   // Two phases when a slot would take at least two whole solves (B >= 2 x resident wavefronts): k1 iterations for every trajectory, the
   // unfinished ones parked, then resumed longest-first (hs_solver_fused.h: ParkArgs).  Needs the per-instance status and residuals.
   int k1 = 0;
@@ -619,7 +601,7 @@ static int launch_hs_fused_w(myr_handle h, int B, double* z, const double* lb, c
                                                                                // (trapezoidal solves are shorter and closer together: two phases cost them 2.5 %;
                                                                                //  the network system's longest solves -- 75 iterations against a median of 24 -- have SMALL
                                                                                //  residuals at the parking point and would come last: 41 -> 52 ms at B = 1024, exp42 / exp43)
-    if (k1 >= o.max_iter || !status || !kkt) k1 = 0;
+    if (k1 >= o.max_iter || !a.status || !a.kkt) k1 = 0;
     if (W::ZLU_GLOBAL && W::MLP) k1 = 0;        // (the network kernel's throughput form: its helper protocol and activation store are not part of a parked record;
                                                 //  the closed-form systems that keep the bound multipliers in the slot's scratch park them with the solver's LDS)
   }
@@ -634,7 +616,7 @@ static int launch_hs_fused_w(myr_handle h, int B, double* z, const double* lb, c
     if (B <= resident / 2 && resident / B - 1 < maxh) maxh = resident / B - 1;      // a small batch: spread the idle workgroups evenly
     if (h->node_helpers >= 0 && h->node_helpers < maxh) maxh = h->node_helpers;
     // whole solves with one shared weight set; every workgroup of the launch must be resident: owners wait for their helpers
-    if (pstride != 0 || k1 > 0 || per_cu < 1 || per_cu != 4 / NWAVES || h->solve_slots > 0) maxh = 0;
+    if (a.pstride != 0 || k1 > 0 || per_cu < 1 || per_cu != 4 / NWAVES || h->solve_slots > 0) maxh = 0;
     if (maxh > 0) {
       grid = (unsigned)((long)B * (maxh + 1) < (long)resident ? B * (maxh + 1) : resident);
       const int nboards = B <= (int)grid ? B : (int)grid;      // workgroups that can own a trajectory (hs_solve_fused_kernel: `fixed`)
@@ -669,15 +651,15 @@ static int launch_hs_fused_w(myr_handle h, int B, double* z, const double* lb, c
     }
     int* cnt = h->park_perm + h->park_n;
     pk = myriad::ParkArgs{1, k1, h->park_perm, cnt + PARK_BUCKETS, (double*)h->park_state, pstr};
-    hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64 * NWAVES), lds, h->stream, B, h->ticket, o, h->vscale, z, lb, ub, lam, (double*)h->sbuf, stride,
-                       params, pstride, cost, status, iters, kkt, h->poison, pk, co);
+    hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64 * NWAVES), lds, h->stream, B, h->ticket, o, h->vscale, a.z, a.lb, a.ub, a.lam, (double*)h->sbuf, stride,
+                       a.params, a.pstride, a.cost, a.status, a.iters, a.kkt, h->poison, pk, co);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(cnt, 0, (PARK_BUCKETS + 1) * sizeof(int), h->stream));
-    HIPCHK(hipMemsetAsync(h->ticket, 0, sizeof(int), h->stream));
+    if (int rc = reset_ticket(h)) return rc;
     const unsigned gb = (unsigned)((B + 255) / 256);
-    hipLaunchKernelGGL(park_hist_kernel, dim3(gb), dim3(256), 0, h->stream, B, status, kkt, cnt);
+    hipLaunchKernelGGL(park_hist_kernel, dim3(gb), dim3(256), 0, h->stream, B, a.status, a.kkt, cnt);
     hipLaunchKernelGGL(park_scan_kernel, dim3(1), dim3(64), 0, h->stream, cnt);
-    hipLaunchKernelGGL(park_scatter_kernel, dim3(gb), dim3(256), 0, h->stream, B, status, kkt, cnt, h->park_perm);
+    hipLaunchKernelGGL(park_scatter_kernel, dim3(gb), dim3(256), 0, h->stream, B, a.status, a.kkt, cnt, h->park_perm);
     pk.mode = 2;
   }
 #ifdef MYR_COOP_TRACE
@@ -698,11 +680,10 @@ static int launch_hs_fused_w(myr_handle h, int B, double* z, const double* lb, c
     }).detach();
   }
 #endif
-  { const int32_t pl[8] = {1, NWAVES, k1, k1 > 0 ? 2 : 1, slots, co.maxh, 0, 0}; if (!h->plan_frozen) memcpy(h->plan, pl, sizeof(pl)); }      // (the plan of THIS handle's last launch; a restoration twin is a handle of its own)
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVES), lds, h->stream, B, h->ticket, o, h->vscale, z, lb, ub, lam, (double*)h->sbuf, stride,
-                     params, pstride, cost, status, iters, kkt, h->poison, pk, co);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
+  set_plan(h, 1, NWAVES, k1, k1 > 0 ? 2 : 1, slots, co.maxh);      // (the plan of THIS handle's last launch; a restoration twin is a handle of its own)
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVES), lds, h->stream, B, h->ticket, o, h->vscale, a.z, a.lb, a.ub, a.lam, (double*)h->sbuf, stride,
+                     a.params, a.pstride, a.cost, a.status, a.iters, a.kkt, h->poison, pk, co);
+  if (int rc = timed_stop(h, MYR_K_SOLVE)) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   if (co.maxh > 0) {
     int ab = 0;
@@ -716,32 +697,26 @@ static int launch_hs_fused_w(myr_handle h, int B, double* z, const double* lb, c
       if (FILE* f = fopen(path, "wb")) { fwrite(sc.data(), sizeof(double), sc.size(), f); fclose(f); }
     }
   }
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms;
-  kt.launches += 1;
-  return MYR_OK;
+  return timed_account(h, MYR_K_SOLVE);      // (a launch the helper protocol aborted is not counted)
 }
 template <class Sys, int SCHEME>
-static int launch_hs_fused(myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params,
-                           int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                           int32_t* iters, double* kkt) {
+static int launch_hs_fused(myr_handle h, const SolveCall& a) {
   if constexpr (NodeTraits<Sys>::mlp) {
     // network dynamics.  Up to one trajectory per CU: four wavefronts share a trajectory (the LATENCY form: a launch is one solve long, idle CUs attach as
     // helpers).  Beyond: two wavefronts per trajectory, two trajectories per CU (the THROUGHPUT form: one trajectory's sequential sweep and interval
     // passes overlap the other's matrix-core passes on the CU's other two SIMDs; bound multipliers in global scratch so that two workgroups fit the LDS).
     // MYRIAD_FUSED_WAVES=2|4 overrides.
-    int waves = (B > device_cus(h)) ? 2 : 4;
+    int waves = (a.B > device_cus(h)) ? 2 : 4;
     if (h->fused_waves == 2 || h->fused_waves == 4) waves = h->fused_waves;
-    if (waves == 2 && pstride == 0 && 2 * HsFused<Sys, 2, 0>::lds_bytes(h->d.intervals) <= 160 * 1024)
-      return launch_hs_fused_w<Sys, 2, 0>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
-    return launch_hs_fused_w<Sys, 4, 0>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+    if (waves == 2 && a.pstride == 0 && 2 * HsFused<Sys, 2, 0>::lds_bytes(h->d.intervals) <= 160 * 1024)
+      return launch_hs_fused_w<Sys, 2, 0>(h, a);
+    return launch_hs_fused_w<Sys, 4, 0>(h, a);
   } else {
     // W = 2: two wavefronts per trajectory for batches of at most two trajectories per CU (a launch then lasts as long as one solve,
     // and the parallel passes of an iteration take half the time: +15 % at B = 512).  Round 3 switched it off -- its build returned
     // results that differed from launch to launch; round 4 found the form of the sweep that does it
     // (hs_solver_fused.h: sweep) and gates every build with tests/test_gpu_poison.py.  MYRIAD_FUSED_WAVES=1|2 overrides the choice.
-    int waves = (B <= 2 * device_cus(h)) ? 2 : 1;
+    int waves = (a.B <= 2 * device_cus(h)) ? 2 : 1;
     // (Four wavefronts per trajectory for batches of at most one trajectory per CU -- chunks of N / 4 stages -- were built and measured in round 6,
     // tools/dev/exp/exp84.sh: same iterates, and NO gain over two wavefronts -- B = 128 50.6 k against 50.4 k solves/s, B = 256 97.5 k against 96.6 k: what the
     // shorter chunks save, the three interface joins, one after the other on wavefront 0, cost.  Not instantiated: 160 KB of code per system.)
@@ -762,28 +737,23 @@ static int launch_hs_fused(myr_handle h, int B, double* z, const double* lb, con
         if (pc1 >= 1 && pc1 <= 2 && pc2 >= pc1) waves = 2;
       }
     }
-    if (so.park_iter > 0) waves = 1;                  // an explicit two-phase launch: only the one-wavefront form parks (include/myriad_hip.h: park_iter)
+    if (a.so.park_iter > 0) waves = 1;                // an explicit two-phase launch: only the one-wavefront form parks (include/myriad_hip.h: park_iter)
     if (h->fused_waves > 0) waves = h->fused_waves;
     if (waves > 2) waves = 2;
-    {
-      if (waves == 2 && HsFused<Sys, 2, SCHEME>::lds_bytes(h->d.intervals) <= 160 * 1024)
-        return launch_hs_fused_w<Sys, 2, SCHEME>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
-    }
-    return launch_hs_fused_w<Sys, 1, SCHEME>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+    if (waves == 2 && HsFused<Sys, 2, SCHEME>::lds_bytes(h->d.intervals) <= 160 * 1024)
+      return launch_hs_fused_w<Sys, 2, SCHEME>(h, a);
+    return launch_hs_fused_w<Sys, 1, SCHEME>(h, a);
   }
 }
 
 template <class Sys, int SCHEME = 0>
-static int launch_hs_solve(myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params,
-                           int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                           int32_t* iters, double* kkt) {
-  const int N = h->d.intervals;
-  const myr_dims& dm = h->dims;
+static int launch_hs_solve(myr_handle h, const SolveCall& a) {
+  const int N = h->d.intervals, B = a.B;
   // one trajectory per wavefront while its LDS working set fits a CU (N <= ~480 for CARTPOLE); beyond that the
   // lane-per-trajectory form, which keeps everything in global scratch, takes over
   if constexpr (HsFused<Sys, 1, SCHEME>::SUPPORTED && !(SCHEME == 1 && NodeTraits<Sys>::mlp)) {
     if (h->solve_mode == 1 && h->solve_fused && HsFused<Sys, (NodeTraits<Sys>::mlp ? 4 : 1), SCHEME>::lds_bytes(N) <= 160 * 1024)
-      return launch_hs_fused<Sys, SCHEME>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+      return launch_hs_fused<Sys, SCHEME>(h, a);
   }
   // (Round 3 kept the trapezoidal scheme with more than one control or more than four states off the wavefront kernel: its general
   // sweep read the end point's Hessian record at the Hermite-Simpson stride -- point 2k + 2 instead of k + 1 -- and BEARPOPULATIONS
@@ -801,9 +771,7 @@ static int launch_hs_solve(myr_handle h, int B, double* z, const double* lb, con
     // workgroup (4 x 24 + 40 KB), or, for batches smaller than the number of CUs, ONE solve whose network passes the four share
     int wpb = 1, coop = 0;
     if (W::MLP) {
-      int dev = 0, cus = 256;
-      HIPCHK(hipGetDevice(&dev));
-      HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+      const int cus = device_cus(h);
       // Small batches: the wavefronts of a workgroup share one trajectory's network passes (cooperative mode) -- four per
       // trajectory up to one trajectory per CU, two up to two per CU (two such workgroups fit a CU), four again up to four per
       // CU (the workgroup takes its trajectories one after the other); beyond that independent solves, four per workgroup.
@@ -812,7 +780,7 @@ static int launch_hs_solve(myr_handle h, int B, double* z, const double* lb, con
       coop = (B <= 4 * cus) ? 1 : 0;
       int coop_wpb = (B > cus && B <= 2 * cus) ? 2 : W::WPB_MAX;
       if (const char* e = getenv("MYRIAD_NODE_COOP")) coop = atoi(e) != 0;
-      if (coop || pstride == 0) {
+      if (coop || a.pstride == 0) {
         wpb = coop ? coop_wpb : W::WPB_MAX;
         if (const char* e = getenv("MYRIAD_NODE_WPB")) { wpb = atoi(e); if (wpb < 1) wpb = 1; if (wpb > W::WPB_MAX) wpb = W::WPB_MAX; }
         while (!coop && wpb > 1 && ((size_t)wpb * W::lds_solver_doubles(N) + NodeTraits<Sys>::lds_doubles) * 8 > 160 * 1024) --wpb;
@@ -828,61 +796,37 @@ static int launch_hs_solve(myr_handle h, int B, double* z, const double* lb, con
     // pulling trajectories from a ticket counter.  Scratch belongs to the SLOT, not to the trajectory: the working set of
     // a launch is slots x 273 KB (280 MB for CARTPOLE N=100) instead of B x 273 KB (1.1 GB at B = 4096) and is re-used
     // trajectory after trajectory, i.e. it stays in the 256 MB Infinity Cache instead of streaming through HBM.
-    int slots = h->solve_slots;              // wavefronts
-    if (slots <= 0) slots = (per_cu > 0 ? per_cu : 4) * device_cus(h) * lwaves;
+    int slots = default_slots(h, per_cu, 4, lwaves);             // wavefronts
     if (slots > B) slots = B;
     slots = (slots + lwaves - 1) / lwaves * lwaves;              // whole workgroups (surplus wavefronts find the ticket counter exhausted)
-    long stride = (W::scratch_doubles(N) + 31) / 32 * 32;
-    if (((stride / 32) & 1) == 0) stride += 32;          // odd multiple of 256 B: rotate slots over HBM channels
+    const long stride = slot_stride(W::scratch_doubles(N));
     const size_t need = (size_t)slots * (size_t)stride * 8;
     if (getenv("MYRIAD_DEBUG_PTRS"))
       fprintf(stderr, "[myriad] wave kernel N=%d B=%d slots=%d wpb=%d coop=%d per_cu=%d lds=%zu stride=%ld doubles need=%zu\n", N, B, slots, wpb, coop, per_cu, lds, stride, need);
-    if (need > h->sbuf_bytes) {
-      if (h->sbuf) HIPCHK(hipFree(h->sbuf));
-      h->sbuf = nullptr; h->sbuf_bytes = 0;
-      HIPCHK(hipMalloc(&h->sbuf, need));
-      h->sbuf_bytes = need;
-    }
-    if (!h->ticket) HIPCHK(hipMalloc(&h->ticket, sizeof(int)));
-    HIPCHK(hipMemsetAsync(h->ticket, 0, sizeof(int), h->stream));
-    HsSolveOpts o = make_opts(h, so);
-    KTimer& kt = h->kt[MYR_K_SOLVE];
-    if (int rc_fill = stack_fill(h)) return rc_fill;
-    HIPCHK(hipEventRecord(kt.a, h->stream));
+    if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, need)) return rc;
+    if (int rc = reset_ticket(h)) return rc;
+    HsSolveOpts o = make_opts(h, a.so);
+    if (int rc = timed_begin(h, MYR_K_SOLVE)) return rc;
     h->last_solve_form = 1;
-    { const int32_t pl[8] = {2, coop ? wpb : 1, 0, 1, slots, 0, 0, 0}; if (!h->plan_frozen) memcpy(h->plan, pl, sizeof(pl)); }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(slots / lwaves)), dim3(64 * wpb), lds, h->stream, B, h->ticket, o, h->vscale, z, lb, ub, lam, (double*)h->sbuf, stride,
-                       params, pstride, cost, status, iters, kkt, coop, h->poison);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(kt.b, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-    kt.sum_ms += ms;
-    kt.launches += 1;
-    return MYR_OK;
+    set_plan(h, 2, coop ? wpb : 1, 0, 1, slots, 0);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(slots / lwaves)), dim3(64 * wpb), lds, h->stream, B, h->ticket, o, h->vscale, a.z, a.lb, a.ub, a.lam, (double*)h->sbuf, stride,
+                       a.params, a.pstride, a.cost, a.status, a.iters, a.kkt, coop, h->poison);
+    return timed_end(h, MYR_K_SOLVE);
   }
-  return solve_lane_colloc_for_system<Sys, SCHEME>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+  return solve_lane_colloc_for_system<Sys, SCHEME>(h, a);
 }
 
 // lane-per-trajectory path, any sweep core (Hermite-Simpson, trapezoidal, shooting)
 template <class Core, class Sys>
-static int launch_lane_solve(myr_handle h, int B, long nst, double* z, const double* lb, const double* ub, const double* params,
-                             int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                             int32_t* iters, double* kkt) {
+static int launch_lane_solve(myr_handle h, const SolveCall& a, long nst) {
   const myr_dims& dm = h->dims;
+  const int B = a.B;
   // batch-minor leading dimension: a multiple of 64 lanes, but an ODD multiple so that consecutive elements of a
   // trajectory (stride Bp*8 bytes) rotate over HBM channels / L2 sets instead of camping on one (power-of-two stride)
   long Bp = ((long)B + 63) / 64 * 64;
   if (((Bp / 64) & 1) == 0) Bp += 64;
   const long n = dm.n, m = dm.m;
-  const size_t need = (size_t)Bp * (size_t)(6 * n + m + nst) * 8;
-  if (need > h->sbuf_bytes) {
-    if (h->sbuf) HIPCHK(hipFree(h->sbuf));
-    h->sbuf = nullptr; h->sbuf_bytes = 0;
-    HIPCHK(hipMalloc(&h->sbuf, need));
-    h->sbuf_bytes = need;
-  }
+  if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, (size_t)Bp * (size_t)(6 * n + m + nst) * 8)) return rc;
   double* sz = (double*)h->sbuf;
   double* slb = sz + n * Bp;
   double* sub = slb + n * Bp;
@@ -894,131 +838,104 @@ static int launch_lane_solve(myr_handle h, int B, long nst, double* z, const dou
   // padded lanes read garbage-free memory
   HIPCHK(hipMemsetAsync(h->sbuf, 0, (size_t)Bp * (size_t)(3 * n) * 8, h->stream));
   dim3 tb(256), tg((unsigned)((n + 31) / 32), (unsigned)((B + 31) / 32));
-  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, h->stream, (const double*)z, sz, B, (int)n, Bp);
-  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, h->stream, lb, slb, B, (int)n, Bp);
-  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, h->stream, ub, sub, B, (int)n, Bp);
-  HsSolveOpts o = make_opts(h, so);
-  KTimer& kt = h->kt[MYR_K_SOLVE];
-  if (int rc_fill = stack_fill(h)) return rc_fill;
-  HIPCHK(hipEventRecord(kt.a, h->stream));
+  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, h->stream, (const double*)a.z, sz, B, (int)n, Bp);
+  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, h->stream, a.lb, slb, B, (int)n, Bp);
+  hipLaunchKernelGGL(transpose_kernel, tg, tb, 0, h->stream, a.ub, sub, B, (int)n, Bp);
+  HsSolveOpts o = make_opts(h, a.so);
+  if (int rc = timed_begin(h, MYR_K_SOLVE)) return rc;
   const int lpw = h->solve_lpw;
   h->last_solve_form = 0;
-  { const int32_t pl[8] = {0, 0, 0, 1, B, 0, 0, 0}; if (!h->plan_frozen) memcpy(h->plan, pl, sizeof(pl)); }
+  set_plan(h, 0, 0, 0, 1, B, 0);
   hipLaunchKernelGGL((lane_solve_kernel<Core, Sys>), dim3((unsigned)((B + lpw - 1) / lpw)), dim3(64), 0, h->stream, B, Bp, lpw, o, h->vscale, sz, slb, sub, szL,
-                     szU, slam, sdz, sst, params, pstride, cost, status, iters, kkt);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
-  hipLaunchKernelGGL(transpose_back_kernel, tg, tb, 0, h->stream, (const double*)sz, z, B, (int)n, Bp);
-  if (lam) {
+                     szU, slam, sdz, sst, a.params, a.pstride, a.cost, a.status, a.iters, a.kkt);
+  if (int rc = timed_stop(h, MYR_K_SOLVE)) return rc;      // the kernel alone is timed: the transposes back come behind the stop event
+  hipLaunchKernelGGL(transpose_back_kernel, tg, tb, 0, h->stream, (const double*)sz, a.z, B, (int)n, Bp);
+  if (a.lam) {
     dim3 tgl((unsigned)((m + 31) / 32), (unsigned)((B + 31) / 32));
-    hipLaunchKernelGGL(transpose_back_kernel, tgl, tb, 0, h->stream, (const double*)slam, lam, B, (int)m, Bp);
+    hipLaunchKernelGGL(transpose_back_kernel, tgl, tb, 0, h->stream, (const double*)slam, a.lam, B, (int)m, Bp);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms;
-  kt.launches += 1;
-  return MYR_OK;
+  return timed_account(h, MYR_K_SOLVE);
 }
 
 // shooting, one trajectory per wavefront (shoot_solver_wave.h) while the iterate fits the LDS of a CU; else the lane form
 template <class Sys, int M>
-static int launch_shoot_solve(myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params,
-                              int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                              int32_t* iters, double* kkt) {
+static int launch_shoot_solve(myr_handle h, const SolveCall& a) {
   const int N = h->d.intervals, cpi = h->d.controls_per_interval;
   using W = ShootWave<Sys, M>;
   const size_t lds = W::lds_bytes(N, cpi);
   if (h->solve_mode != 1 || lds > 160 * 1024)
-    return launch_lane_solve<ShootCore<Sys, M>, Sys>(h, B, ShootCore<Sys, M>::stage_doubles(N, cpi), z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+    return launch_lane_solve<ShootCore<Sys, M>, Sys>(h, a, ShootCore<Sys, M>::stage_doubles(N, cpi));
   auto kern = shoot_solve_wave_kernel<Sys, M>;
   int per_cu = 0;
   if (int rc = kernel_blocks_per_cu(h, reinterpret_cast<const void*>(kern), 64, lds, &per_cu)) return rc;
-  int slots = h->solve_slots;
-  if (slots <= 0) slots = (per_cu > 0 ? per_cu : 4) * device_cus(h);
-  if (slots > B) slots = B;
-  if (!h->ticket) HIPCHK(hipMalloc(&h->ticket, sizeof(int)));
-  HIPCHK(hipMemsetAsync(h->ticket, 0, sizeof(int), h->stream));
-  HsSolveOpts o = make_opts(h, so);
+  int slots = default_slots(h, per_cu, 4);
+  if (slots > a.B) slots = a.B;
+  if (int rc = reset_ticket(h)) return rc;
+  HsSolveOpts o = make_opts(h, a.so);
   // network systems: records, activations and tangents of the matrix-core passes, per resident workgroup (shoot_solver_wave.h: mlp_scratch_doubles)
-  long sstride = (W::mlp_scratch_doubles(N, cpi) + 31) / 32 * 32;
-  if (sstride > 0) {
-    if (((sstride / 32) & 1) == 0) sstride += 32;
-    const size_t need = (size_t)slots * (size_t)sstride * 8;
-    if (need > h->sbuf_bytes) {
-      if (h->sbuf) HIPCHK(hipFree(h->sbuf));
-      h->sbuf = nullptr; h->sbuf_bytes = 0;
-      HIPCHK(hipMalloc(&h->sbuf, need));
-      h->sbuf_bytes = need;
-    }
-  }
-  KTimer& kt = h->kt[MYR_K_SOLVE];
-  if (int rc_fill = stack_fill(h)) return rc_fill;
-  HIPCHK(hipEventRecord(kt.a, h->stream));
+  const long sdoubles = W::mlp_scratch_doubles(N, cpi);
+  const long sstride = sdoubles > 0 ? slot_stride(sdoubles) : 0;
+  if (sstride > 0)
+    if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, (size_t)slots * (size_t)sstride * 8)) return rc;
+  if (int rc = timed_begin(h, MYR_K_SOLVE)) return rc;
   h->last_solve_form = 1;
-  { const int32_t pl[8] = {3, 1, 0, 1, slots, 0, 0, 0}; if (!h->plan_frozen) memcpy(h->plan, pl, sizeof(pl)); }
-  hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, h->stream, B, h->ticket, o, h->vscale, z, lb, ub, lam, params, pstride,
-                     cost, status, iters, kkt, h->poison, sstride > 0 ? (double*)h->sbuf : (double*)nullptr, sstride);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms;
-  kt.launches += 1;
-  return MYR_OK;
+  set_plan(h, 3, 1, 0, 1, slots, 0);
+  hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, h->stream, a.B, h->ticket, o, h->vscale, a.z, a.lb, a.ub, a.lam, a.params, a.pstride,
+                     a.cost, a.status, a.iters, a.kkt, h->poison, sstride > 0 ? (double*)h->sbuf : (double*)nullptr, sstride);
+  return timed_end(h, MYR_K_SOLVE);
 }
 
 // One function template per transcription, so that the build can give each its own object (MYR_TU_PART below: the solver kernels of a wide system
 // are minutes of compile time per scheme).
 template <class Sys, int SCHEME>
-int solve_lane_colloc_for_system(MYR_SOLVE_ARGS) {
+int solve_lane_colloc_for_system(myr_handle h, const SolveCall& a) {
   const int N = h->d.intervals;
   if constexpr (SCHEME == 1) {
     if constexpr (Sys::PARAMS_BY_POINTER) return fail(MYR_E_UNSUPPORTED, "myr_solve: NODE systems are built for HERMITE_SIMPSON");
-    else return launch_lane_solve<TrapCore<Sys>, Sys>(h, B, TrapCore<Sys>::stage_doubles(N), z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+    else return launch_lane_solve<TrapCore<Sys>, Sys>(h, a, TrapCore<Sys>::stage_doubles(N));
   } else
-    return launch_lane_solve<HsSolver<Sys>, Sys>(h, B, HsSol<Sys>::stage_doubles(N), z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+    return launch_lane_solve<HsSolver<Sys>, Sys>(h, a, HsSol<Sys>::stage_doubles(N));
 }
 template <class Sys>
-int solve_hs_for_system(MYR_SOLVE_ARGS) {
-  return launch_hs_solve<Sys>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+int solve_hs_for_system(myr_handle h, const SolveCall& a) {
+  return launch_hs_solve<Sys>(h, a);
 }
 template <class Sys>
-int solve_trap_for_system(MYR_SOLVE_ARGS) {      // wavefront form (falls back to the lane form for MYRIAD_SOLVE_MODE=lane / very large N)
+int solve_trap_for_system(myr_handle h, const SolveCall& a) {      // wavefront form (falls back to the lane form for MYRIAD_SOLVE_MODE=lane / very large N)
   if constexpr (Sys::PARAMS_BY_POINTER) return fail(MYR_E_UNSUPPORTED, "myr_solve: NODE systems are built for HERMITE_SIMPSON");
   // (a twin too wide for the fused kernel's block sweep would cost minutes of build time per solver on round 2's kernel: refused; no twin is, since round 5)
   else if constexpr (Sys::ID >= 100 && Sys::NW > 9 && !HsFused<Sys, 1, 1>::SUPPORTED) return fail(MYR_E_UNSUPPORTED, "myr_solve: the trapezoidal solver of this elastic twin is not built");
-  else return launch_hs_solve<Sys, 1>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+  else return launch_hs_solve<Sys, 1>(h, a);
 }
 template <class Sys>
-int solve_shoot_for_system(MYR_SOLVE_ARGS) {
+int solve_shoot_for_system(myr_handle h, const SolveCall& a) {
   // elastic twins (id >= 100) exist for the collocation solvers, whose restoration device they are; their shooting solver is not built
   if constexpr (Sys::ID >= 100) return fail(MYR_E_UNSUPPORTED, "myr_solve: elastic twins are built for the collocation transcriptions");
   else {
     if (h->d.integration_method == MYR_INT_RK4)
-      return launch_shoot_solve<Sys, 2>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
-    return launch_shoot_solve<Sys, 1>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+      return launch_shoot_solve<Sys, 2>(h, a);
+    return launch_shoot_solve<Sys, 1>(h, a);
   }
 }
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)      // the scheme solvers this object does not hold: no implicit instantiation
 #if MYR_TU_PART != 1
-extern template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(MYR_SOLVE_ARG_TYPES);
+extern template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 #endif
 #if MYR_TU_PART != 3
-extern template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(MYR_SOLVE_ARG_TYPES);
+extern template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 #endif
 #if MYR_TU_PART != 4
-extern template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(MYR_SOLVE_ARG_TYPES);
+extern template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 #endif
 #endif
 template <class Sys>
-int solve_for_system(MYR_SOLVE_ARGS) {
+int solve_for_system(myr_handle h, const SolveCall& a) {
   switch (h->d.transcription) {
-    case MYR_TR_HERMITE_SIMPSON: return solve_hs_for_system<Sys>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
-    case MYR_TR_TRAPEZOIDAL: return solve_trap_for_system<Sys>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
-    case MYR_TR_SHOOTING: return solve_shoot_for_system<Sys>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+    case MYR_TR_HERMITE_SIMPSON: return solve_hs_for_system<Sys>(h, a);
+    case MYR_TR_TRAPEZOIDAL: return solve_trap_for_system<Sys>(h, a);
+    case MYR_TR_SHOOTING: return solve_shoot_for_system<Sys>(h, a);
   }
   return fail(MYR_E_ARG, "solve: unknown transcription");
 }
@@ -1050,19 +967,10 @@ int launch_fbsm(myr_handle h, int B, long Bp, int N, const double* x0, const dou
   if constexpr (!Indirect<Sys>::SUPPORTED) {
     return fail(MYR_E_UNSUPPORTED, "myr_fbsm: this system has no adjoint dynamics (not an IndirectFHCS on the path)");
   } else {
-    KTimer& kt = h->kt[MYR_K_FBSM];
-    if (int rc_fill = stack_fill(h)) return rc_fill;
-    HIPCHK(hipEventRecord(kt.a, h->stream));
+    if (int rc = timed_begin(h, MYR_K_FBSM)) return rc;
     hipLaunchKernelGGL(fbsm_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, Bp, N, h->d.T, x0, adjT, params,
                        pstride, lo, hi, bang, delta, max_sweeps, X, U, A, sweeps);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(kt.b, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-    kt.sum_ms += ms;
-    kt.launches += 1;
-    return MYR_OK;
+    return timed_end(h, MYR_K_FBSM);
   }
 }
 
@@ -1078,8 +986,7 @@ int rollout_for_system(myr_handle h, int B, int num_steps, int u_rows, const dou
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
   LINK template int eval_for_system<S>(myr_handle, int, const double*, const double*, int, double*, double*, double*, double*);   \
   LINK template int products_for_system<S>(myr_handle, const ProdArgs&);                                                          \
-  LINK template int solve_for_system<S>(myr_handle, int, double*, const double*, const double*, const double*, int,               \
-                                        const myr_solve_opts&, double*, double*, int32_t*, int32_t*, double*);                    \
+  LINK template int solve_for_system<S>(myr_handle, const SolveCall&);                                                            \
   LINK template int rollout_for_system<S>(myr_handle, int, int, int, const double*, const double*, const double*, int, double*, double*); \
   LINK template int launch_fbsm<S>(myr_handle, int, long, int, const double*, const double*, const double*, int, const VarScale&,  \
                                    const VarScale&, double, double, int, double*, double*, double*, int32_t*);
@@ -1087,16 +994,16 @@ int rollout_for_system(myr_handle h, int B, int num_steps, int u_rows, const dou
 // a system's object in parts (the build splits the slow ones): -DMYR_TU_PART=1 the Hermite-Simpson wavefront solvers and the dispatch, 3 the trapezoidal
 // wavefront solvers, 4 the shooting solvers, 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
 #if MYR_TU_PART == 1
-template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(MYR_SOLVE_ARG_TYPES);
-template int solve_for_system<myriad::MYR_TU_SYSTEM>(MYR_SOLVE_ARG_TYPES);
+template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
+template int solve_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 3
-template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(MYR_SOLVE_ARG_TYPES);
+template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 4
-template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(MYR_SOLVE_ARG_TYPES);
+template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 5
-template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(MYR_SOLVE_ARG_TYPES);
+template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 6
-template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(MYR_SOLVE_ARG_TYPES);
+template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, const SolveCall&);
 #else
 #define MYR_SYSTEM_ENTRY_POINTS_REST(S)                                                                                            \
   template int eval_for_system<S>(myr_handle, int, const double*, const double*, int, double*, double*, double*, double*);         \
@@ -1272,6 +1179,9 @@ static int no_such_path(myr_handle h, const char* who) {
   return fail(MYR_E_ARG, std::string(who) + ": unknown system");
 }
 
+// carves of the host-call staging buffer (dbuf) and of the restoration buffers, in doubles: every carve keeps 16-byte alignment
+static size_t al(size_t v) { return (v + 1) & ~(size_t)1; }
+
 static int dispatch_eval(myr_handle h, int B, const double* z, const double* params, int pstride,
                          double* f, double* g, double* c, double* j) {
   switch (h->d.system_id) {
@@ -1300,9 +1210,8 @@ extern "C" int myr_eval(myr_handle h, int32_t B, const double* z, const double* 
   const size_t nz = (size_t)B * dm.n, npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
   const size_t nf = f ? (size_t)B : 0, ng = gradf ? (size_t)B * dm.ngrad : 0;
   const size_t nc = c ? (size_t)B * dm.m : 0, nj = jblk ? (size_t)B * dm.jblk : 0;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };   // keep 16-byte alignment of every carve
   const size_t total = al(nz) + al(npar) + al(nf) + al(ng) + al(nc) + al(nj);
-  int rc = ensure_dbuf(h, total * 8);
+  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * 8);
   if (rc) return rc;
   double* dz = (double*)h->dbuf;
   double* dp = dz + al(nz);
@@ -1358,8 +1267,7 @@ static int products_call(myr_handle h, int op, const char* who, int32_t B, const
   if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, std::string(who) + ": bad mem kind");
   const size_t nz = (size_t)B * dm.n, nw = (size_t)B * (op == PRODOP_VJP ? dm.m : dm.n), no = (size_t)B * (op == PRODOP_VJP ? dm.n : dm.m);
   const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };
-  rc = ensure_dbuf(h, (al(nz) + al(nw) + al(no) + al(npar)) * 8);
+  rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nz) + al(nw) + al(no) + al(npar)) * 8);
   if (rc) return rc;
   double* dz = (double*)h->dbuf; double* dw = dz + al(nz); double* dout = dw + al(nw); double* dp = dout + al(no);
   HIPCHK(hipMemcpyAsync(dz, z, nz * 8, hipMemcpyHostToDevice, h->stream));
@@ -1398,8 +1306,7 @@ extern "C" int myr_exgd(myr_handle h, int32_t B, double* z, double* lam, const d
   if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_exgd: bad mem kind");
   const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
   const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };
-  rc = ensure_dbuf(h, (3 * al(nz) + al(nl) + al(npar)) * 8);
+  rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (3 * al(nz) + al(nl) + al(npar)) * 8);
   if (rc) return rc;
   double* dz = (double*)h->dbuf; double* dlb = dz + al(nz); double* dub = dlb + al(nz); double* dl = dub + al(nz); double* dp = dl + al(nl);
   HIPCHK(hipMemcpyAsync(dz, z, nz * 8, hipMemcpyHostToDevice, h->stream));
@@ -1416,14 +1323,12 @@ extern "C" int myr_exgd(myr_handle h, int32_t B, double* z, double* lam, const d
   return MYR_OK;
 }
 
-static int dispatch_solve(myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params,
-                          int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                          int32_t* iters, double* kkt) {
+static int dispatch_solve(myr_handle h, const SolveCall& a) {
   switch (h->d.system_id) {
-#define X(N) case MYR_SYS_##N: return solve_for_system<Sys##N>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+#define X(N) case MYR_SYS_##N: return solve_for_system<Sys##N>(h, a);
     MYR_CLOSED_FORM_SYSTEMS(X)
 #undef X
-    case MYR_SYS_NODE_CARTPOLE: return solve_for_system<SysNODE_CARTPOLE>(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+    case MYR_SYS_NODE_CARTPOLE: return solve_for_system<SysNODE_CARTPOLE>(h, a);
   }
   return no_such_path(h, "solve");
 }
@@ -1452,29 +1357,23 @@ void scale_out_kernel(long total_z, long total_l, int n, int xcount, int ns, int
   }
 }
 
-static int dispatch_solve_scaled(myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params,
-                                 int pstride, const myr_solve_opts& so, double* lam, double* cost, int32_t* status,
-                                 int32_t* iters, double* kkt) {
-  if (!h->vscale_on) return dispatch_solve(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+static int dispatch_solve_scaled(myr_handle h, const SolveCall& a) {
+  if (!h->vscale_on) return dispatch_solve(h, a);
   const myr_dims& dm = h->dims;
-  const size_t need = 2 * (size_t)B * dm.n * 8;
-  if (need > h->vbuf_bytes) {
-    if (h->vbuf) HIPCHK(hipFree(h->vbuf));
-    h->vbuf = nullptr; h->vbuf_bytes = 0;
-    HIPCHK(hipMalloc(&h->vbuf, need));
-    h->vbuf_bytes = need;
-  }
+  if (int rc = ensure_buf(&h->vbuf, &h->vbuf_bytes, 2 * (size_t)a.B * dm.n * 8)) return rc;
   double* lbs = (double*)h->vbuf;
-  double* ubs = lbs + (size_t)B * dm.n;
-  const long tz = (long)B * dm.n, tl = lam ? (long)B * dm.m : 0;
+  double* ubs = lbs + (size_t)a.B * dm.n;
+  SolveCall scaled = a;      // z is scaled in place; the bounds are not the caller's to change
+  scaled.lb = lbs; scaled.ub = ubs;
+  const long tz = (long)a.B * dm.n, tl = a.lam ? (long)a.B * dm.m : 0;
   const int xcount = dm.x_rows * dm.ns;
   long blocks = (tz + 255) / 256; if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(scale_in_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, dm.n, xcount, dm.ns, dm.nu, h->vscale, z, lb, ub, lbs, ubs);
+  hipLaunchKernelGGL(scale_in_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, dm.n, xcount, dm.ns, dm.nu, h->vscale, a.z, a.lb, a.ub, lbs, ubs);
   HIPCHK(hipGetLastError());
-  int rc = dispatch_solve(h, B, z, lbs, ubs, params, pstride, so, lam, cost, status, iters, kkt);
+  int rc = dispatch_solve(h, scaled);
   // unscale even after a failed launch sequence is pointless: return the error as is
   if (rc) return rc;
-  hipLaunchKernelGGL(scale_out_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, tl, dm.n, xcount, dm.ns, dm.nu, dm.m, h->vscale, z, lam);
+  hipLaunchKernelGGL(scale_out_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, tl, dm.n, xcount, dm.ns, dm.nu, dm.m, h->vscale, a.z, a.lam);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   return MYR_OK;
@@ -1644,23 +1543,25 @@ static myr_handle twin_of(myr_handle h) {
   return t;
 }
 
-static int solve_restored(myr_handle h, int B, double* z, const double* lb, const double* ub, const double* params, int pstride,
-                          const myr_solve_opts& so, double* lam, double* cost, int32_t* status, int32_t* iters, double* kkt) {
+static int solve_restored(myr_handle h, const SolveCall& a) {
+  const int B = a.B, pstride = a.pstride;
+  double* const z = a.z; const double *lb = a.lb, *ub = a.ub, *params = a.params;
   h->info_start.assign(B, 0); h->info_attempts.assign(B, 1); h->info_restored.assign(B, 0);
   h->plan_frozen = false;
   struct Thaw { myr_handle h; ~Thaw() { h->plan_frozen = false; } } thaw{h};
-  const RestoreCfg cfg = restore_cfg(so);
-  if (!cfg.elastic && !cfg.starts) return dispatch_solve_scaled(h, B, z, lb, ub, params, pstride, so, lam, cost, status, iters, kkt);
+  const RestoreCfg cfg = restore_cfg(a.so);
+  if (!cfg.elastic && !cfg.starts) return dispatch_solve_scaled(h, a);
   const myr_dims& dm = h->dims;
   const int n = dm.n, m = dm.m, ns = dm.ns, nu = dm.nu, np = dm.np;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };
   // the caller's guess is overwritten by the first attempt: keep it
   if (int rc = ensure_buf(&h->rbuf, &h->rbuf_bytes, (al((size_t)B * n) + 2 * al((size_t)B)) * 8)) return rc;
   double* z0c = (double*)h->rbuf;
-  int32_t* dstat = status ? status : (int32_t*)(z0c + al((size_t)B * n));
-  int32_t* dit = iters ? iters : (int32_t*)(z0c + al((size_t)B * n) + al((size_t)B));
+  int32_t* dstat = a.status ? a.status : (int32_t*)(z0c + al((size_t)B * n));
+  int32_t* dit = a.iters ? a.iters : (int32_t*)(z0c + al((size_t)B * n) + al((size_t)B));
   HIPCHK(hipMemcpyAsync(z0c, z, (size_t)B * n * 8, hipMemcpyDeviceToDevice, h->stream));
-  if (int rc = dispatch_solve_scaled(h, B, z, lb, ub, params, pstride, so, lam, cost, dstat, dit, kkt)) return rc;
+  SolveCall first = a;      // status and iterations are needed here whether the caller asked for them or not
+  first.status = dstat; first.iters = dit;
+  if (int rc = dispatch_solve_scaled(h, first)) return rc;
   h->plan_frozen = true;
   if (!h->nfail_host) HIPCHK(hipHostMalloc((void**)&h->nfail_host, 64, hipHostMallocDefault));
   if (!h->nfail_dev) HIPCHK(hipMalloc((void**)&h->nfail_dev, 64));
@@ -1730,9 +1631,9 @@ static int solve_restored(myr_handle h, int B, double* z, const double* lb, cons
   auto scatter = [&](const std::vector<int32_t>& take, int nf) -> int {
     HIPCHK(hipMemcpyAsync(dtake, take.data(), (size_t)nf * 4, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)nf * n)), dim3(256), 0, h->stream, (long)nf * n, n, didx, dtake, zf, z);
-    if (lam) hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)nf * m)), dim3(256), 0, h->stream, (long)nf * m, m, didx, dtake, lamf, lam);
-    if (cost) hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)nf)), dim3(256), 0, h->stream, (long)nf, 1, didx, dtake, costf, cost);
-    if (kkt) hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)nf * 3)), dim3(256), 0, h->stream, (long)nf * 3, 3, didx, dtake, kktf, kkt);
+    if (a.lam) hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)nf * m)), dim3(256), 0, h->stream, (long)nf * m, m, didx, dtake, lamf, a.lam);
+    if (a.cost) hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)nf)), dim3(256), 0, h->stream, (long)nf, 1, didx, dtake, costf, a.cost);
+    if (a.kkt) hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)nf * 3)), dim3(256), 0, h->stream, (long)nf * 3, 3, didx, dtake, kktf, a.kkt);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));     // (`take` is a host vector of the caller's frame)
     return MYR_OK;
@@ -1745,8 +1646,11 @@ static int solve_restored(myr_handle h, int B, double* z, const double* lb, cons
     HIPCHK(hipStreamSynchronize(h->stream));
     return MYR_OK;
   };
-  myr_solve_opts plain = so;
-  plain.restoration = 0;
+  // every further attempt solves the working set of the failed rows, with no restoration of its own: on this handle ...
+  SolveCall again = a;
+  again.z = zf; again.lb = lbf; again.ub = ubf; again.params = pfp; again.pstride = per_row_params ? np : pstride;
+  again.so.restoration = 0;
+  again.lam = lamf; again.cost = costf; again.status = statf; again.iters = itf; again.kkt = kktf;
 
   if (twin) {      // ---- elastic phase -----------------------------------------------------------------------------------------
     const int nf = (int)fail_.size();
@@ -1759,8 +1663,11 @@ static int solve_restored(myr_handle h, int B, double* z, const double* lb, cons
     hipLaunchKernelGGL(twin_widen_kernel, dim3(grid_for((long)nf * nt)), dim3(256), 0, h->stream, (long)nf * nt, nx, nu, ns, -INFINITY, lbf, lbt, n, nt);
     hipLaunchKernelGGL(twin_widen_kernel, dim3(grid_for((long)nf * nt)), dim3(256), 0, h->stream, (long)nf * nt, nx, nu, ns, INFINITY, ubf, ubt, n, nt);
     HIPCHK(hipGetLastError());
-    myr_solve_opts topt = plain;
-    if (topt.max_iter > 500) topt.max_iter = 500;      // per twin solve (the ones that help take 30-300 iterations)
+    // ... and on the twin handle: the widened rows, rho as one more parameter of every row, status and iterations only
+    SolveCall tw = again;
+    tw.z = zt; tw.lb = lbt; tw.ub = ubt; tw.params = pt; tw.pstride = np + 1;
+    if (tw.so.max_iter > 500) tw.so.max_iter = 500;      // per twin solve (the ones that help take 30-300 iterations)
+    tw.lam = nullptr; tw.cost = nullptr; tw.kkt = nullptr;
     const double rhos[3] = {1.0, 1e2, 1e4};
     std::vector<double> slack_prev(nf, 0.0), slack_last(nf, 0.0);
     std::vector<int64_t> it_acc(nf, 0);
@@ -1770,7 +1677,8 @@ static int solve_restored(myr_handle h, int B, double* z, const double* lb, cons
       hipLaunchKernelGGL(twin_params_kernel, dim3(grid_for((long)nf * (np + 1))), dim3(256), 0, h->stream, nf, np, pfp, per_row_params ? np : 0, ddef, rhos[k], pt);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(h->stream));      // the twin runs on a stream of its own
-      const int rc = dispatch_solve_scaled(twin, nf, zt, lbt, ubt, pt, np + 1, topt, nullptr, nullptr, statf, itf, nullptr);
+      tw.B = nf;
+      const int rc = dispatch_solve_scaled(twin, tw);
       if (rc == MYR_E_UNSUPPORTED) {      // (a twin whose solver is not built for this scheme): drop the handle -- its stream and buffers -- for good, and do not
         twin_ok = false;                  // leave "... not built" behind as the last error of a myr_solve that returns MYR_OK
         h->twin_unavailable = true;
@@ -1793,7 +1701,8 @@ static int solve_restored(myr_handle h, int B, double* z, const double* lb, cons
     if (twin_ok) {
       hipLaunchKernelGGL(twin_narrow_kernel, dim3(grid_for((long)nf * n)), dim3(256), 0, h->stream, (long)nf * n, nx, nu, ns, zt, zf, n, nt);
       HIPCHK(hipGetLastError());
-      if (int rc = dispatch_solve_scaled(h, nf, zf, lbf, ubf, pfp, per_row_params ? np : pstride, plain, lamf, costf, statf, itf, kktf)) return rc;
+      again.B = nf;
+      if (int rc = dispatch_solve_scaled(h, again)) return rc;
       if (int rc = read_back(nf)) return rc;
       std::vector<int32_t> take(nf, 0), left;
       for (int r = 0; r < nf; ++r) {
@@ -1826,7 +1735,8 @@ static int solve_restored(myr_handle h, int B, double* z, const double* lb, cons
       if (int rc = dispatch_rollout(h, nf, steps, rr, dx0, dus, pfp, per_row_params ? np : pstride, dxs, nullptr)) return rc;
       hipLaunchKernelGGL(excitation_pack_kernel, dim3(grid_for((long)nf * n)), dim3(256), 0, h->stream, (long)nf * n, n, nx, ns, nu, steps, xstride, rr, ustride, dxs, dus, lbf, ubf, zf);
       HIPCHK(hipGetLastError());
-      if (int rc = dispatch_solve_scaled(h, nf, zf, lbf, ubf, pfp, per_row_params ? np : pstride, plain, lamf, costf, statf, itf, kktf)) return rc;
+      again.B = nf;
+      if (int rc = dispatch_solve_scaled(h, again)) return rc;
       if (int rc = read_back(nf)) return rc;
       std::vector<int32_t> take(nf, 0), left;
       for (int r = 0; r < nf; ++r) {
@@ -1882,31 +1792,56 @@ extern "C" int myr_set_var_scale(myr_handle h, const double* scale) {
   return MYR_OK;
 }
 
+// ---- myr_solve / myr_solve_x0: what the two entry points share ---------------------------------------------------------------
+// The argument checks, in the order both make them, on the call as the user passed it (`c`; c->so is filled from `opts` here).  `who` names the
+// entry point, `arrays` its pointers that must not be null (`null`: one is); mem_early: the memory kind where it is tested at this point
+// (myr_solve_x0; myr_solve tests it after hipSetDevice).  *empty: a batch of zero instances -- nothing to do, and nothing further is checked.
+static int check_solve_args(myr_handle h, const char* who, const char* arrays, bool null, const int32_t* mem_early, const myr_solve_opts* opts,
+                            SolveCall* c, bool* empty) {
+  const std::string w(who);
+  *empty = false;
+  if (!h || null) return fail(MYR_E_ARG, w + ": null handle, " + arrays);
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
+  if (c->B < 0) return fail(MYR_E_ARG, w + ": negative batch");
+  if (c->B == 0) { h->info_start.clear(); h->info_attempts.clear(); h->info_restored.clear(); *empty = true; return MYR_OK; }
+  if (c->params && c->pstride != 0 && c->pstride != h->dims.np)
+    return fail(MYR_E_ARG, w + ": params_stride must be 0 (shared) or np");
+  if (!c->params && h->d.system_id == MYR_SYS_NODE_CARTPOLE) return fail(MYR_E_ARG, w + ": a NODE system needs its weights in `params`");
+  if (mem_early && *mem_early != MYR_MEM_HOST && *mem_early != MYR_MEM_DEVICE) return fail(MYR_E_ARG, w + ": bad mem kind");
+  myr_solve_opts& so = c->so;
+  if (opts) so = *opts; else myr_default_solve_opts(&so);
+  if (so.max_iter < 0 || !(so.tol_feas > 0) || !(so.tol_stat > 0) || !(so.tol_compl > 0) || !(so.mu_init > 0))
+    return fail(MYR_E_ARG, w + ": bad options");
+  return MYR_OK;
+}
+// the results of a solve, from the staging arrays `d` to the host caller's `user` (all but z optional)
+static int download_solve(myr_handle h, const SolveCall& d, const SolveCall& user) {
+  const size_t B = (size_t)d.B;
+  HIPCHK(hipMemcpyAsync(user.z, d.z, B * h->dims.n * 8, hipMemcpyDeviceToHost, h->stream));
+  if (user.lam) HIPCHK(hipMemcpyAsync(user.lam, d.lam, B * h->dims.m * 8, hipMemcpyDeviceToHost, h->stream));
+  if (user.cost) HIPCHK(hipMemcpyAsync(user.cost, d.cost, B * 8, hipMemcpyDeviceToHost, h->stream));
+  if (user.status) HIPCHK(hipMemcpyAsync(user.status, d.status, B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (user.iters) HIPCHK(hipMemcpyAsync(user.iters, d.iters, B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (user.kkt) HIPCHK(hipMemcpyAsync(user.kkt, d.kkt, B * 24, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MYR_OK;
+}
+
 extern "C" int myr_solve(myr_handle h, int32_t B, double* z, const double* lb, const double* ub,
                          const double* params, int32_t params_stride, const myr_solve_opts* opts,
                          double* lam, double* cost, int32_t* status, int32_t* iters, double* kkt, int32_t mem) {
-  if (!h || !z || !lb || !ub) return fail(MYR_E_ARG, "myr_solve: null handle, z, lb or ub");
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, "myr_solve");
-  if (B < 0) return fail(MYR_E_ARG, "myr_solve: negative batch");
-  if (B == 0) { h->info_start.clear(); h->info_attempts.clear(); h->info_restored.clear(); return MYR_OK; }
-  if (params && params_stride != 0 && params_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_solve: params_stride must be 0 (shared) or np");
-  if (!params && h->d.system_id == MYR_SYS_NODE_CARTPOLE) return fail(MYR_E_ARG, "myr_solve: a NODE system needs its weights in `params`");
-  myr_solve_opts so;
-  if (opts) so = *opts; else myr_default_solve_opts(&so);
-  if (so.max_iter < 0 || !(so.tol_feas > 0) || !(so.tol_stat > 0) || !(so.tol_compl > 0) || !(so.mu_init > 0))
-    return fail(MYR_E_ARG, "myr_solve: bad options");
+  SolveCall user{B, z, lb, ub, params, params_stride, {}, lam, cost, status, iters, kkt};
+  bool empty = false;
+  if (int rc = check_solve_args(h, "myr_solve", "z, lb or ub", !z || !lb || !ub, nullptr, opts, &user, &empty)) return rc;
+  if (empty) return MYR_OK;
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
-  if (mem == MYR_MEM_DEVICE)
-    return solve_restored(h, B, z, lb, ub, params, params_stride, so, lam, cost, status, iters, kkt);
+  if (mem == MYR_MEM_DEVICE) return solve_restored(h, user);
   if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_solve: bad mem kind");
   const size_t nz = (size_t)B * dm.n, nl = lam ? (size_t)B * dm.m : 0;
   const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };
   const size_t total = 3 * al(nz) + al(nl) + al(npar) + al(B) /*cost*/ + al(B) /*status+iters as int32 pairs*/ + al(3 * (size_t)B);
-  int rc = ensure_dbuf(h, total * 8);
-  if (rc) return rc;
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * 8)) return rc;
   double* dz = (double*)h->dbuf;
   double* dlb = dz + al(nz);
   double* dub = dlb + al(nz);
@@ -1920,16 +1855,9 @@ extern "C" int myr_solve(myr_handle h, int32_t B, double* z, const double* lb, c
   HIPCHK(hipMemcpyAsync(dlb, lb, nz * 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(dub, ub, nz * 8, hipMemcpyHostToDevice, h->stream));
   if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  rc = solve_restored(h, B, dz, dlb, dub, npar ? dp : nullptr, params_stride, so, nl ? dlam : nullptr, dcost, dstat, dit, dkkt);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(z, dz, nz * 8, hipMemcpyDeviceToHost, h->stream));
-  if (nl) HIPCHK(hipMemcpyAsync(lam, dlam, nl * 8, hipMemcpyDeviceToHost, h->stream));
-  if (cost) HIPCHK(hipMemcpyAsync(cost, dcost, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
-  if (status) HIPCHK(hipMemcpyAsync(status, dstat, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-  if (iters) HIPCHK(hipMemcpyAsync(iters, dit, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-  if (kkt) HIPCHK(hipMemcpyAsync(kkt, dkkt, (size_t)B * 24, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return MYR_OK;
+  const SolveCall d{B, dz, dlb, dub, npar ? dp : nullptr, params_stride, user.so, nl ? dlam : nullptr, dcost, dstat, dit, dkkt};      // the batch in the staging buffer
+  if (int rc = solve_restored(h, d)) return rc;
+  return download_solve(h, d, user);
 }
 
 // ---- myr_solve_x0: B instances that differ in their START STATE only ------------------------------------------------
@@ -1960,77 +1888,55 @@ __global__ void pack_x0_kernel(long total, int n, int ns, int xcount, const doub
 extern "C" int myr_solve_x0(myr_handle h, int32_t B, const double* x0s, const double* g0, const double* g1, const double* lb,
                             const double* ub, const double* params, int32_t params_stride, const myr_solve_opts* opts,
                             double* z, double* lam, double* cost, int32_t* status, int32_t* iters, double* kkt, int32_t mem) {
-  if (!h || !x0s || !g0 || !g1 || !lb || !ub || !z) return fail(MYR_E_ARG, "myr_solve_x0: null handle, x0s, g0, g1, lb, ub or z");
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, "myr_solve_x0");
-  if (B < 0) return fail(MYR_E_ARG, "myr_solve_x0: negative batch");
-  if (B == 0) { h->info_start.clear(); h->info_attempts.clear(); h->info_restored.clear(); return MYR_OK; }
-  if (params && params_stride != 0 && params_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_solve_x0: params_stride must be 0 (shared) or np");
-  if (!params && h->d.system_id == MYR_SYS_NODE_CARTPOLE) return fail(MYR_E_ARG, "myr_solve_x0: a NODE system needs its weights in `params`");
-  if (mem != MYR_MEM_HOST && mem != MYR_MEM_DEVICE) return fail(MYR_E_ARG, "myr_solve_x0: bad mem kind");
-  myr_solve_opts so;
-  if (opts) so = *opts; else myr_default_solve_opts(&so);
-  if (so.max_iter < 0 || !(so.tol_feas > 0) || !(so.tol_stat > 0) || !(so.tol_compl > 0) || !(so.mu_init > 0))
-    return fail(MYR_E_ARG, "myr_solve_x0: bad options");
+  SolveCall user{B, z, nullptr, nullptr, params, params_stride, {}, lam, cost, status, iters, kkt};      // (lb, ub are templates here: the batch's bounds are made below)
+  bool empty = false;
+  if (int rc = check_solve_args(h, "myr_solve_x0", "x0s, g0, g1, lb, ub or z", !x0s || !g0 || !g1 || !lb || !ub || !z, &mem, opts, &user, &empty)) return rc;
+  if (empty) return MYR_OK;
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
   const bool host = mem == MYR_MEM_HOST;
   const size_t nz = (size_t)B * dm.n, nl = lam ? (size_t)B * dm.m : 0, nx0 = (size_t)B * dm.ns;
   const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };
   // device scratch: the expanded bounds always; for host callers also the iterate, the inputs and the results
   size_t total = 2 * al(nz);
   if (host) total += al(nz) + al(nx0) + 4 * al((size_t)dm.n) + al(nl) + al(npar) + al(B) + al(B) + al(3 * (size_t)B);
-  int rc = ensure_dbuf(h, total * 8);
-  if (rc) return rc;
+  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * 8)) return rc;
   double* dlb = (double*)h->dbuf;
   double* dub = dlb + al(nz);
-  double* dz = z; const double* dx0 = x0s; const double* dg0 = g0; const double* dg1 = g1; const double* dlt = lb; const double* dut = ub;
-  const double* dpar = params;
-  double* dlam = lam; double* dcost = cost; int32_t* dstat = status; int32_t* dit = iters; double* dkkt = kkt;
+  SolveCall d = user;      // the batch the solver sees: a device caller's own arrays with the expanded bounds; a host caller's all staged
+  d.lb = dlb; d.ub = dub;
+  const double* dx0 = x0s; const double* dg0 = g0; const double* dg1 = g1; const double* dlt = lb; const double* dut = ub;
   if (host) {
     double* q = dub + al(nz);
-    dz = q; q += al(nz);
+    d.z = q; q += al(nz);
     double* hx0 = q; q += al(nx0);
     double* tpl = q; q += 4 * al((size_t)dm.n);
-    dlam = nl ? q : nullptr; q += al(nl);
+    d.lam = nl ? q : nullptr; q += al(nl);
     double* hp = q; q += al(npar);
-    dcost = q; q += al(B);
-    dstat = (int32_t*)q; dit = dstat + B; q += al(B);
-    dkkt = q;
+    d.cost = q; q += al(B);
+    d.status = (int32_t*)q; d.iters = d.status + B; q += al(B);
+    d.kkt = q;
     HIPCHK(hipMemcpyAsync(hx0, x0s, nx0 * 8, hipMemcpyHostToDevice, h->stream));
     const double* src[4] = {g0, g1, lb, ub};
     for (int k = 0; k < 4; ++k) HIPCHK(hipMemcpyAsync(tpl + k * al((size_t)dm.n), src[k], (size_t)dm.n * 8, hipMemcpyHostToDevice, h->stream));
     if (npar) HIPCHK(hipMemcpyAsync(hp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
     dx0 = hx0; dg0 = tpl; dg1 = tpl + al((size_t)dm.n); dlt = tpl + 2 * al((size_t)dm.n); dut = tpl + 3 * al((size_t)dm.n);
-    dpar = npar ? hp : nullptr;
+    d.params = npar ? hp : nullptr;
   }
   {
     const long tz = (long)nz;
     long blocks = (tz + 255) / 256; if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(pack_x0_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, dm.n, dm.ns, dm.x_rows * dm.ns, dx0, dg0, dg1, dlt, dut, dz, dlb, dub);
+    hipLaunchKernelGGL(pack_x0_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, dm.n, dm.ns, dm.x_rows * dm.ns, dx0, dg0, dg1, dlt, dut, d.z, dlb, dub);
     HIPCHK(hipGetLastError());
   }
-  rc = solve_restored(h, B, dz, dlb, dub, dpar, params_stride, so, dlam, dcost, dstat, dit, dkkt);
-  if (rc) return rc;
-  if (host) {
-    HIPCHK(hipMemcpyAsync(z, dz, nz * 8, hipMemcpyDeviceToHost, h->stream));
-    if (nl) HIPCHK(hipMemcpyAsync(lam, dlam, nl * 8, hipMemcpyDeviceToHost, h->stream));
-    if (cost) HIPCHK(hipMemcpyAsync(cost, dcost, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, dstat, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    if (iters) HIPCHK(hipMemcpyAsync(iters, dit, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    if (kkt) HIPCHK(hipMemcpyAsync(kkt, dkkt, (size_t)B * 24, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return MYR_OK;
+  if (int rc = solve_restored(h, d)) return rc;
+  return host ? download_solve(h, d, user) : MYR_OK;
 }
 
 static int dispatch_rollout(myr_handle h, int B, int num_steps, int u_rows, const double* x0, const double* us,
                             const double* params, int pstride, double* xs, double* cost) {
-  KTimer& kt = h->kt[MYR_K_ROLLOUT];
-  if (int rc_fill = stack_fill(h)) return rc_fill;
-  HIPCHK(hipEventRecord(kt.a, h->stream));
-  int rc = MYR_E_ARG;
+  int rc = timed_begin(h, MYR_K_ROLLOUT);
+  if (rc) return rc;
   switch (h->d.system_id) {
 #define X(N) case MYR_SYS_##N: rc = rollout_for_system<Sys##N>(h, B, num_steps, u_rows, x0, us, params, pstride, xs, cost); break;
     MYR_CLOSED_FORM_SYSTEMS(X)
@@ -2039,13 +1945,7 @@ static int dispatch_rollout(myr_handle h, int B, int num_steps, int u_rows, cons
     default: return no_such_path(h, "rollout");
   }
   if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(kt.b, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-  kt.sum_ms += ms; kt.launches += 1;
-  return MYR_OK;
+  return timed_end(h, MYR_K_ROLLOUT);
 }
 
 extern "C" int myr_rollout(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* x0, const double* us,
@@ -2064,8 +1964,7 @@ extern "C" int myr_rollout(myr_handle h, int32_t B, int32_t num_steps, int32_t u
   const size_t nx0 = (size_t)B * dm.ns, nus = (size_t)B * u_rows * dm.nu;
   const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
   const size_t nxs = xs ? (size_t)B * (num_steps + 1) * dm.ns : 0, nc = cost ? (size_t)B : 0;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };
-  int rc = ensure_dbuf(h, (al(nx0) + al(nus) + al(npar) + al(nxs) + al(nc)) * 8);
+  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nx0) + al(nus) + al(npar) + al(nxs) + al(nc)) * 8);
   if (rc) return rc;
   double* dx0 = (double*)h->dbuf;
   double* dus = dx0 + al(nx0);
@@ -2103,10 +2002,9 @@ extern "C" int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, co
   if (discrete && !params) return fail(MYR_E_ARG, "myr_fbsm: a discrete system needs `params`");
   const size_t rows_x = (size_t)(N + 1) * dm.ns, rows_u = (size_t)(N + (discrete ? 0 : 1)) * dm.nu;
   const size_t nx0 = (size_t)B * dm.ns, npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  auto al = [](size_t v) { return (v + 1) & ~(size_t)1; };
   // batch-minor working arrays + instance-major staging for the transposes + sweeps
   const size_t work = (2 * rows_x + rows_u) * (size_t)Bp, stage = (size_t)B * (rows_x > rows_u ? rows_x : rows_u);
-  int rc = ensure_dbuf(h, (al(nx0) + al(npar) + al((size_t)dm.ns) + al(work) + al(stage) + al((size_t)B)) * 8);
+  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nx0) + al(npar) + al((size_t)dm.ns) + al(work) + al(stage) + al((size_t)B)) * 8);
   if (rc) return rc;
   double* dx0 = (double*)h->dbuf;
   double* dp = dx0 + al(nx0);
@@ -2125,19 +2023,10 @@ extern "C" int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, co
     MYR_CLOSED_FORM_SYSTEMS(X)
 #undef X
     case MYR_SYS_INVASIVEPLANT: {
-      KTimer& kt = h->kt[MYR_K_FBSM];
-      if (int rc_fill = stack_fill(h)) return rc_fill;
-      HIPCHK(hipEventRecord(kt.a, h->stream));
+      if (int rc_begin = timed_begin(h, MYR_K_FBSM)) return rc_begin;
       hipLaunchKernelGGL(fbsm_discrete_kernel<DiscINVASIVEPLANT>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, Bp, N, dx0,
                          adj_T ? dadj : nullptr, dp, params_stride, vlo, vhi, delta, max_sweeps, X, U, A, dsw);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(kt.b, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, kt.a, kt.b));
-      kt.sum_ms += ms;
-      kt.launches += 1;
-      rc = MYR_OK;
+      rc = timed_end(h, MYR_K_FBSM);
       break;
     }
     default: rc = fail(MYR_E_UNSUPPORTED, "myr_fbsm: this system has no adjoint dynamics");
