@@ -70,29 +70,6 @@ struct HsSolveOpts {
   double rho_term = 1e4;   // quadratic weight on pinned terminal states inside the QP (does not change its solution)
 };
 
-// penalty relaxation of the l1 merit function (compile-time: the by-value options struct of the kernels is left alone,
-// see DESIGN.md on the compiler's sensitivity to its layout): the penalty only has to dominate the CURRENT multipliers;
-// steps blocked by bounds early on can push it orders of magnitude above that, after which every full step is rejected
-// for a marginal increase of the constraint violation (Maratos-type crawl: config 3's stragglers).  When it has
-// exceeded PEN_RELAX_RATIO x the value the descent condition asks for during PEN_RELAX consecutive iterations it is
-// reset to twice that value, at most PEN_RELAX_MAX times per solve (so the monotone argument applies from then on).
-#ifndef MYR_PEN_RELAX
-#define MYR_PEN_RELAX 5          // 0 = off
-#endif
-// warm-started inertia correction (delta_warm): the first attempt of an iteration uses delta_last / DELTA_WARM_DIV; a
-// failed attempt multiplies by 8, i.e. lands at 1.33 delta_last.  Measured on the headline workload (ms per 4096
-// solves / median / p99 iterations): div 3: 39.1 / 21 / 34, 4: 39.7 / 21 / 34, 5: 38.0 / 21 / 26, 6: 36.1 / 20 / 25,
-// 8: 38.9 / 20 / 25, 12: 38.7 / 21 / 27 -- with 3 the retry overshoots to 2.7 delta_last and the correction ratchets up.
-#ifndef MYR_DW_DIV
-#define MYR_DW_DIV 6.0
-#endif
-constexpr double DELTA_WARM_DIV = MYR_DW_DIV;
-constexpr int PEN_RELAX = MYR_PEN_RELAX, PEN_RELAX_MAX = 8;
-#ifndef MYR_PEN_RELAX_LAM
-#define MYR_PEN_RELAX_LAM 1.1
-#endif
-constexpr double PEN_RELAX_RATIO = 10.0, PEN_RELAX_LAM = MYR_PEN_RELAX_LAM;
-
 struct HsSolveResult {
   int status, iters;
   int sweeps = 0;          // factorisation sweeps incl. inertia-correction retries
@@ -251,6 +228,9 @@ MYR_HD inline void chol_solve(const double* a, double* b) {
 }
 
 }  // namespace detail
+}  // namespace myriad
+#include "ip_policy.h"   // the interior-point loop's scalar state and rules (uses HsSolveOpts and detail:: above)
+namespace myriad {
 
 // One collocation point's linearisation.
 template <class Sys>
@@ -980,126 +960,69 @@ struct IpLoop {
     using FwdOut = typename Core::FwdOut;
     const int n = Core::nvars(o);
     Core::init(w, n);
-    double mu = o.mu_init, pen = 1.0;
-    int pen_over = 0, pen_cuts = 0;
-    double nuT[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) nuT[i] = 0.0;
-    const double mu_min = dmin(o.tol_compl, o.tol_stat) * 0.1;
+    IpState<NS> s;
+    double hist[NMMAX];
+    s.start(o);
     res.status = 1; res.iters = o.max_iter;
-    int stall = 0, small_steps = 0;
-    double delta_last = 0.0, lm = 0.0;
-    constexpr int NMMAX = 8;
-    double hist[NMMAX]; int nhist = 0, hpos = 0; double hist_mu = -1.0, hist_pen = -1.0;
     SweepOut so;
     for (int it = 0; it <= o.max_iter; ++it) {
-      // inertia correction (global, as in interior-point NLP codes): retry the factorisation with W + delta I
-      // until every stage pivot is positive; the last resort keeps the stage-local convexification.
-      double delta = lm;     // Levenberg-Marquardt floor adapted from the line-search history (see below)
-      if (o.delta_warm && delta_last > o.delta_warm_min) delta = dmax(delta, delta_last / DELTA_WARM_DIV);   // skip the doomed delta = 0 attempt
+      double delta = s.first_delta(o);
       for (int tr_ = 0; tr_ < 12; ++tr_) {
+        // every rung but the last gives up at its first regularised pivot (the last keeps the stage-local convexification).  The wavefront
+        // kernels (IpState::rung_aborts) also stop giving up beyond delta = 1e8 and end the ladder there; here it goes on to its twelfth rung.
         so.abort_on_reg = (tr_ < 11);
-        Core::backward(w, o, p, nuT, delta, so);
+        Core::backward(w, o, p, s.nuT, delta, so);
         ++res.sweeps;
         if (so.nreg == 0) break;
-        if (delta == 0.0) delta = (delta_last > 0.0) ? dmax(1e-8, delta_last / 3.0) : 1e-4;
-        else delta *= (delta_last > 0.0) ? 8.0 : 100.0;
-        if (delta > 1e8) { so.abort_on_reg = false; }
+        delta = s.next_delta(delta);
       }
-      delta_last = (delta > lm) ? delta : 0.0;
-      // KKT error with the usual multiplier scaling
-      double sd = 1.0;
-      {
-        double sm = so.sum_mult; int nm = so.n_mult;
-        for (int i = 0; i < n; ++i) {
-          const double l = w.lb[i], u = w.ub[i], zl = w.zL[i], zu = w.zU[i];
-          const bool fr = l < u;
-          const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-          sm += (hl ? zl : 0.0) + (hu ? zu : 0.0);
-          nm += (hl ? 1 : 0) + (hu ? 1 : 0);
-        }
-        if (nm > 0) sd = dmax(1.0, sm / nm / 100.0);
+      s.close_ladder(delta);
+      // the bound multipliers join the sweep's sums here; the wavefront kernels get them from their linearisation pass
+      double sm = so.sum_mult; int nm = so.n_mult;
+      for (int i = 0; i < n; ++i) {
+        const double l = w.lb[i], u = w.ub[i], zl = w.zL[i], zu = w.zU[i];
+        const bool fr = l < u;
+        const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
+        sm += (hl ? zl : 0.0) + (hu ? zu : 0.0);
+        nm += (hl ? 1 : 0) + (hu ? 1 : 0);
       }
-      const double stat = so.stat / sd, comp = so.compl_max / sd;
-      res.cost = so.f; res.feas = so.cinf; res.stat = stat; res.compl_ = comp;
-      if (!(finite_(so.f) && finite_(so.cinf) && finite_(so.stat))) { res.status = 2; res.iters = it; return; }
-      if (so.cinf <= o.tol_feas && stat <= o.tol_stat && comp <= o.tol_compl) { res.status = 0; res.iters = it; return; }
+      const IpKkt k = s.kkt(o, sm, nm, so.f, so.stat, so.compl_max, so.cinf);
+      res.cost = so.f; res.feas = so.cinf; res.stat = k.stat; res.compl_ = k.comp;
+      if (!k.finite) { res.status = 2; res.iters = it; return; }
+      if (k.converged) { res.status = 0; res.iters = it; return; }
       if (it == o.max_iter) break;
-      // barrier update (monotone, superlinear): error of the barrier problem vs kappa_eps * mu
-      for (int guard = 0; guard < 8; ++guard) {
-        // error of the barrier problem: complementarity |s*z - mu| from the extreme products
-        const double cerr = (so.compl_min <= so.compl_max) ? dmax(fabs(so.compl_max - mu), fabs(so.compl_min - mu)) : 0.0;
-        const double emu = dmax(dmax(stat, so.cinf), cerr / sd);
-        if (emu <= o.kappa_eps * mu && mu > mu_min) {
-          const double nm = dmax(mu_min, dmin(o.kappa_mu * mu, pow(mu, o.theta_mu)));
-          mu = nm;
-        } else break;
-      }
+      s.barrier_update(o, k, so.cinf, so.compl_min, so.compl_max);      // (after the sweep; HsFused::solve has tests and update in front of it)
       double nu[NS];
-      Core::solve_nu(so, mu, nu);
+      Core::solve_nu(so, s.mu, nu);
       FwdOut fo;
-      Core::forward(w, o, p, mu, nu, so.term_pinned, fo);
+      Core::forward(w, o, p, s.mu, nu, so.term_pinned, fo);
       if (!(finite_(fo.gphi) && finite_(fo.alpha_p))) { res.status = 2; res.iters = it; return; }
-      // l1 merit: penalty large enough to make dz a descent direction
-      if (so.c1 > 0.0) {
-        const double need = fo.gphi / (0.9 * so.c1);
-        if (pen < need) pen = need + 1.0;
-        if (PEN_RELAX > 0) {
-          // never below the multipliers where the core asks for it (exactness of the l1 penalty): single shooting, whose
-          // stragglers need it (config 3: slowest solve 257 -> 130 iterations).  The collocation cores keep the plain
-          // rule: with the floor the trapezoidal lane kernel lost 9 % of a CARTPOLE batch on the GPU -- in fixed lane
-          // positions, and not on the host build of the same code (compiler fragility).
-          const double floor_ = Core::PEN_LAM_FLOOR ? PEN_RELAX_LAM * so.lam_inf : 0.0;
-          const double want = dmax(2.0 * dmax(need, 0.0) + 1.0, floor_);
-          pen_over = (pen > PEN_RELAX_RATIO * want) ? pen_over + 1 : 0;
-          if (pen_over >= PEN_RELAX && pen_cuts < PEN_RELAX_MAX) { pen = want; pen_over = 0; ++pen_cuts; }
-        }
-      }
-      const double Dphi = fo.gphi - pen * so.c1;
+      // never below the multipliers where the core asks for it (exactness of the l1 penalty): single shooting, whose stragglers need it (config 3:
+      // slowest solve 257 -> 130 iterations).  The collocation cores keep the plain rule: with the floor the trapezoidal lane kernel lost 9 % of a
+      // CARTPOLE batch on the GPU -- in fixed lane positions, and not on the host build of the same code (compiler
+      // fragility).  The wavefront loops pass no floor.
+      const double Dphi = s.penalty_update(fo.gphi, so.c1, Core::PEN_LAM_FLOOR ? PEN_RELAX_LAM * so.lam_inf : 0.0);
+      // merit value at alpha = 0 from a trial of its own (the wavefront loops take it from by-products of the linearisation)
       double f0, bar0, c10;
-      Core::trial(w, o, p, 0.0, mu, f0, bar0, c10);
-      const double phi0 = f0 + bar0 + pen * c10;
-      // non-monotone Armijo reference (Grippo-Lampariello-Lucidi): the largest of the last NM merit values of the
-      // SAME merit function (history is dropped whenever mu or the penalty changes); cures Maratos-type stalls
-      if (mu != hist_mu || pen != hist_pen) { nhist = 0; hpos = 0; hist_mu = mu; hist_pen = pen; }
-      double phiref = phi0;
-      for (int j = 0; j < nhist; ++j) phiref = dmax(phiref, hist[j]);
-      if (o.nonmono > 0) { hist[hpos % o.nonmono] = phi0; ++hpos; if (nhist < o.nonmono) ++nhist; }
+      Core::trial(w, o, p, 0.0, s.mu, f0, bar0, c10);
+      const double phi0 = f0 + bar0 + s.pen * c10;
+      const double phiref = s.merit_reference(o, hist, phi0);
       double a = fo.alpha_p;
       bool ok = false;
       for (int ls = 0; ls < 40; ++ls) {
         double ft, bt, ct;
-        if (Core::trial(w, o, p, a, mu, ft, bt, ct)) {
-          const double phit = ft + bt + pen * ct;
-          if (phit <= phiref + 1e-8 * a * Dphi + 1e-13 * fabs(phi0)) { ok = true; break; }
-        }
+        if (Core::trial(w, o, p, a, s.mu, ft, bt, ct) && s.accepts(ft + bt + s.pen * ct, phiref, a, Dphi, phi0)) { ok = true; break; }
         a *= 0.5;
       }
-      if (!ok) {
-        // no acceptable step along dz: take the tiny step anyway a few times (helps past round-off), then give up
-        if (++stall > 5) { res.status = 3; res.iters = it; return; }
-      } else stall = 0;
-      // bound multipliers follow the primal backtracking factor (keeps s*z near mu when the line search cuts the step)
-      const double ad = o.dual_follow ? fo.alpha_d * (a / fo.alpha_p) : fo.alpha_d;
+      if (s.stalled(ok)) { res.status = 3; res.iters = it; return; }
+      const double ad = s.dual_step(o, a, fo.alpha_p, fo.alpha_d);
 #ifdef MYR_TRACE
-      printf("it %3d f=%.8f cinf=%.2e stat=%.2e comp=%.2e mu=%.1e a=%.3g amax=%.3g ad=%.3g nreg=%d pen=%.3g gphi=%.3g ok=%d\n", it, so.f, so.cinf, stat, comp, mu, a, fo.alpha_p, ad, so.nreg, pen, fo.gphi, (int)ok);
+      printf("it %3d f=%.8f cinf=%.2e stat=%.2e comp=%.2e mu=%.1e a=%.3g amax=%.3g ad=%.3g nreg=%d pen=%.3g gphi=%.3g ok=%d\n", it, so.f, so.cinf, k.stat, k.comp, s.mu, a, fo.alpha_p, ad, so.nreg, s.pen, fo.gphi, (int)ok);
 #endif
-      Core::update(w, n, a, ad, mu, o.kappa_sigma);
+      Core::update(w, n, a, ad, s.mu, o.kappa_sigma);
 #pragma unroll
-      for (int i = 0; i < NS; ++i) nuT[i] += a * (nu[i] - nuT[i]);
-      // re-centering: a run of tiny accepted steps means the iterate left the neighbourhood of the central path for
-      // this mu (barrier parameter reduced too early); go back up one decade instead of crawling
-      // step-quality feedback: a step cut hard by the line search means the quadratic model over-reaches ->
-      // damp the next Newton system (W + lm I); full steps relax the damping again
-      if (o.lm_init > 0.0) {
-        const double ratio = o.lm_abs ? a : a / fo.alpha_p;   // step actually taken, relative to the full Newton step
-        if (ratio <= 0.25) lm = dmin(1e2, dmax(o.lm_init, 4.0 * lm));
-        else if (ratio >= 0.99) { lm *= 0.25; if (lm < 0.1 * o.lm_init) lm = 0.0; }
-      }
-      if (o.recenter > 0) {
-        small_steps = (a < o.recenter_alpha) ? small_steps + 1 : 0;
-        if (small_steps >= o.recenter && mu < o.mu_init) { mu = dmin(o.mu_init, 10.0 * mu); small_steps = 0; }
-      }
+      for (int i = 0; i < NS; ++i) s.follow_nu(i, a, nu[i]);
+      s.after_step(o, a, fo.alpha_p);
     }
     res.status = 1; res.iters = o.max_iter;
   }

@@ -2452,22 +2452,18 @@ struct HsFused {
     if (c.tid < ZR) c.zr[c.tid] = 0.0;
   }
 
-  // ---- the solve (control flow identical to HsWave::solve / HsSolver::solve) -----------------------------------------------------
+  // ---- the solve: this kernel's passes around the one interior-point policy of ip_policy.h ---------------------------------------
   __device__ static void solve(Ctx& c, const HsSolveOpts& o, const double* zg, HsSolveResult& res, int park_mode = 0, int park_k1 = 0,
                                double* sv = nullptr) {
     using namespace detail;
-    constexpr int NMMAX = 8;
-    static_assert(17 + NS + NMMAX + 5 <= NSCAL, "record of a parked trajectory");
-    double mu = o.mu_init, pen = 1.0;
-    int pen_over = 0, pen_cuts = 0;
-    double nuT[NS];
+    // the record of a parked trajectory: the policy's block (IpState::save / load), then this kernel's own five doubles
+    constexpr int PK_UNI = IpState<NS>::RECORD, PK_RES = PK_UNI + 1;
+    static_assert(PK_RES + 4 <= NSCAL, "record of a parked trajectory");
+    IpState<NS> s;                     // the loop's scalars and every rule on them: ip_policy.h
+    double hist[NMMAX];
+    s.start(o);
 #pragma unroll
-    for (int i = 0; i < NS; ++i) nuT[i] = 0.0;
-    int stall = 0, small_steps = 0;
-    double delta_last = 0.0, lm = 0.0;
-    double hist[NMMAX]; int nhist = 0, hpos = 0; double hist_mu = -1.0, hist_pen = -1.0;
-#pragma unroll
-    for (int i = 0; i < NMMAX; ++i) hist[i] = 0.0;
+    for (int i = 0; i < NMMAX; ++i) hist[i] = 0.0;      // (this loop only: the park record holds every entry)
     Step pending{false, 0.0, 0.0, 0.0, o.kappa_sigma};
     int it0 = 0;
     res.cost = 0.0; res.feas = 0.0; res.stat = 0.0; res.compl_ = 0.0;
@@ -2480,22 +2476,15 @@ struct HsFused {
         for (int i = c.tid; i < 2 * c.n; i += NT) c.zL[i] = __builtin_nontemporal_load(&sv[NSCAL + nl + i]);      // (zU follows zL)
       }
       if (c.tid < ZR) c.zr[c.tid] = 0.0;
-      mu = sv[0]; pen = sv[1]; pen_over = (int)sv[2]; pen_cuts = (int)sv[3]; stall = (int)sv[4]; small_steps = (int)sv[5];
-      delta_last = sv[6]; lm = sv[7]; nhist = (int)sv[8]; hpos = (int)sv[9]; hist_mu = sv[10]; hist_pen = sv[11];
-      pending.on = sv[12] != 0.0; pending.ap = sv[13]; pending.ad = sv[14]; pending.mu = sv[15]; pending.ksig = sv[16];
-#pragma unroll
-      for (int i = 0; i < NS; ++i) nuT[i] = sv[17 + i];
-#pragma unroll
-      for (int i = 0; i < NMMAX; ++i) hist[i] = sv[17 + NS + i];
-      c.uni = sv[17 + NS + NMMAX] != 0.0;
-      res.cost = sv[18 + NS + NMMAX]; res.feas = sv[19 + NS + NMMAX]; res.stat = sv[20 + NS + NMMAX]; res.compl_ = sv[21 + NS + NMMAX];
+      s.load(sv, hist, pending);
+      c.uni = sv[PK_UNI] != 0.0;
+      res.cost = sv[PK_RES]; res.feas = sv[PK_RES + 1]; res.stat = sv[PK_RES + 2]; res.compl_ = sv[PK_RES + 3];
       it0 = park_k1;
     } else
       init(c, zg);
     wsync();
 #pragma unroll
     for (int q = 0; q < NS; ++q) c.term_pinned[q] = !(c.sB[2 * NW + q] < c.sB[3 * NW + q]);
-    const double mu_min = dmin(o.tol_compl, o.tol_stat) * 0.1;
     res.status = 1; res.iters = o.max_iter;
     for (int it = it0; it <= o.max_iter; ++it) {
       if (park_mode == 1 && it == park_k1) {
@@ -2506,57 +2495,38 @@ struct HsFused {
           for (int i = c.tid; i < 2 * c.n; i += NT) __builtin_nontemporal_store(c.zL[i], &sv[NSCAL + nl + i]);
         }
         if (c.tid == 0) {
-          sv[0] = mu; sv[1] = pen; sv[2] = (double)pen_over; sv[3] = (double)pen_cuts; sv[4] = (double)stall; sv[5] = (double)small_steps;
-          sv[6] = delta_last; sv[7] = lm; sv[8] = (double)nhist; sv[9] = (double)hpos; sv[10] = hist_mu; sv[11] = hist_pen;
-          sv[12] = pending.on ? 1.0 : 0.0; sv[13] = pending.ap; sv[14] = pending.ad; sv[15] = pending.mu; sv[16] = pending.ksig;
-#pragma unroll
-          for (int i = 0; i < NS; ++i) sv[17 + i] = nuT[i];
-#pragma unroll
-          for (int i = 0; i < NMMAX; ++i) sv[17 + NS + i] = hist[i];
-          sv[17 + NS + NMMAX] = c.uni ? 1.0 : 0.0;
-          sv[18 + NS + NMMAX] = res.cost; sv[19 + NS + NMMAX] = res.feas; sv[20 + NS + NMMAX] = res.stat; sv[21 + NS + NMMAX] = res.compl_;
+          s.save(sv, hist, pending);
+          sv[PK_UNI] = c.uni ? 1.0 : 0.0;
+          sv[PK_RES] = res.cost; sv[PK_RES + 1] = res.feas; sv[PK_RES + 2] = res.stat; sv[PK_RES + 3] = res.compl_;
         }
         res.status = MYR_STATUS_PARKED_; res.iters = it;
         return;
       }
       if constexpr (MLP) { if (c.board) coop_refresh(c); }      // helper workgroups attached since the last iteration?
       BOut p1;
-      { NuT nu_; for (int q = 0; q < NS; ++q) nu_.v[q] = nuT[q]; p1 = backward_pass(c, pending, nu_); }
+      { NuT nu_; for (int q = 0; q < NS; ++q) nu_.v[q] = s.nuT[q]; p1 = backward_pass(c, pending, nu_); }
       pending.on = false;
       c.h_valid = false;                    // (from here on the store holds the activations of THIS iterate, whichever pass wrote them; the flag is for the next linearisation)
       wsync();
       MYR_PH(0)
       double stat_raw;
-      const double mu_hess = mu;              // (two-level sweep: the records' "1" column holds g0 + mu_hess g1)
-      stat_raw = hessian_pass(c, mu);
+      const double mu_hess = s.mu;            // (two-level sweep: the records' "1" column holds g0 + mu_hess g1)
+      stat_raw = hessian_pass(c, s.mu);
       wsync();
       MYR_PH(4)
       const double c1 = p1.c1, cinf = p1.cinf, sum_mult = p1.sum_mult;
-      double delta = lm;
-      if (o.delta_warm && delta_last > o.delta_warm_min) delta = dmax(delta, delta_last / DELTA_WARM_DIV);
+      double delta = s.first_delta(o);
       int nreg = 0;
-      auto next_delta = [&](double d) {       // the inertia-correction ladder (IPOPT's: first 1e-4 or a third of the last one, then x 100 / x 8)
-        return d == 0.0 ? ((delta_last > 0.0) ? dmax(1e-8, delta_last / 3.0) : 1e-4) : d * ((delta_last > 0.0) ? 8.0 : 100.0);
-      };
       // (Two-level sweep: the barrier parameter is folded into the sweep's "1" column, so the tests and the barrier update come BEFORE the sweep -- they
       // depend on the two passes above only.  Every form has this order since round 6: the converged iteration then returns WITHOUT its sweep, one
       // sweep in twenty-one of a headline solve, same bits.  Round 5's order -- the last iteration's sweep run and dropped -- is in the history at 2373201.)
       {
-        const int nm = MLAM * c.N * NS + p1.nm;
-        const double sd = nm > 0 ? dmax(1.0, (sum_mult + p1.sm) / nm / 100.0) : 1.0;
-        const double stat = stat_raw / sd, comp = p1.cmax / sd;
-        res.cost = p1.f; res.feas = cinf; res.stat = stat; res.compl_ = comp;
-        if (__builtin_amdgcn_readfirstlane((int)!(finite_(p1.f) && finite_(cinf) && finite_(stat_raw)))) { res.status = 2; res.iters = it; return; }
-        if (__builtin_amdgcn_readfirstlane((int)(cinf <= o.tol_feas && stat <= o.tol_stat && comp <= o.tol_compl))) { res.status = 0; res.iters = it; return; }
+        const IpKkt k = s.kkt(o, sum_mult + p1.sm, MLAM * c.N * NS + p1.nm, p1.f, stat_raw, p1.cmax, cinf);
+        res.cost = p1.f; res.feas = cinf; res.stat = k.stat; res.compl_ = k.comp;
+        if (__builtin_amdgcn_readfirstlane((int)!k.finite)) { res.status = 2; res.iters = it; return; }
+        if (__builtin_amdgcn_readfirstlane((int)k.converged)) { res.status = 0; res.iters = it; return; }
         if (it == o.max_iter) break;
-        for (int guard = 0; guard < 8; ++guard) {
-          const double cerr = (p1.cmin <= p1.cmax) ? dmax(fabs(p1.cmax - mu), fabs(p1.cmin - mu)) : 0.0;
-          const double emu = dmax(dmax(stat, cinf), cerr / sd);
-          if (emu <= o.kappa_eps * mu && mu > mu_min) {
-            const double nmu = dmax(mu_min, dmin(o.kappa_mu * mu, pow(mu, o.theta_mu)));
-            mu = nmu;
-          } else break;
-        }
+        s.barrier_update(o, k, cinf, p1.cmin, p1.cmax);
       }
       // (Speculative second rung, -DMYR_FUSED_SPEC -- the W > 1 forms without a two-level sweep: trapezoidal, the block sweep of the wider systems.
       // Round 4 saw TIMBERHARVEST N = 6 take another path from handle to handle in this form; round 5 traced it to a spill the compiler placed in front of
@@ -2572,14 +2542,14 @@ struct HsFused {
         // (tl_join) and eliminates the first point.  One rung of the inertia ladder = W chunk sweeps side by side + the join; a rung fails when a
         // stage pivot of any chunk, a pivot of an interface or the first point's is not positive.  (The speculative second rung of round 5 is gone:
         // wavefront 1 has its own chunk to sweep.)
-        if (__builtin_amdgcn_readfirstlane((int)(mu != mu_hess))) {      // the barrier parameter moved after the hessian pass wrote g0 + mu g1: add the difference
-          tl_fold(c, mu - mu_hess);
+        if (__builtin_amdgcn_readfirstlane((int)(s.mu != mu_hess))) {      // the barrier parameter moved after the hessian pass wrote g0 + mu g1: add the difference
+          tl_fold(c, s.mu - mu_hess);
           wsync();
         }
         MYR_PH(3)
         double* cnt = c.sTh + TL_TH1;         // pivot counts: the chunks', the join's
         for (int tr_ = 0; tr_ < 12; ++tr_) {
-          const bool abort_on_reg = (tr_ < 11) && !(delta > 1e8);
+          const bool abort_on_reg = s.rung_aborts(tr_, delta);
           int nr = 0;
           if (tl_edge(c.N, c.wave + 1) > tl_edge(c.N, c.wave)) nr = sweep_chunk(c, o, delta, abort_on_reg, c.wave);
           cnt[c.wave] = (double)nr;             // (every lane: the count is wave-uniform)
@@ -2614,7 +2584,7 @@ struct HsFused {
           wsync();
           MYR_PH(6)
           if (nreg == 0 || !abort_on_reg) break;
-          delta = next_delta(delta);
+          delta = s.next_delta(delta);
         }
       } else
       if constexpr (SPEC) {
@@ -2624,8 +2594,8 @@ struct HsFused {
         // iterates are those of the one-wavefront form.
         use_set(c, c.kgA, c.xA);
         for (int tr_ = 0; tr_ < 12; tr_ += 2) {
-          const double delta_b = next_delta(delta);
-          const bool abort_a = (tr_ < 11) && !(delta > 1e8), abort_b = (tr_ + 1 < 11) && !(delta_b > 1e8);
+          const double delta_b = s.next_delta(delta);
+          const bool abort_a = s.rung_aborts(tr_, delta), abort_b = s.rung_aborts(tr_ + 1, delta_b);
           {
             Ctx cw = c;
             if (c.wave == 1) use_set(cw, c.kgB, c.xB);
@@ -2647,11 +2617,11 @@ struct HsFused {
             wsync();
             break;
           }
-          delta = next_delta(delta_b);
+          delta = s.next_delta(delta_b);
         }
       } else {
         for (int tr_ = 0; tr_ < 12; ++tr_) {
-          const bool abort_on_reg = (tr_ < 11) && !(delta > 1e8);
+          const bool abort_on_reg = s.rung_aborts(tr_, delta);
           if constexpr (W > 1) {
             if (c.wave == 0) {
               nreg = sweep(c, o, delta, abort_on_reg);
@@ -2664,14 +2634,14 @@ struct HsFused {
           MYR_PH(6)
           if (nreg == 0) break;
           if (!abort_on_reg) break;
-          delta = next_delta(delta);
+          delta = s.next_delta(delta);
         }
       }
-      delta_last = (delta > lm) ? delta : 0.0;
+      s.close_ladder(delta);
 #ifdef MYR_TRACE
       if (c.lane == 0 && c.traj < MYR_TRACE)
         printf("T b%d w%d it%d f=%.17g c1=%.17g cinf=%.17g stat=%.17g sm=%.17g lg=%.17g nreg=%d delta=%.9g mu=%.9g pen=%.9g\n", c.traj, c.wave, it,
-               p1.f, p1.c1, p1.cinf, stat_raw, p1.sum_mult, p1.lg, nreg, delta, mu, pen);
+               p1.f, p1.c1, p1.cinf, stat_raw, p1.sum_mult, p1.lg, nreg, delta, s.mu, s.pen);
 #endif
       typename S::SweepOut so;
 #pragma unroll
@@ -2679,9 +2649,9 @@ struct HsFused {
 #pragma unroll
       for (int i = 0; i < NS; ++i) so.term_pinned[i] = c.term_pinned[i];
       double nu[NS];
-      S::solve_nu(so, TL ? 0.0 : mu, nu);      // (two-level sweep: mu is folded into the "1" column)
+      S::solve_nu(so, TL ? 0.0 : s.mu, nu);      // (two-level sweep: mu is folded into the "1" column)
       double th[NC];
-      th[0] = 1.0; th[1] = TL ? 0.0 : mu;
+      th[0] = 1.0; th[1] = TL ? 0.0 : s.mu;
 #pragma unroll
       for (int i = 0; i < NS; ++i) th[2 + i] = nu[i];
       if constexpr (TL) {
@@ -2690,59 +2660,33 @@ struct HsFused {
       }
       MYR_PH(7)
       typename S::FwdOut fo;
-      { ThT th_; for (int q = 0; q < NC; ++q) th_.v[q] = th[q]; fo = forward_pass(c, o, mu, th_); }
+      { ThT th_; for (int q = 0; q < NC; ++q) th_.v[q] = th[q]; fo = forward_pass(c, o, s.mu, th_); }
       wsync();
       MYR_PH(8)
       if (!(finite_(fo.gphi) && finite_(fo.alpha_p))) { res.status = 2; res.iters = it; return; }
-      if (c1 > 0.0) {
-        const double need = fo.gphi / (0.9 * c1);
-        if (pen < need) pen = need + 1.0;
-        if (PEN_RELAX > 0) {
-          const double want = 2.0 * dmax(need, 0.0) + 1.0;
-          pen_over = (pen > PEN_RELAX_RATIO * want) ? pen_over + 1 : 0;
-          if (pen_over >= PEN_RELAX && pen_cuts < PEN_RELAX_MAX) { pen = want; pen_over = 0; ++pen_cuts; }
-        }
-      }
-      const double Dphi = fo.gphi - pen * c1;
-      const double f0 = p1.f, bar0 = mu * p1.lg, c10 = c1;
-      const double phi0 = f0 + bar0 + pen * c10;
-      if (mu != hist_mu || pen != hist_pen) { nhist = 0; hpos = 0; hist_mu = mu; hist_pen = pen; }
-      double phiref = phi0;
-      for (int j = 0; j < nhist; ++j) phiref = dmax(phiref, hist[j]);
-      if (o.nonmono > 0) { hist[hpos % o.nonmono] = phi0; ++hpos; if (nhist < o.nonmono) ++nhist; }
+      const double Dphi = s.penalty_update(fo.gphi, c1);      // (no floor from the multipliers: that is IpLoop's, for shooting)
+      // merit value at the current point from by-products of the linearisation, as in HsWave::solve
+      const double f0 = p1.f, bar0 = s.mu * p1.lg, c10 = c1;
+      const double phi0 = f0 + bar0 + s.pen * c10;
+      const double phiref = s.merit_reference(o, hist, phi0);
       double a = fo.alpha_p;
       bool ok = false;
       for (int ls = 0; ls < 40; ++ls) {
-        double ft, bt, ct;
-        const TrialOut tr1 = trial_pass(c, a, mu);
-        ft = tr1.f; bt = tr1.bar; ct = tr1.c1;
-        if (tr1.ok) {
-          const double phit = ft + bt + pen * ct;
-          if (phit <= phiref + 1e-8 * a * Dphi + 1e-13 * fabs(phi0)) { ok = true; break; }
-        }
+        const TrialOut tr1 = trial_pass(c, a, s.mu);
+        if (tr1.ok && s.accepts(tr1.f + tr1.bar + s.pen * tr1.c1, phiref, a, Dphi, phi0)) { ok = true; break; }
         a *= 0.5;
       }
-      if (!ok) {
-        if (++stall > 5) { res.status = 3; res.iters = it; return; }
-      } else stall = 0;
+      if (s.stalled(ok)) { res.status = 3; res.iters = it; return; }
       c.h_valid = ok;                       // network systems: the accepted trial point is the next iterate, its activations are in the store
       MYR_PH(11)
 #ifdef MYR_TRACE
       if (c.lane == 0 && c.traj < MYR_TRACE)
         printf("S b%d w%d it%d ap=%.17g ad=%.17g gphi=%.17g a=%.17g ok=%d nu0=%.17g\n", c.traj, c.wave, it, fo.alpha_p, fo.alpha_d, fo.gphi, a, (int)ok, nu[0]);
 #endif
-      pending.on = true; pending.ap = a; pending.ad = o.dual_follow ? fo.alpha_d * (a / fo.alpha_p) : fo.alpha_d; pending.mu = mu;
+      pending.on = true; pending.ap = a; pending.ad = s.dual_step(o, a, fo.alpha_p, fo.alpha_d); pending.mu = s.mu;
 #pragma unroll
-      for (int i = 0; i < NS; ++i) nuT[i] += a * (nu[i] - nuT[i]);
-      if (o.lm_init > 0.0) {
-        const double ratio = o.lm_abs ? a : a / fo.alpha_p;
-        if (ratio <= 0.25) lm = dmin(1e2, dmax(o.lm_init, 4.0 * lm));
-        else if (ratio >= 0.99) { lm *= 0.25; if (lm < 0.1 * o.lm_init) lm = 0.0; }
-      }
-      if (o.recenter > 0) {
-        small_steps = (a < o.recenter_alpha) ? small_steps + 1 : 0;
-        if (small_steps >= o.recenter && mu < o.mu_init) { mu = dmin(o.mu_init, 10.0 * mu); small_steps = 0; }
-      }
+      for (int i = 0; i < NS; ++i) s.follow_nu(i, a, nu[i]);
+      s.after_step(o, a, fo.alpha_p);
       wsync();
     }
     res.status = 1; res.iters = o.max_iter;

@@ -1658,24 +1658,17 @@ struct HsWave {
     if (c.lane < ZR) c.zr[c.lane] = 0.0;
   }
 
-  // ---- the solve (control flow identical to HsSolver<Sys>::solve) ------------------------------------------------
+  // ---- the solve: this kernel's passes around the one interior-point policy of ip_policy.h ---------------------------
   __device__ static void solve(Ctx& c, const HsSolveOpts& o, HsSolveResult& res) {
     using namespace detail;
     init(c);
     wsync();
 #pragma unroll
     for (int q = 0; q < NS; ++q) { const long i = zi(c, c.K - 1, q); c.term_pinned[q] = !(c.lb[i] < c.ub[i]); }
-    double mu = o.mu_init, pen = 1.0;
-    int pen_over = 0, pen_cuts = 0;
-    double nuT[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) nuT[i] = 0.0;
-    const double mu_min = dmin(o.tol_compl, o.tol_stat) * 0.1;
+    IpState<NS> s;                     // the loop's scalars and every rule on them: ip_policy.h
+    double hist[NMMAX];
+    s.start(o);
     res.status = 1; res.iters = o.max_iter;
-    int stall = 0, small_steps = 0;
-    double delta_last = 0.0, lm = 0.0;
-    constexpr int NMMAX = 8;
-    double hist[NMMAX]; int nhist = 0, hpos = 0; double hist_mu = -1.0, hist_pen = -1.0;
     Step pending{false, 0.0, 0.0, 0.0, o.kappa_sigma};
     for (int it = 0; it <= o.max_iter; ++it) {
       P1 p1;
@@ -1687,7 +1680,7 @@ struct HsWave {
       intervals_elim(c, c1, cinf);
       wsync();
       MYR_PH(1)
-      adjoint_recur(c, nuT);
+      adjoint_recur(c, s.nuT);
       wsync();
       MYR_PH(2)
       intervals_lambda(c, lam_inf, sum_mult);
@@ -1697,11 +1690,10 @@ struct HsWave {
       wsync();
       MYR_PH(4)
       // inertia correction with retries (only the delta-dependent phases are redone)
-      double delta = lm;
-      if (o.delta_warm && delta_last > o.delta_warm_min) delta = dmax(delta, delta_last / DELTA_WARM_DIV);
+      double delta = s.first_delta(o);
       int nreg = 0;
       for (int tr_ = 0; tr_ < 12; ++tr_) {
-        bool abort_on_reg = (tr_ < 11) && !(delta > 1e8);
+        const bool abort_on_reg = s.rung_aborts(tr_, delta);
         if constexpr (!MFMA_RICCATI && !TRAP) intervals_qm(c, delta);   // the matrix-core sweep forms the midpoint terms itself
         wsync();
         MYR_PH(5)
@@ -1712,25 +1704,15 @@ struct HsWave {
         MYR_PH(6)
         if (nreg == 0) break;
         if (!abort_on_reg) break;
-        if (delta == 0.0) delta = (delta_last > 0.0) ? dmax(1e-8, delta_last / 3.0) : 1e-4;
-        else delta *= (delta_last > 0.0) ? 8.0 : 100.0;
+        delta = s.next_delta(delta);
       }
-      delta_last = (delta > lm) ? delta : 0.0;
-      const int nm = MLAM * c.N * NS + p1.nm;
-      const double sd = nm > 0 ? dmax(1.0, (sum_mult + p1.sm) / nm / 100.0) : 1.0;
-      const double stat = stat_raw / sd, comp = p1.cmax / sd;
-      res.cost = p1.f; res.feas = cinf; res.stat = stat; res.compl_ = comp;
-      if (!(finite_(p1.f) && finite_(cinf) && finite_(stat_raw))) { res.status = 2; res.iters = it; return; }
-      if (cinf <= o.tol_feas && stat <= o.tol_stat && comp <= o.tol_compl) { res.status = 0; res.iters = it; return; }
+      s.close_ladder(delta);
+      const IpKkt k = s.kkt(o, sum_mult + p1.sm, MLAM * c.N * NS + p1.nm, p1.f, stat_raw, p1.cmax, cinf);
+      res.cost = p1.f; res.feas = cinf; res.stat = k.stat; res.compl_ = k.comp;
+      if (!k.finite) { res.status = 2; res.iters = it; return; }
+      if (k.converged) { res.status = 0; res.iters = it; return; }
       if (it == o.max_iter) break;
-      for (int guard = 0; guard < 8; ++guard) {
-        const double cerr = (p1.cmin <= p1.cmax) ? dmax(fabs(p1.cmax - mu), fabs(p1.cmin - mu)) : 0.0;
-        const double emu = dmax(dmax(stat, cinf), cerr / sd);
-        if (emu <= o.kappa_eps * mu && mu > mu_min) {
-          const double nmu = dmax(mu_min, dmin(o.kappa_mu * mu, pow(mu, o.theta_mu)));
-          mu = nmu;
-        } else break;
-      }
+      s.barrier_update(o, k, cinf, p1.cmin, p1.cmax);      // (after the sweep; HsFused::solve has tests and update in front of it)
       // terminal multipliers (every lane, identical)
       typename S::SweepOut so;
 #pragma unroll
@@ -1738,9 +1720,9 @@ struct HsWave {
 #pragma unroll
       for (int i = 0; i < NS; ++i) so.term_pinned[i] = c.term_pinned[i];
       double nu[NS];
-      S::solve_nu(so, mu, nu);
+      S::solve_nu(so, s.mu, nu);
       double th[NC];
-      th[0] = 1.0; th[1] = mu;
+      th[0] = 1.0; th[1] = s.mu;
 #pragma unroll
       for (int i = 0; i < NS; ++i) th[2 + i] = nu[i];
       MYR_PH(7)
@@ -1756,55 +1738,29 @@ struct HsWave {
       wsync();
       MYR_PH(9)
       typename S::FwdOut fo;
-      points_limits(c, o, mu, fo);
+      points_limits(c, o, s.mu, fo);
       MYR_PH(10)
       if (!(finite_(fo.gphi) && finite_(fo.alpha_p))) { res.status = 2; res.iters = it; return; }
-      if (c1 > 0.0) {
-        const double need = fo.gphi / (0.9 * c1);
-        if (pen < need) pen = need + 1.0;
-        if (PEN_RELAX > 0) {         // penalty relaxation (see hs_solver.h)
-          const double want = 2.0 * dmax(need, 0.0) + 1.0;
-          pen_over = (pen > PEN_RELAX_RATIO * want) ? pen_over + 1 : 0;
-          if (pen_over >= PEN_RELAX && pen_cuts < PEN_RELAX_MAX) { pen = want; pen_over = 0; ++pen_cuts; }
-        }
-      }
-      const double Dphi = fo.gphi - pen * c1;
+      const double Dphi = s.penalty_update(fo.gphi, c1);      // (no floor from the multipliers: that is IpLoop's, for shooting)
       // merit value at the current point: objective, barrier sum and l1 defect norm are by-products of the
       // linearisation phases (same formulas as trial()), so no trial at alpha = 0 is spent on it
-      const double f0 = p1.f, bar0 = mu * p1.lg, c10 = c1;
-      const double phi0 = f0 + bar0 + pen * c10;
-      // non-monotone Armijo reference (see hs_solver.h)
-      if (mu != hist_mu || pen != hist_pen) { nhist = 0; hpos = 0; hist_mu = mu; hist_pen = pen; }
-      double phiref = phi0;
-      for (int j = 0; j < nhist; ++j) phiref = dmax(phiref, hist[j]);
-      if (o.nonmono > 0) { hist[hpos % o.nonmono] = phi0; ++hpos; if (nhist < o.nonmono) ++nhist; }
+      const double f0 = p1.f, bar0 = s.mu * p1.lg, c10 = c1;
+      const double phi0 = f0 + bar0 + s.pen * c10;
+      const double phiref = s.merit_reference(o, hist, phi0);
       double a = fo.alpha_p;
       bool ok = false;
       for (int ls = 0; ls < 40; ++ls) {
         double ft, bt, ct;
-        if (trial(c, a, mu, ft, bt, ct)) {
-          const double phit = ft + bt + pen * ct;
-          if (phit <= phiref + 1e-8 * a * Dphi + 1e-13 * fabs(phi0)) { ok = true; break; }
-        }
+        if (trial(c, a, s.mu, ft, bt, ct) && s.accepts(ft + bt + s.pen * ct, phiref, a, Dphi, phi0)) { ok = true; break; }
         a *= 0.5;
       }
-      if (!ok) {
-        if (++stall > 5) { res.status = 3; res.iters = it; return; }
-      } else stall = 0;
+      if (s.stalled(ok)) { res.status = 3; res.iters = it; return; }
       MYR_PH(11)
-      pending.on = true; pending.ap = a; pending.ad = o.dual_follow ? fo.alpha_d * (a / fo.alpha_p) : fo.alpha_d; pending.mu = mu;
+      pending.on = true; pending.ap = a; pending.ad = s.dual_step(o, a, fo.alpha_p, fo.alpha_d); pending.mu = s.mu;
       MYR_PH(12)
 #pragma unroll
-      for (int i = 0; i < NS; ++i) nuT[i] += a * (nu[i] - nuT[i]);
-      if (o.lm_init > 0.0) {     // step-quality feedback -> Levenberg-Marquardt damping (see hs_solver.h)
-        const double ratio = o.lm_abs ? a : a / fo.alpha_p;   // step actually taken, relative to the full Newton step
-        if (ratio <= 0.25) lm = dmin(1e2, dmax(o.lm_init, 4.0 * lm));
-        else if (ratio >= 0.99) { lm *= 0.25; if (lm < 0.1 * o.lm_init) lm = 0.0; }
-      }
-      if (o.recenter > 0) {
-        small_steps = (a < o.recenter_alpha) ? small_steps + 1 : 0;
-        if (small_steps >= o.recenter && mu < o.mu_init) { mu = dmin(o.mu_init, 10.0 * mu); small_steps = 0; }
-      }
+      for (int i = 0; i < NS; ++i) s.follow_nu(i, a, nu[i]);
+      s.after_step(o, a, fo.alpha_p);
       wsync();
     }
     res.status = 1; res.iters = o.max_iter;

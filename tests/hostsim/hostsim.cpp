@@ -181,3 +181,66 @@ extern "C" int hostsim_solve_shoot(int system_id, int I, int cpi, int method, do
   }
   return -1;
 }
+
+// ---- the interior-point policy (myriad_amd/csrc/ip_policy.h) on given scalars: tests/test_hostsim.py restates the rules ----
+static HsSolveOpts policy_opts(double tol_stat, double tol_compl, double mu_init) { return HsSolveOpts{1, 1.0, 1, 1e-8, tol_stat, tol_compl, mu_init}; }
+
+// out[0] = the first rung, out[i] = rung i of the ladder, out[rungs] = delta_last as the ladder closed at rung `rungs - 1` leaves it
+extern "C" void hostsim_policy_ladder(double lm, double delta_last, int delta_warm, double delta_warm_min, int rungs, double* out) {
+  HsSolveOpts o = policy_opts(1e-6, 1e-7, 0.1);
+  o.delta_warm = delta_warm; o.delta_warm_min = delta_warm_min;
+  IpState<4> s;
+  s.start(o);
+  s.lm = lm; s.delta_last = delta_last;
+  out[0] = s.first_delta(o);
+  for (int i = 1; i < rungs; ++i) out[i] = s.next_delta(out[i - 1]);
+  s.close_ladder(out[rungs - 1]);
+  out[rungs] = s.delta_last;
+}
+
+// one barrier update at the given KKT figures; returns the new mu, *mu_min the floor the state derived from the tolerances
+extern "C" double hostsim_policy_barrier(double mu, double tol_stat, double tol_compl, double kappa_mu, double theta_mu, double kappa_eps,
+                                         double sd, double stat, double cinf, double compl_min, double compl_max, double* mu_min) {
+  HsSolveOpts o = policy_opts(tol_stat, tol_compl, mu);
+  o.kappa_mu = kappa_mu; o.theta_mu = theta_mu; o.kappa_eps = kappa_eps;
+  IpState<4> s;
+  s.start(o);
+  IpKkt k{sd, stat, 0.0, true, false};
+  s.barrier_update(o, k, cinf, compl_min, compl_max);
+  *mu_min = s.mu_min;
+  return s.mu;
+}
+
+// the penalty rule over `iters` iterations; out[3 i ..] = penalty, pen_over, pen_cuts after iteration i; slope[i] = the returned merit slope
+extern "C" void hostsim_policy_penalty(int iters, const double* gphi, const double* c1, const double* floor_, double* out, double* slope) {
+  HsSolveOpts o = policy_opts(1e-6, 1e-7, 0.1);
+  IpState<4> s;
+  s.start(o);
+  for (int i = 0; i < iters; ++i) {
+    slope[i] = floor_ ? s.penalty_update(gphi[i], c1[i], floor_[i]) : s.penalty_update(gphi[i], c1[i]);
+    out[3 * i] = s.pen; out[3 * i + 1] = s.pen_over; out[3 * i + 2] = s.pen_cuts;
+  }
+}
+
+// park record of a state with NS = 4: the fields in `in` (12 scalars, 5 of the step, 4 nuT, 8 hist; assigned by NAME here) are saved
+// to sv, loaded into a fresh state and read back, by name again, to `back`.  Returns the record's length.
+extern "C" int hostsim_policy_record(const double* in, double* sv, double* back) {
+  struct Step { bool on; double ap, ad, mu, ksig; };
+  HsSolveOpts o = policy_opts(1e-6, 1e-7, 0.1);
+  IpState<4> s, r;
+  double hist[NMMAX], rhist[NMMAX];
+  s.start(o); r.start(o);
+  s.mu = in[0]; s.pen = in[1]; s.pen_over = (int)in[2]; s.pen_cuts = (int)in[3]; s.stall = (int)in[4]; s.small_steps = (int)in[5];
+  s.delta_last = in[6]; s.lm = in[7]; s.nhist = (int)in[8]; s.hpos = (int)in[9]; s.hist_mu = in[10]; s.hist_pen = in[11];
+  Step p{in[12] != 0.0, in[13], in[14], in[15], in[16]}, q{false, 0.0, 0.0, 0.0, 0.0};
+  for (int i = 0; i < 4; ++i) s.nuT[i] = in[17 + i];
+  for (int i = 0; i < NMMAX; ++i) { hist[i] = in[21 + i]; rhist[i] = 0.0; }
+  s.save(sv, hist, p);
+  r.load(sv, rhist, q);
+  back[0] = r.mu; back[1] = r.pen; back[2] = r.pen_over; back[3] = r.pen_cuts; back[4] = r.stall; back[5] = r.small_steps;
+  back[6] = r.delta_last; back[7] = r.lm; back[8] = r.nhist; back[9] = r.hpos; back[10] = r.hist_mu; back[11] = r.hist_pen;
+  back[12] = q.on ? 1.0 : 0.0; back[13] = q.ap; back[14] = q.ad; back[15] = q.mu; back[16] = q.ksig;
+  for (int i = 0; i < 4; ++i) back[17 + i] = r.nuT[i];
+  for (int i = 0; i < NMMAX; ++i) back[21 + i] = rhist[i];
+  return IpState<4>::RECORD;
+}

@@ -177,3 +177,177 @@ def test_shooting_core_matches_oracle_slsqp(sim, name, I, cpi, method):
   survey = {("SIMPLECASE", 10): -1.3543305221, ("VANDERPOL", 1): 2.8731963348, ("CANCERTREATMENT", 1): 20.5735535185}
   if (name, I) in survey and method == "HEUN":
     assert cost[0] == pytest.approx(survey[(name, I)], rel=1e-4) and cost[0] <= survey[(name, I)] + 1e-9   # SLSQP at default ftol=1e-6 stops slightly short
+
+
+# ---- the interior-point policy (myriad_amd/csrc/ip_policy.h): the rules the lane, wave and fused loops share, restated here ----
+DELTA_WARM_DIV, PEN_RELAX, PEN_RELAX_MAX, PEN_RELAX_RATIO = 6.0, 5, 8, 10.0
+
+
+def _ladder(sim, lm, delta_last, warm, warm_min=3e-3, rungs=8):
+  sim.hostsim_policy_ladder.argtypes = [C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p]
+  out = np.zeros(rungs + 1)
+  sim.hostsim_policy_ladder(lm, delta_last, warm, warm_min, rungs, A(out))
+  return out[:rungs], out[rungs]
+
+
+def _ladder_rule(lm, delta_last, warm, warm_min, rungs):
+  d = lm
+  if warm and delta_last > warm_min:
+    d = max(d, delta_last / DELTA_WARM_DIV)
+  seq = [d]
+  for _ in range(rungs - 1):
+    d = seq[-1]
+    if d == 0.0:
+      seq.append(max(1e-8, delta_last / 3.0) if delta_last > 0.0 else 1e-4)
+    else:
+      seq.append(d * (8.0 if delta_last > 0.0 else 100.0))
+  return np.array(seq), (seq[-1] if seq[-1] > lm else 0.0)
+
+
+def test_policy_ladder_from_a_cold_start(sim):
+  """delta_last = 0: 0, 1e-4, then x 100 per rung (1e10 at rung 7 of this count); the closed ladder remembers its last rung"""
+  seq, last = _ladder(sim, 0.0, 0.0, 1, rungs=9)
+  want = np.array([0.0] + [1e-4 * 100.0 ** i for i in range(8)])
+  np.testing.assert_allclose(seq, want, rtol=4e-16 * 8)      # (eight roundings at most)
+  np.testing.assert_array_equal(seq[:4], [0.0, 1e-4, 1e-4 * 100.0, 1e-4 * 100.0 * 100.0])
+  assert seq[8] > 1e8 and last == seq[8]
+  np.testing.assert_array_equal(seq, _ladder_rule(0.0, 0.0, 1, 3e-3, 9)[0])
+  # a ladder that ends at its first rung (delta = lm) leaves no memory
+  assert _ladder(sim, 0.0, 0.0, 0, rungs=1)[1] == 0.0
+  assert _ladder(sim, 3e-5, 0.0, 0, rungs=1) == (np.array([3e-5]), 0.0)
+
+
+@pytest.mark.parametrize("warm", [0, 1])
+@pytest.mark.parametrize("lm", [0.0, 3e-5, 0.2])
+def test_policy_ladder_after_a_correction(sim, warm, lm):
+  """delta_last = 0.3: without delta_warm the first rung is the Levenberg-Marquardt floor and a zero rung is followed by
+  delta_last / 3; with it the first rung is max(lm, delta_last / 6); every further rung x 8"""
+  seq, last = _ladder(sim, lm, 0.3, warm, rungs=6)
+  want, want_last = _ladder_rule(lm, 0.3, warm, 3e-3, 6)
+  np.testing.assert_array_equal(seq, want)
+  assert last == want_last
+  assert seq[0] == (max(lm, 0.3 / 6.0) if warm else lm)
+  assert seq[1] == (0.3 / 3.0 if seq[0] == 0.0 else seq[0] * 8.0)
+  # below delta_warm_min the warm start does not apply
+  assert _ladder(sim, lm, 1e-3, 1, rungs=1)[0][0] == lm
+
+
+def _barrier(sim, mu, tol_stat=1e-6, tol_compl=1e-7, kmu=0.2, tmu=1.5, keps=10.0, sd=1.0, stat=0.0, cinf=0.0, cmin=1.0, cmax=0.0):
+  sim.hostsim_policy_barrier.argtypes = [C.c_double] * 11 + [C.c_void_p]
+  sim.hostsim_policy_barrier.restype = C.c_double
+  mm = np.zeros(1)
+  return sim.hostsim_policy_barrier(mu, tol_stat, tol_compl, kmu, tmu, keps, sd, stat, cinf, cmin, cmax, A(mm)), mm[0]
+
+
+def _barrier_rule(mu, mu_min, kmu, tmu, keps, sd, stat, cinf, cmin, cmax):
+  import math
+  for _ in range(8):
+    cerr = max(abs(cmax - mu), abs(cmin - mu)) if cmin <= cmax else 0.0
+    emu = max(max(stat, cinf), cerr / sd)
+    if emu <= keps * mu and mu > mu_min:
+      mu = max(mu_min, min(kmu * mu, math.pow(mu, tmu)))
+    else:
+      break
+  return mu
+
+
+def test_policy_barrier_update(sim):
+  """the chain of reductions mu <- max(mu_min, min(kappa_mu mu, mu^theta_mu)) while the barrier problem's error is within
+  kappa_eps mu: down to mu_min = min(tol_compl, tol_stat) / 10, at most 8 per update"""
+  tol = 2e-15      # pow() and a handful of roundings
+  # no error at all (no bounded variable: compl_min > compl_max): the chain from 0.1 reaches the floor in 6 reductions
+  mu, mu_min = _barrier(sim, 0.1)
+  assert mu_min == min(1e-7, 1e-6) * 0.1 and mu == mu_min
+  assert _barrier_rule(0.1, mu_min, 0.2, 1.5, 10.0, 1.0, 0.0, 0.0, 1.0, 0.0) == mu_min
+  # the guard: kappa_mu = 0.9, theta_mu = 1 -> every reduction is x 0.9, and there are exactly 8 of them
+  mu, mu_min = _barrier(sim, 0.1, kmu=0.9, tmu=1.0)
+  np.testing.assert_allclose(mu, 0.1 * 0.9 ** 8, rtol=tol)
+  np.testing.assert_allclose(mu, _barrier_rule(0.1, mu_min, 0.9, 1.0, 10.0, 1.0, 0.0, 0.0, 1.0, 0.0), rtol=tol)
+  # the chain stops where the error exceeds kappa_eps mu: stationarity 3e-3 allows 0.1 -> 0.02 -> 0.0028.. -> 1.5e-4 and no further
+  for kw in (dict(stat=3e-3), dict(cinf=3e-3), dict(stat=1e-9, cmin=0.0995, cmax=0.1008, sd=2.0), dict(stat=20.0)):
+    mu, mu_min = _barrier(sim, 0.1, **kw)
+    a = dict(sd=1.0, stat=0.0, cinf=0.0, cmin=1.0, cmax=0.0); a.update(kw)
+    np.testing.assert_allclose(mu, _barrier_rule(0.1, mu_min, 0.2, 1.5, 10.0, a["sd"], a["stat"], a["cinf"], a["cmin"], a["cmax"]), rtol=tol)
+  np.testing.assert_allclose(_barrier(sim, 0.1, stat=3e-3)[0], ((0.1 * 0.2) ** 1.5) ** 1.5, rtol=tol)
+  assert _barrier(sim, 0.1, stat=20.0)[0] == 0.1
+  # at the floor nothing moves
+  assert _barrier(sim, 1e-8)[0] == 1e-8
+
+
+def _penalty(sim, gphi, c1, floor_=None):
+  sim.hostsim_policy_penalty.argtypes = [C.c_int] + [C.c_void_p] * 5
+  n = len(gphi)
+  g = np.asarray(gphi, float); c = np.asarray(c1, float); out = np.zeros(3 * n); slope = np.zeros(n)
+  fl = None if floor_ is None else np.asarray(floor_, float)
+  sim.hostsim_policy_penalty(n, A(g), A(c), None if fl is None else A(fl), A(out), A(slope))
+  return out.reshape(n, 3), slope
+
+
+def _penalty_rule(gphi, c1, floor_=None):
+  pen, over, cuts, rows, slope = 1.0, 0, 0, [], []
+  for i in range(len(gphi)):
+    if c1[i] > 0.0:
+      need = gphi[i] / (0.9 * c1[i])
+      if pen < need:
+        pen = need + 1.0
+      want = max(2.0 * max(need, 0.0) + 1.0, 0.0 if floor_ is None else floor_[i])
+      over = over + 1 if pen > PEN_RELAX_RATIO * want else 0
+      if over >= PEN_RELAX and cuts < PEN_RELAX_MAX:
+        pen, over, cuts = want, 0, cuts + 1
+    rows.append((pen, over, cuts)); slope.append(gphi[i] - pen * c1[i])
+  return np.array(rows), np.array(slope)
+
+
+@pytest.mark.parametrize("floor_", [None, 0.0, 7.0, 400.0])
+def test_policy_penalty_rule(sim, floor_):
+  """the l1 penalty rises to need + 1, is reset to max(2 max(need, 0) + 1, floor) after PEN_RELAX consecutive iterations above
+  PEN_RELAX_RATIO times that, at most PEN_RELAX_MAX times per solve; c1 = 0 leaves everything alone"""
+  n = 80
+  # need = 0.5 everywhere but for a spike every 6 iterations up to iteration 54 (need = 1000, 2000, ...); iteration 5 has c1 = 0
+  gphi = np.full(n, 0.9 * 0.5); c1 = np.ones(n)
+  gphi[0:60:6] = 0.9 * 1000.0 * (1.0 + np.arange(10))
+  c1[5] = 0.0
+  fl = None if floor_ is None else np.full(n, floor_)
+  got, gslope = _penalty(sim, gphi, c1, fl)
+  want, wslope = _penalty_rule(gphi, c1, fl)
+  np.testing.assert_array_equal(got, want)
+  np.testing.assert_array_equal(gslope, wslope)
+  cut = np.flatnonzero(np.diff(got[:, 2]) > 0) + 1
+  assert got[0, 0] == 1001.0 and got[6, 0] == 2001.0
+  assert tuple(got[5]) == tuple(got[4])             # c1 = 0: penalty and counters untouched
+  if floor_ == 400.0:
+    # 10 x 400 is first exceeded by the spike of iteration 18 (penalty 4001): cuts at 23, 29, ..., 59, to the floor
+    assert got[:19, 1].max() == 0
+    np.testing.assert_array_equal(cut, np.arange(23, 60, 6))
+    np.testing.assert_array_equal(got[cut, 0], 400.0)
+  else:
+    # iterations 1-4 count to 4, iteration 5 does not count, the spike of iteration 6 resets: no cut yet.  From then on five
+    # iterations over -> a cut at 11, 17, ..., 53: eight of them, and no ninth after the spike of iteration 54
+    assert tuple(got[4]) == (1001.0, 4, 0)
+    np.testing.assert_array_equal(cut, np.arange(11, 54, 6))
+    assert len(cut) == PEN_RELAX_MAX
+    np.testing.assert_array_equal(got[cut, 0], max(2.0 * 0.5 + 1.0, floor_ or 0.0))
+    assert tuple(got[-1]) == (10001.0, 25, PEN_RELAX_MAX)
+
+
+def test_policy_park_record_round_trip(sim):
+  """save / load of the state, its history and the pending step: every field comes back, at the documented offsets
+  (0-11 mu, pen, pen_over, pen_cuts, stall, small_steps, delta_last, lm, nhist, hpos, hist_mu, hist_pen; 12-16 the step:
+  on, ap, ad, mu, ksig; 17 nuT[NS]; 17 + NS hist[8]; NS = 4 here)"""
+  sim.hostsim_policy_record.argtypes = [C.c_void_p] * 3
+  NS = 4
+  fields = np.array([3.25e-3, 41.5, 3, 2, 4, 1, 0.375, 1.2e-4, 3, 7, 3.25e-3, 41.5,       # the twelve scalars
+                     1.0, 0.625, 0.5, 6.5e-3, 1e10,                                       # the pending step
+                     -1.5, 2.5, 0.0, 1e-300,                                              # nuT
+                     10.0, -11.0, 12.5, 0.0, 1e300, -0.0, 17.0, 18.0])                    # hist
+  assert len(np.unique(fields[[0, 1, 6, 7, 13, 14, 15, 16]])) == 8
+  sv = np.full(48, np.nan); back = np.full(fields.size, np.nan)
+  n = sim.hostsim_policy_record(A(fields), A(sv), A(back))
+  assert n == 17 + NS + 8 == fields.size
+  np.testing.assert_array_equal(sv[:n], fields)
+  assert np.isnan(sv[n:]).all()                     # nothing written behind the record
+  np.testing.assert_array_equal(back, fields)
+  # a step that is off
+  fields[12] = 0.0
+  sim.hostsim_policy_record(A(fields), A(sv), A(back))
+  assert sv[12] == 0.0 and back[12] == 0.0

@@ -5,13 +5,14 @@ Every translation unit of the library (the job list of __graft_entry__.build()) 
 plus --cuda-device-only -S.  The only text that depends on where a tree lies is the __hip_cuid_<hash> symbol: it is replaced by a
 fixed token.  Per job the tool prints `identical`, or the functions whose text differs.
 
-  python tools/dev/cmp_device_code.py TREE_A TREE_B [-DNAME=V ...] [--only REGEX] [--normalise] [--listings DIR] [--reuse] [-j N]
+  python tools/dev/cmp_device_code.py TREE_A TREE_B [-DNAME=V ...] [--only REGEX] [--normalise [--max-ranges N]] [--listings DIR] [--reuse] [-j N]
 
   -DNAME=V      an extra define for both compiles (e.g. the fallback form: -DMYR_FUSED_SPEC=0 -DMYR_SWEEP_CALL_W=0)
   --only        jobs whose name matches (e.g. 'SysCARTPOLE.p[13]')
   --normalise   compare instruction sequences: comments and directives dropped, register names and .LBB labels replaced.  Per
                 differing function: the index ranges that differ, the indices of the first and the last v_mfma, and whether the
-                sequence between those two is unchanged (the stage code of a sweep lies there)
+                sequence between those two is unchanged (the stage code of a sweep lies there); --max-ranges N prints the first N ranges
+                and the number of the others (a re-allocated kernel has thousands)
   --listings    where the listings go (DIR/a, DIR/b; default build/cmp); --reuse keeps a listing that is already there
 """
 import argparse
@@ -72,7 +73,7 @@ def mfma_span(x):
   return (k[0], k[-1]) if k else (0, -1)
 
 
-def compare(name, ta, tb, normalise):
+def compare(name, ta, tb, normalise, max_ranges=0):
   """report lines of one job"""
   if ta == tb:
     return [f"{name}: identical"]
@@ -92,7 +93,8 @@ def compare(name, ta, tb, normalise):
     same = x[fa:la + 1] == y[fb:lb + 1]
     rep.append(f"  differs: {k[:150]}\n    instructions {len(x)} -> {len(y)}; v_mfma first / last {fa} / {la} -> {fb} / {lb}; "
                f"first to last v_mfma {'unchanged' if same else 'CHANGED'}\n    ranges: " +
-               ", ".join(f"a[{o[1]}:{o[2]}] b[{o[3]}:{o[4]}]" for o in ops))
+               ", ".join(f"a[{o[1]}:{o[2]}] b[{o[3]}:{o[4]}]" for o in (ops[:max_ranges] if max_ranges else ops)) +
+               (f", ... {len(ops) - max_ranges} more, the last a[{ops[-1][1]}:{ops[-1][2]}] b[{ops[-1][3]}:{ops[-1][4]}]" if max_ranges and len(ops) > max_ranges else ""))
   if not rep:
     return [f"{name}: identical" + (" after normalising" if normalise else " in every function (text outside the functions differs)")]
   return [f"{name}: {len(rep)} function(s) differ"] + rep
@@ -104,6 +106,7 @@ def main():
   ap.add_argument("-D", dest="defs", action="append", default=[])
   ap.add_argument("--only", default=".")
   ap.add_argument("--normalise", action="store_true")
+  ap.add_argument("--max-ranges", type=int, default=0)
   ap.add_argument("--listings", default=os.path.join(ROOT, "build", "cmp"))
   ap.add_argument("--reuse", action="store_true")
   ap.add_argument("-j", type=int, default=min(16, os.cpu_count() or 4))
@@ -118,7 +121,7 @@ def main():
   print(f"# {len(jobs)} jobs{' ' + ' '.join(extra) if extra else ''}{', normalised' if args.normalise else ''}")
   differing = 0
   for i, (name, _) in enumerate(jobs):
-    rep = compare(name + "".join(" " + e for e in extra), texts[2 * i], texts[2 * i + 1], args.normalise)
+    rep = compare(name + "".join(" " + e for e in extra), texts[2 * i], texts[2 * i + 1], args.normalise, args.max_ranges)
     differing += len(rep) > 1
     print("\n".join(rep), flush=True)
   print(f"# {len(jobs) - differing} of {len(jobs)} jobs identical")
