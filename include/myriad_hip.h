@@ -79,7 +79,7 @@ enum { MYR_STATUS_CONVERGED = 0, MYR_STATUS_MAXITER = 1, MYR_STATUS_NAN = 2, MYR
           whose elastic twin converges with a slack that does not vanish as its penalty grows */
        MYR_STATUS_INFEASIBLE = 4 };
 /* kernel ids for myr_kernel_time */
-enum { MYR_K_EVAL = 0, MYR_K_SOLVE = 1, MYR_K_ROLLOUT = 2, MYR_K_RESID = 3, MYR_K_PROD = 4, MYR_K_FBSM = 5, MYR_K_COUNT = 6 };
+enum { MYR_K_EVAL = 0, MYR_K_SOLVE = 1, MYR_K_ROLLOUT = 2, MYR_K_RESID = 3, MYR_K_PROD = 4, MYR_K_FBSM = 5, MYR_K_FIT = 6, MYR_K_COUNT = 7 };
 /* error codes */
 enum { MYR_OK = 0, MYR_E_ARG = -1, MYR_E_UNSUPPORTED = -2, MYR_E_HIP = -3, MYR_E_CAPACITY = -4 };
 
@@ -292,6 +292,24 @@ int myr_exgd(myr_handle h, int32_t B, double* z, double* lam, const double* lb, 
 int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, const double* adj_T, const double* params,
              int32_t params_stride, const double* clip_lo, const double* clip_hi, double bang, double delta,
              int32_t max_sweeps, double* xs, double* us, double* adjs, int32_t* sweeps, int32_t mem);
+
+/*
+ * Trajectory-matching loss and its gradient in the model parameters (experiments/mle_sysid.py:89-136,
+ * neural_ode/node_training.py:31-61): for each of B recorded trajectories, integrate its controls from its first recorded state with the
+ * handle's integration_method and h = T / num_steps (the steps of myr_rollout: utils.py:80-131, control rows beyond u_rows clamp to the
+ * last one), and take
+ *   loss[b] = sum_{t=0..num_steps} wt[t] * sum_i (xh_b[t][i] - xs_obs_b[t][i])^2,      grad[b][k] = d loss[b] / d params[k]
+ * by one forward rollout and one reverse sweep on the device.
+ *   xs_obs [B][num_steps+1][ns]; us [B][u_rows][nu]; wt [num_steps+1] or NULL (= 1);
+ *   params as in myr_rollout (NULL = the system's defaults; NODE: required, params_stride 0 only); loss [B] (may be NULL);
+ *   grad [B][np] if grad_stride == np, [np] = sum over the batch if grad_stride == 0.
+ * The sum over the batch runs in a fixed order without atomics: the same bits on every call, for MYR_MEM_HOST and MYR_MEM_DEVICE alike.
+ * A parameter that enters the running cost only has gradient 0.  MYR_E_UNSUPPORTED: INVASIVEPLANT, the elastic twins (fit the system
+ * itself), per-instance NODE weights; MYR_E_ARG: a grad_stride or params_stride other than 0 and np, bad sizes.
+ */
+int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                 const double* wt, const double* params, int32_t params_stride,
+                 double* loss, double* grad, int32_t grad_stride, int32_t mem);
 
 /* Average device time (HIP events on the handle's stream) of the launches of one kernel since the last reset. */
 int myr_kernel_time(myr_handle h, int32_t kernel_id, double* avg_ms, int32_t* launches);

@@ -24,13 +24,13 @@ SYS_IDS = {"CARTPOLE": 0, "VANDERPOL": 1, "CANCERTREATMENT": 2, "SIMPLECASE": 3,
 TR_IDS = {"HERMITE_SIMPSON": 0, "TRAPEZOIDAL": 1, "SHOOTING": 2}
 INT_IDS = {"EULER": 0, "HEUN": 1, "MIDPOINT": 2, "RK4": 3}
 MEM_HOST, MEM_DEVICE = 0, 1
-K_EVAL, K_SOLVE, K_ROLLOUT, K_RESID, K_PROD, K_FBSM = 0, 1, 2, 3, 4, 5
+K_EVAL, K_SOLVE, K_ROLLOUT, K_RESID, K_PROD, K_FBSM, K_FIT = 0, 1, 2, 3, 4, 5, 6
 STATUS_NAMES = {0: "CONVERGED", 1: "MAXITER", 2: "NAN", 3: "STALLED", 4: "INFEASIBLE"}
 STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr_solve (csrc/myriad_hip.hip: solve_restored), never by a kernel
 
 EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
            "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
-           "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan"]
+           "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad"]
 
 
 class ProblemDesc(C.Structure):
@@ -98,6 +98,8 @@ def load() -> C.CDLL:
   lib.myr_solve_plan.restype = C.c_int
   lib.myr_rollout.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
   lib.myr_rollout.restype = C.c_int
+  lib.myr_fit_grad.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
+  lib.myr_fit_grad.restype = C.c_int
   lib.myr_set_var_scale.argtypes = [vp, dp]
   lib.myr_set_var_scale.restype = C.c_int
   lib.myr_vjp.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32]
@@ -316,6 +318,34 @@ class Engine:
     _chk(self.lib.myr_rollout(self._h, B, int(num_steps), int(us.shape[1]), _addr(x0), _addr(us), _addr(p), ps,
                               _addr(xs), _addr(cost), MEM_HOST), "myr_rollout")
     return xs, cost
+
+  def fit_grad(self, xs_obs, us, params=None, wt=None, reduce=False):
+    """myr_fit_grad: trajectory-matching loss and its gradient in the model parameters.  xs_obs [B,S+1,ns] (recorded states; the
+    rollout starts from xs_obs[:,0]), us [B,u_rows,nu], params [np] (shared) or [B,np] (None: the system's defaults), wt [S+1]
+    (None: 1).  Returns {"loss" [B], "grad" [B,np], or [np] = the sum over the batch with reduce=True}."""
+    xs_obs = _f64(xs_obs)
+    us = _f64(us)
+    if xs_obs.ndim == 2:
+      xs_obs = xs_obs[None]
+    if us.ndim == 2:
+      us = us[None]
+    B, S = xs_obs.shape[0], xs_obs.shape[1] - 1
+    if xs_obs.ndim != 3 or xs_obs.shape[2] != self.ns or S < 1:
+      raise ValueError(f"xs_obs must be [B,S+1,{self.ns}] with S >= 1")
+    if us.ndim != 3 or us.shape[0] != B or us.shape[2] != self.nu:
+      raise ValueError(f"us must be [B,u_rows,{self.nu}]")
+    p, ps = self._params(params, B)
+    w = None if wt is None else _f64(wt, (S + 1,))
+    loss = np.empty(B)
+    grad = np.empty(self.np) if reduce else np.empty((B, self.np))
+    _chk(self.lib.myr_fit_grad(self._h, B, S, int(us.shape[1]), _addr(xs_obs), _addr(us), _addr(w), _addr(p), ps, _addr(loss),
+                               _addr(grad), 0 if reduce else self.np, MEM_HOST), "myr_fit_grad")
+    return {"loss": loss, "grad": grad}
+
+  def fit_grad_device(self, B, num_steps, u_rows, xs_obs, us, grad, grad_stride, params=None, params_stride=0, wt=None, loss=None):
+    """Zero-copy variant of fit_grad: every array is a device tensor on this handle's device."""
+    _chk(self.lib.myr_fit_grad(self._h, int(B), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), _addr(wt), _addr(params),
+                               int(params_stride), _addr(loss), _addr(grad), int(grad_stride), MEM_DEVICE), "myr_fit_grad")
 
   # ---- Lagrangian products / extragradient (collocation transcriptions) ------------------------
   def _batch2(self, a, width, name):

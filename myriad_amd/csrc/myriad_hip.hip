@@ -10,6 +10,7 @@
 #include <chrono>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/myriad_hip.h"
@@ -23,6 +24,7 @@
 #include "os_solver.h"
 #include "shoot_eval.h"
 #include "rollout.h"
+#include "fit.h"
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
@@ -982,12 +984,34 @@ int rollout_for_system(myr_handle h, int B, int num_steps, int u_rows, const dou
   return MYR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// trajectory-matching loss and its parameter gradient (fit.h: fit_lane_kernel, node_fit_kernel)
+// ------------------------------------------------------------------------------------------------
+// xh: [num_steps+1][NS][Bp] state scratch; loss [B] or null; grad [B][NP] rows
+template <class Sys>
+int fit_for_system(myr_handle h, int B, long Bp, int num_steps, int u_rows, const double* xs_obs, const double* us, const double* wt,
+                   const double* params, int pstride, double* xh, double* loss, double* grad) {
+  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // shared weights only (myr_fit_grad has checked): one wavefront per trajectory
+    (void)pstride;
+    hipLaunchKernelGGL(node_fit_kernel<NodeFit>, dim3((unsigned)((B + NodeFit::WPB - 1) / NodeFit::WPB)), dim3(64 * NodeFit::WPB), 0, h->stream, B, Bp,
+                       (int)h->d.integration_method, num_steps, h->d.T / num_steps, u_rows, xs_obs, us, wt, params, xh, loss, grad);
+    return MYR_OK;
+  } else if constexpr (!SysDp<Sys>::SUPPORTED) {
+    return fail(MYR_E_UNSUPPORTED, std::string("myr_fit_grad: no parameter derivatives are generated for ") + Sys::NAME);
+  } else {
+    hipLaunchKernelGGL(fit_lane_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, Bp, (int)h->d.integration_method, num_steps,
+                       h->d.T / num_steps, u_rows, xs_obs, us, wt, params, pstride, xh, loss, grad);
+    return MYR_OK;
+  }
+}
+
 // ---- per-system entry points: explicit instantiation (system objects) / extern declaration (main object) -----------------
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
   LINK template int eval_for_system<S>(myr_handle, int, const double*, const double*, int, double*, double*, double*, double*);   \
   LINK template int products_for_system<S>(myr_handle, const ProdArgs&);                                                          \
   LINK template int solve_for_system<S>(myr_handle, const SolveCall&);                                                            \
   LINK template int rollout_for_system<S>(myr_handle, int, int, int, const double*, const double*, const double*, int, double*, double*); \
+  LINK template int fit_for_system<S>(myr_handle, int, long, int, int, const double*, const double*, const double*, const double*, int, double*, double*, double*); \
   LINK template int launch_fbsm<S>(myr_handle, int, long, int, const double*, const double*, const double*, int, const VarScale&,  \
                                    const VarScale&, double, double, int, double*, double*, double*, int32_t*);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
@@ -1009,6 +1033,7 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, 
   template int eval_for_system<S>(myr_handle, int, const double*, const double*, int, double*, double*, double*, double*);         \
   template int products_for_system<S>(myr_handle, const ProdArgs&);                                                                \
   template int rollout_for_system<S>(myr_handle, int, int, int, const double*, const double*, const double*, int, double*, double*); \
+  template int fit_for_system<S>(myr_handle, int, long, int, int, const double*, const double*, const double*, const double*, int, double*, double*, double*); \
   template int launch_fbsm<S>(myr_handle, int, long, int, const double*, const double*, const double*, int, const VarScale&,        \
                               const VarScale&, double, double, int, double*, double*, double*, int32_t*);
 MYR_SYSTEM_ENTRY_POINTS_REST(myriad::MYR_TU_SYSTEM)
@@ -1978,6 +2003,103 @@ extern "C" int myr_rollout(myr_handle h, int32_t B, int32_t num_steps, int32_t u
   if (rc) return rc;
   if (nxs) HIPCHK(hipMemcpyAsync(xs, dxs, nxs * 8, hipMemcpyDeviceToHost, h->stream));
   if (nc) HIPCHK(hipMemcpyAsync(cost, dc, nc * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return MYR_OK;
+}
+
+// Sum of the per-trajectory gradient rows in a fixed order: block k owns entry k; thread t adds rows t, t + 256, ... in ascending order, then the
+// 256 partial sums meet in a fixed tree.  No atomics: the same bits on every call.  (Neighbouring threads read rows np apart -- not coalesced: the
+// kernel reads B * np doubles once, and the rows keep the layout the caller gets with grad_stride == np.)
+static __global__ __launch_bounds__(256) void fit_reduce_kernel(int B, int np, const double* __restrict__ rows, double* __restrict__ out) {
+  __shared__ double part[256];
+  const int k = blockIdx.x, t = threadIdx.x;
+  double a = 0.0;
+  for (long b = t; b < B; b += 256) a += rows[b * np + k];
+  part[t] = a;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) part[t] += part[t + w];
+    __syncthreads();
+  }
+  if (t == 0) out[k] = part[0];
+}
+
+static bool fit_supported(int id) {
+  switch (id) {
+#define X(N) case MYR_SYS_##N: return SysDp<Sys##N>::SUPPORTED;
+    MYR_CLOSED_FORM_SYSTEMS(X)
+#undef X
+    case MYR_SYS_NODE_CARTPOLE: return true;
+  }
+  return false;
+}
+static bool sys_known(int id) { SysInfo si; return sys_info(id, &si); }
+
+// device pointers throughout; grad: [B][np] rows (grad_stride == np) or the [np] sum over the batch (grad_stride == 0, rows in sbuf)
+static int dispatch_fit(myr_handle h, int B, int num_steps, int u_rows, const double* xs_obs, const double* us, const double* wt,
+                        const double* params, int pstride, double* loss, double* grad, int grad_stride) {
+  const myr_dims& dm = h->dims;
+  long Bp = ((long)B + 63) / 64 * 64;
+  if (((Bp / 64) & 1) == 0) Bp += 64;                 // odd multiple of 64 lanes: rotate the state rows over the HBM channels
+  const size_t nxh = (size_t)(num_steps + 1) * dm.ns * (size_t)Bp, nrows = grad_stride ? 0 : (size_t)B * dm.np;
+  if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, (al(nxh) + al(nrows)) * 8)) return rc;
+  double* xh = (double*)h->sbuf;
+  double* rows = grad_stride ? grad : xh + al(nxh);
+  if (!fit_supported(h->d.system_id))                  // refused before the timer starts: begin and end stay paired
+    return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
+                                     : no_such_path(h, "myr_fit_grad");
+  int rc = timed_begin(h, MYR_K_FIT);
+  if (rc) return rc;
+  switch (h->d.system_id) {
+#define X(N) case MYR_SYS_##N: rc = fit_for_system<Sys##N>(h, B, Bp, num_steps, u_rows, xs_obs, us, wt, params, pstride, xh, loss, rows); break;
+    MYR_CLOSED_FORM_SYSTEMS(X)
+#undef X
+    case MYR_SYS_NODE_CARTPOLE: rc = fit_for_system<SysNODE_CARTPOLE>(h, B, Bp, num_steps, u_rows, xs_obs, us, wt, params, pstride, xh, loss, rows); break;
+  }
+  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, B, (int)dm.np, rows, grad);
+  const int rc_end = timed_end(h, MYR_K_FIT);          // on every path
+  return rc ? rc : rc_end;
+}
+
+extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                            const double* wt, const double* params, int32_t params_stride, double* loss, double* grad,
+                            int32_t grad_stride, int32_t mem) {
+  if (!h || !xs_obs || !us || !grad) return fail(MYR_E_ARG, "myr_fit_grad: null handle, xs_obs, us or grad");
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, "myr_fit_grad");
+  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
+  if (B < 0 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_grad: bad sizes");
+  if (grad_stride != 0 && grad_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_fit_grad: grad_stride must be 0 (one row: the sum over the batch) or np (a row per trajectory)");
+  if (params && params_stride != 0 && params_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_fit_grad: params_stride must be 0 (shared) or np");
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE) {
+    if (!params) return fail(MYR_E_ARG, "myr_fit_grad: a NODE system needs its weights in `params`");
+    if (params_stride != 0) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: a NODE system takes one shared set of weights (params_stride 0)");
+  }
+  if (mem != MYR_MEM_DEVICE && mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_fit_grad: bad mem kind");
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  if (mem == MYR_MEM_DEVICE) return dispatch_fit(h, B, num_steps, u_rows, xs_obs, us, wt, params, params_stride, loss, grad, grad_stride);
+  const size_t nxs = (size_t)B * (num_steps + 1) * dm.ns, nus = (size_t)B * u_rows * dm.nu, nwt = wt ? (size_t)num_steps + 1 : 0;
+  const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
+  const size_t nl = loss ? (size_t)B : 0, ng = grad_stride ? (size_t)B * dm.np : (size_t)dm.np;
+  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nxs) + al(nus) + al(nwt) + al(npar) + al(nl) + al(ng)) * 8);
+  if (rc) return rc;
+  double* dxs = (double*)h->dbuf;
+  double* dus = dxs + al(nxs);
+  double* dwt = dus + al(nus);
+  double* dp = dwt + al(nwt);
+  double* dl = dp + al(npar);
+  double* dg = dl + al(nl);
+  HIPCHK(hipMemcpyAsync(dxs, xs_obs, nxs * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dus, us, nus * 8, hipMemcpyHostToDevice, h->stream));
+  if (nwt) HIPCHK(hipMemcpyAsync(dwt, wt, nwt * 8, hipMemcpyHostToDevice, h->stream));
+  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
+  rc = dispatch_fit(h, B, num_steps, u_rows, dxs, dus, nwt ? dwt : nullptr, npar ? dp : nullptr, params_stride, nl ? dl : nullptr, dg, grad_stride);
+  if (rc) return rc;
+  if (nl) HIPCHK(hipMemcpyAsync(loss, dl, nl * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(grad, dg, ng * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return MYR_OK;
 }

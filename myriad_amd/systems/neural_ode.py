@@ -15,6 +15,27 @@ from myriad_amd.systems import FiniteHorizonControlSystem
 _DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data")
 
 
+_LAYERS = ("linear", "linear_1", "linear_2")
+
+
+def flat_from_mapping(params) -> np.ndarray:
+  """Haiku mapping {'linear': {'w' (in, out), 'b'}, 'linear_1', 'linear_2'} -> the device vector w1|b1|w2|b2|w3|b3 (csrc/node_system.h)."""
+  return np.concatenate([np.concatenate([np.asarray(params[k]["w"], dtype=np.float64).ravel(),
+                                         np.asarray(params[k]["b"], dtype=np.float64).ravel()]) for k in _LAYERS])
+
+
+def mapping_from_flat(flat, sizes=(5, 64, 64, 4)) -> dict:
+  """The inverse of flat_from_mapping for layer widths `sizes` = (inputs, hidden, hidden, outputs): also the layout of a gradient row."""
+  flat = np.asarray(flat, dtype=np.float64)
+  if flat.shape != (sum(a * b + b for a, b in zip(sizes[:-1], sizes[1:])),):
+    raise ValueError(f"expected {sum(a * b + b for a, b in zip(sizes[:-1], sizes[1:]))} entries, got {flat.shape}")
+  out, o = {}, 0
+  for k, a, b in zip(_LAYERS, sizes[:-1], sizes[1:]):
+    out[k] = {"w": flat[o:o + a * b].reshape(a, b).copy(), "b": flat[o + a * b:o + a * b + b].copy()}
+    o += a * b + b
+  return out
+
+
 class NeuralODE:
   """The part of create_node.NeuralODE the planning path uses: .params (Haiku layout) and .net.apply."""
 
@@ -67,6 +88,4 @@ class NodeSystem(FiniteHorizonControlSystem):
 
   def params_from_mapping(self, params) -> np.ndarray:
     """Flatten the Haiku mapping into the device order w1|b1|w2|b2|w3|b3 (csrc/node_system.h)."""
-    ks = ("linear", "linear_1", "linear_2")
-    return np.concatenate([np.concatenate([np.asarray(params[k]["w"], dtype=np.float64).ravel(),
-                                           np.asarray(params[k]["b"], dtype=np.float64).ravel()]) for k in ks])
+    return flat_from_mapping(params)

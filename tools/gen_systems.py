@@ -8,12 +8,16 @@ The symbolic definitions below RESTATE the reference's system definitions (citat
 to /root/reference/); derivatives and common-subexpression elimination are done by sympy here, at
 development time.  The generated header is committed; this script is only re-run when a system
 is added.  Run:  python tools/gen_systems.py
+
+`python tools/gen_systems.py --dp` writes myriad_amd/csrc/systems_dp_gen.h instead: the parameter derivatives of the
+dynamics (SysDp<Sys>::vjp_p, the reverse sweep of csrc/fit.h), from the same definitions.  systems_gen.h is left alone.
 """
 import os
 import sympy as sp
 from sympy.printing.c import C99CodePrinter
 
 OUT = os.path.join(os.path.dirname(__file__), "..", "myriad_amd", "csrc", "systems_gen.h")
+OUT_DP = os.path.join(os.path.dirname(__file__), "..", "myriad_amd", "csrc", "systems_dp_gen.h")
 
 
 class inboxf(sp.Function):
@@ -426,6 +430,56 @@ def gen_system(S):
   return "\n".join(o)
 
 
+def gen_system_dp(S):
+  """SysDp<Sys>::vjp_p: gp[k] = sum_i v[i] d f_i / d p_k of the field gen_system() emits (same substitution of the variable scales)."""
+  name, x, u, p = S["name"], list(S["x"]), list(S["u"]), list(S["p"])
+  ns, nu, npar = len(x), len(u), len(p)
+  w = x + u
+  nw = ns + nu
+  sc = list(sp.symbols(f"sc0:{nw}", positive=True))
+  isc = list(sp.symbols(f"isc0:{ns}", positive=True))
+  smap = {v: sc[i] * v for i, v in enumerate(w)}
+  f = [sp.sympify(e).subs(smap, simultaneous=True) * isc[i] for i, e in enumerate(S["f"])]
+  v = sp.symbols(f"v0:{ns}", real=True)
+  gp = [sum(v[i] * sp.diff(f[i], p[k]) for i in range(ns)) for k in range(npar)]   # a cost-only parameter: the structural zero
+  o = []
+  o.append(f"// ===== {name} (id {S['id']}): np={npar} ({', '.join(S['pnames'])}) =====")
+  o.append(f"template <> struct SysDp<Sys{name}> {{")
+  o.append("  static constexpr bool SUPPORTED = true;")
+  o.append("  MYR_HD static inline void vjp_p(const double* x, const double* u, const double* p, const double* v, double* gp) {")
+  un = []
+  for nm, syms, off in (("x", x, 0), ("u", u, 0), ("p", p, 0), ("p", sc, npar), ("p", isc, npar + nw), ("v", v, 0)):
+    for i, sy in enumerate(syms):
+      un.append(f"    const double {sy} = {nm}[{off + i}];")
+  o.append("\n".join(un))
+  o.append("\n".join(f"    (void){sy};" for sy in (x + u + p + sc + isc + list(v))))
+  o.append(emit_block([(f"gp[{k}]", gp[k]) for k in range(npar)], "    "))
+  o.append("  }")
+  o.append("};")
+  return "\n".join(o)
+
+
+def main_dp():
+  parts = ["// GENERATED by tools/gen_systems.py --dp (sympy) -- do not edit by hand.",
+           "// Parameter derivatives of the closed-form dynamics of systems_gen.h: SysDp<Sys>::vjp_p(x, u, p, v, gp) writes",
+           "// gp[k] = sum_i v[i] d f_i / d p_k, k < NP (p: the system's whole parameter buffer, variable scales included).  A parameter",
+           "// that enters the running cost only gets a literal 0.  The elastic twins have no specialisation (SUPPORTED = false).",
+           "#pragma once",
+           '#include "systems_gen.h"',
+           "namespace myriad {",
+           "template <class Sys> struct SysDp { static constexpr bool SUPPORTED = false; };",
+           ""]
+  for S in systems():
+    if S["name"].endswith("_ELASTIC"):
+      continue
+    parts.append(gen_system_dp(S))
+    parts.append("")
+  parts.append("}  // namespace myriad")
+  with open(OUT_DP, "w") as fh:
+    fh.write("\n".join(parts) + "\n")
+  print("wrote", os.path.abspath(OUT_DP))
+
+
 def main():
   parts = ["// GENERATED by tools/gen_systems.py (sympy) -- do not edit by hand.",
            "// Closed-form dynamics / cost / derivative code for the control systems on the hot path.",
@@ -508,4 +562,5 @@ MYR_HD inline void fold_terminal(const double* x, const double* u, const double*
 
 
 if __name__ == "__main__":
-  main()
+  import sys
+  main_dp() if "--dp" in sys.argv[1:] else main()
