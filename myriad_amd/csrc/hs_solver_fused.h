@@ -27,20 +27,6 @@
 
 namespace myriad {
 
-// A condition that is the same in every lane by the algorithm but not by the compiler's analysis, as a wave-uniform value: the branch on
-// it is a scalar branch (s_cbranch_scc), not an EXEC-masked region.  Used by the sweeps of the W > 1 kernels (inlined into a kernel whose
-// wavefronts take different paths; measured there: B = 256 / 512 kernel 2.95 / 3.10 ms against 3.01 / 3.15 ms); the sweep W = 1 calls as a
-// function keeps the per-lane form (all-or-none masks in uniform control flow, gated by the same tests: the scalar form costs it 1.6 %,
-// 14.55 against 14.33 ms -- profiles/r04/README.md; the switch that forced one form everywhere is in the history at 2373201).
-template <bool ON>
-__device__ inline bool uniform_if(bool c) {
-  if constexpr (ON) return __builtin_amdgcn_readfirstlane((int)c) != 0;
-  else return c;
-}
-
-// lane l <- lane l - 1 (lane 0: unspecified, the callers overwrite it)
-__device__ inline double lane_up1(double v) { return __shfl_up(v, 1, 64); }
-
 // W wavefronts share one trajectory (W = 1: the throughput form, four trajectories per CU; W = 2: the small-batch form, each
 // wavefront takes every other block of 64 stages / points and they meet at workgroup barriers -- the carries of the two wave
 // scans and the neighbour records cross through LDS; the Riccati sweep runs in wavefront 0).
@@ -1096,7 +1082,7 @@ struct HsFused {
     return nreg;
   }
 
-  // ---- Riccati sweep on v_mfma_f64_16x16x4_f64: HsWave::riccati_mfma (tile slots, chaining, pivot rule: see there), reading
+  // ---- Riccati sweep on v_mfma_f64_16x16x4_f64: the tile of riccati_tile.h (slots, chaining, pivot rule: see there), reading
   // the symmetric-packed point records; the prefetch ring reads PF stages below stage 0 into the padding in front of hr / st.
   // ONE body for the two uses of the tile.  CHUNK == false: the plain sweep over all N stages (k_lo_, k_hi_, last_, xo unused: the stage range
   // is [0, N), `last` the constant true), results to sP | sPc | sTnu, then the first point.  CHUNK == true: level 1 of the two-level sweep,
@@ -1112,7 +1098,6 @@ struct HsFused {
   // affine function of theta_c (the plain sweep's terminal-multiplier bookkeeping, with the control's row 7 kept as well) -- in ONE exchange block
   // (the layout of sP | sPc | sTnu | sKu, the control's T row where sKu is); tl_join eliminates the multipliers.  Gains K | kc as before (kc column
   // 1 now multiplies nu_u).  Same pivot rule; no first point.
-  typedef double mfma_d4 __attribute__((ext_vector_type(4)));
   template <bool CHUNK>
   __device__ static int riccati_tile(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg, int k_lo_, int k_hi_, bool last_, double* xo) {
     using namespace detail;
@@ -1122,10 +1107,7 @@ struct HsFused {
     static_assert(!CHUNK || (NC == NS + 2 && NU == 1), "slot 7 takes the control's multiplier");
     const int lane = c.lane;
     const int g = lane >> 4, j = lane & 15;
-    const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
-    const int ycol = scol >= 0 ? scol : ((j == 12 || j == 13) ? NS + 1 : ((j == 8 || j == 9) ? NS + 2 : -1));
-    const int cc = j == 6 ? 0 : (j == 7 ? 1 : (j == 10 ? 2 : (j == 11 ? 3 : (j == 14 ? 4 : (j == 15 ? 5 : -1)))));
-    const int rcc = (cc >= 0 && cc < NC) ? cc : -1;
+    const int scol = tile_scol<NS>(j), ycol = tile_ycol<NS, true>(j, scol), rcc = tile_rcc<NC>(j);
     const bool rowx = g < NS;
     const double* he = c.hr + (long)(2 * (k_hi - 1) + 2) * HR_N;
     const double* hm = he - HR_N;
@@ -1154,12 +1136,7 @@ struct HsFused {
     double X0 = (pinr && scol == g) ? rho0 : ((pinr && rcc == 2 + g) ? 1.0 : 0.0);
     double X1 = (!last && g < 2) ? (scol == NS ? rho0 : (rcc == 1 ? 1.0 : 0.0)) : 0.0;
     const double dv0 = (rowx && scol == g) ? delta : 0.0, dv1 = (g < 2 && scol == NS) ? delta : 0.0;
-    const double f_a1 = j < 6 ? 1.0 : 0.0;
-    const double f_keep = rcc >= 0 ? 1.0 : 0.0;
-    const double f_she = (j == 8 || j == 9) ? 1.0 : 0.0, f_shm = (j == 12 || j == 13) ? 1.0 : 0.0;
-    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = (CHUNK ? g >= 2 : g == 2) ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;      // (a chunk carries row 7 -- the control's multiplier -- like row 6)
-    const bool a3_on = g < 2 && (j < 6 || (CHUNK && j == 7) || j == 10 || j == 11 || j == 14 || j == 15);          // ... and takes the rank-2 update like the rows nu_x
-    const double f_a3m = (a3_on && g == 0) ? -1.0 : 0.0, f_a3e = (a3_on && g == 1) ? -1.0 : 0.0;
+    const TileMask<CHUNK, true> m(g, j, rcc);
     const int k_off = (g == 0 && scol >= 0 && j != 5) ? scol : ((g == 0 && rcc >= 0) ? NQ * NW + rcc : -1);
     const int k_str = k_off < 0 ? 1 : ((scol >= 0) ? NW : NC);
     double* k_ptr = k_off >= 0 ? c.kg + (long)(k_hi - 1) * KSTR + k_off : c.zr + ZR - 2;
@@ -1175,79 +1152,38 @@ struct HsFused {
       for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
       __builtin_amdgcn_sched_barrier(0);      // (slot by slot, in ring order: the loop's first stage then waits for slot 0 alone, not for the youngest loads)
     }
-    double QmU = 0.0;
-    mfma_d4 Qm;
-    {
-      double n0 = in[0][3] + dv0, n1 = in[0][4] + dv1;
-      const double s0 = W0::dpp_row_shr8(n0), s1 = W0::dpp_row_shr8(n1);
-      mfma_d4 C;
-      C[0] = fma(s0, f_shm, n0 * f_keep);
-      C[1] = fma(s1, f_shm, n1 * f_keep);
-      C[2] = 0.0; C[3] = 0.0;
-      const mfma_d4 R = __builtin_amdgcn_mfma_f64_16x16x4f64(n0 * f_a1, in[0][5], C, 0, 0, 0);
-      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(in[0][5], R[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-      QmU = R[1];
-    }
-    mfma_d4 D3 = {X0, X1, 0.0, 0.0};
+    // This stage is NOT HsWave::riccati_mfma's arithmetic, it only shares its pieces (riccati_tile.h): rows 8..15 of R~ and of the midpoint's R are zero --
+    // the A operand has no such rows -- and stay zero from stage to stage, so the previous result IS the next C operand's upper half (D1c, Rmc: no zero
+    // fill); the control rows of the midpoint's R enter rows 12..15 of Q where Q is consumed (QmU) instead of through a C operand that is zero but for them.
     mfma_d4 D1c = {0.0, 0.0, 0.0, 0.0}, Rmc = {0.0, 0.0, 0.0, 0.0};
+    mfma_d4 Qm;
+    double QmU;
+    auto mid_part = [&](double n0, double n1, double Gm, const mfma_d4& Cup) -> mfma_d4 {
+      const mfma_d4 Rm = tile_prod1<8>(n0 + dv0, n1 + dv1, Gm, m.f_a1, m.f_keep, m.f_shm, Cup);
+      Qm = tile_mfma(Gm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0});
+      QmU = Rm[1];
+      return Rm;
+    };
+    mid_part(in[0][3], in[0][4], in[0][5], mfma_d4{0.0, 0.0, 0.0, 0.0});
+    mfma_d4 D3 = {X0, X1, 0.0, 0.0};
     // one stage from ring slot u
     auto stage = [&](const int u) {
-      X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], f_x1, in[u][1] + dv1);
+      X0 = D3[0] + (in[u][0] + dv0); X1 = fma(D3[1], m.f_x1, in[u][1] + dv1);
       const double G = in[u][2];
       const double nn0 = in[(u + 1) % PF][3], nn1 = in[(u + 1) % PF][4], nGm = in[(u + 1) % PF][5];
-      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
-      // (rows 8..15 of R~ are zero -- the A operand has no such rows -- and stay zero from stage to stage: the previous result IS the next C operand's
-      //  upper half, no zero fill)
-      mfma_d4 C1 = D1c;
-      C1[0] = fma(sh0, f_she, X0 * f_keep);
-      C1[1] = fma(sh1, f_she, X1 * f_keep);
-      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+      const mfma_d4 D1 = tile_prod1<4>(X0, X1, G, m.f_a1, m.f_keep, m.f_she, D1c);
       D1c = D1;
-      mfma_d4 C2;
-      C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
+      mfma_d4 C2 = tile_c2_hs(D3, D1, Qm, m.f_t1, m.f_t23);
       C2[3] += QmU;
-      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
+      const mfma_d4 D2 = tile_mfma(G, D1[0], C2);
       // midpoint part of stage k-1 (independent of the recursion): issued HERE, so that its two dependent products run on
       // the matrix pipe while the vector pipe waits for D2 and computes the gains -- behind D3 they delayed the next stage's D1
-      double m0 = nn0 + dv0, m1 = nn1 + dv1;
-      const double ms0 = W0::dpp_row_shr8(m0), ms1 = W0::dpp_row_shr8(m1);
-      mfma_d4 Cm = Rmc;
-      Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-      Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-      const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
-      Rmc = Rm;
-      // (the control rows of R enter rows 12..15 of Q: added where Q is consumed -- QmU -- instead of through a C operand that is zero but for them)
-      Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], mfma_d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-      QmU = Rm[1];
-      const double q00 = W0::rdlane(D2[3], 12), q10 = W0::rdlane(D2[2], 12), q11 = W0::rdlane(D2[2], 8);
-      const double det = fma(q00, q11, -(q10 * q10));
-      const double rdet = fast_rcp(det);
-      const double b0 = D2[3], b1 = D2[2];
-      double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
-      double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
-      // (the pivot test is wave-uniform -- the pivots come from v_readlane -- but the compiler sees per-lane values: decided in the
-      //  vector unit and, in the W > 1 kernels, made a SCALAR branch through readfirstlane, so that no matrix instruction of their sweep
-      //  sits inside an EXEC-masked region: v_mfma does not honour EXEC on this part, tools/dev/litmus/mfma_exec.hip)
-      const bool rare_ = !(q00 > reg_floor) || !(det > reg_floor * q00);
-      if (uniform_if<(W > 1)>(rare_)) {                                       // rare
-        const double u00 = q00, u10 = q10, u11 = q11;
-        double d0 = u00;
-        if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
-        const double i0 = fast_rcp(d0);
-        const double l10 = u10 * i0;
-        double d1 = u11 - l10 * l10 * d0;
-        if (!(d1 > reg_floor)) { d1 = dmax(fabs(d1), reg_floor); ++nreg; }
-        const double i1 = fast_rcp(d1);
-        kk0 = b0; kk1 = b1;
-        kk1 -= l10 * kk0;
-        kk0 *= i0; kk1 *= i1;
-        kk0 -= l10 * kk1;
-      }
-      k_ptr[0] = kk0; k_ptr[k_str] = kk1;
+      Rmc = mid_part(nn0, nn1, nGm, Rmc);
+      // (the pivot branch is a SCALAR branch in the W > 1 kernels -- tile_gain2 -- and an abort waits for the top of the next group, below)
+      const TileGain2 gn = tile_gain2<(W > 1)>(D2, reg_floor, nreg, TileNoStop());
+      k_ptr[0] = gn.kk0; k_ptr[k_str] = gn.kk1;
       k_ptr -= k_step;
-      const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
-      const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);
-      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      D3 = tile_update2(D2, gn.kk0, gn.kk1, m.f_a3m, m.f_a3e, g);
       // refill slot u (stage k - PF) only here, behind the pivot branch: the scheduler cannot lift the loads above D2, the last reader of
       // the slot's G, so they land in the ring's own registers.  Issued in front of D2, they needed temporaries that the end of the stage
       // copied into the ring -- a wait for this stage's own loads.
@@ -1280,41 +1216,12 @@ struct HsFused {
       stage(u);
     }
     if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
-    X0 = D3[0]; X1 = D3[1];
-    const double T1 = D3[1], T2 = D3[2], T3 = D3[3];
     if constexpr (!CHUNK) {
-      if (scol >= 0 && j != 5) {
-        if (rowx) c.sP[g * NW + scol] = X0;
-        if (g == 0) c.sP[NS * NW + scol] = X1;
-      }
-      if (rcc >= 0) {
-        if (rowx) c.sPc[g * NC + rcc] = X0;
-        if (g == 0) c.sPc[NS * NC + rcc] = X1;
-        if (g >= 2 && g - 2 < NS) c.sTnu[(g - 2) * NC + rcc] = T2;
-        if (g >= 2 && g < NS) c.sTnu[g * NC + rcc] = T3;
-      }
-      wave_sync<true>();
-      if (g == 2 && rcc >= 2) c.sTnu[(rcc - 2) * NC + 0] += T1;
-      wave_sync<true>();
+      tile_store_first<false, NS, NC>(D3, g, j, scol, rcc, rowx, c.sP, c.sPc, c.sTnu, [] { wave_sync<true>(); });
       return riccati_first_point(c, o, delta, nreg);
     } else {
       double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;      // T: rows nu_x (NS), then the row of nu_u
-      if (scol >= 0 && j != 5) {
-        if (rowx) xP[g * NW + scol] = X0;
-        if (g == 0) xP[NS * NW + scol] = X1;
-      }
-      if (rcc >= 0) {
-        if (rowx) xPc[g * NC + rcc] = X0;
-        if (g == 0) xPc[NS * NC + rcc] = X1;
-        if (g >= 2 && g - 2 < NS) xT[(g - 2) * NC + rcc] = T2;
-        if (g >= 2 && g < NS) xT[g * NC + rcc] = T3;
-        if (g == 3) xT[NS * NC + rcc] = T1;
-      }
-      wave_sync<true>();
-      // the part of T[nu_m]["1"] that the products leave in row "1" (g^T pc', as in the plain sweep)
-      if (g == 2 && rcc >= 2) xT[(rcc - 2) * NC + 0] += T1;
-      if (g == 2 && rcc == 1) xT[NS * NC + 0] += T1;
-      wave_sync<true>();
+      tile_store_first<true, NS, NC>(D3, g, j, scol, rcc, rowx, xP, xPc, xT, [] { wave_sync<true>(); });
       return nreg;
     }
   }
@@ -1364,19 +1271,6 @@ struct HsFused {
     for (int cc = 0; cc < NC; ++cc)
       if (g_slot_cc(g_rhs_slot(cc)) != cc || g_rhs_slot(cc) >= 16 * G_CT) return false;
     return g_rhs_slot(0) < 16 && g_rhs_slot(1) < 16;
-  }
-  // every lane group <- the values of lane groups 0..3 (same lane within the group): v_permlane32_swap, then v_permlane16_swap twice
-  __device__ static inline void gather4(double x, double* o) {
-    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(x), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(x), false, false);
-    // [0]: groups (0, 1, 0, 1); [1]: groups (2, 3, 2, 3)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const auto l2 = __builtin_amdgcn_permlane16_swap(lo[h], lo[h], false, false);
-      const auto h2 = __builtin_amdgcn_permlane16_swap(hi[h], hi[h], false, false);
-      o[2 * h] = __hiloint2double(h2[0], l2[0]);
-      o[2 * h + 1] = __hiloint2double(h2[1], l2[1]);
-    }
   }
   __device__ static int riccati_mfma_gen(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
     using namespace detail;
@@ -1566,7 +1460,7 @@ struct HsFused {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int q = 0; q <= r; ++q) Lq[r * 4 + q] = (r < nbq) ? W0::rdlane(kk[QT][4 * b + r], QL + 4 * b + q) : (r == q ? 1.0 : 0.0);
+            for (int q = 0; q <= r; ++q) Lq[r * 4 + q] = (r < nbq) ? rdlane(kk[QT][4 * b + r], QL + 4 * b + q) : (r == q ? 1.0 : 0.0);
           nreg += ldl_reg<4>(Lq, dinv, reg_floor);
           if (nreg > 0 && abort_on_reg) return nreg;
           const double mQ = (qc[QT] >= 4 * (b + 1)) ? -1.0 : 0.0;       // ... and the q rows that are still alive
@@ -1594,7 +1488,7 @@ struct HsFused {
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int e = 4 * (b + 1); e < NQ; ++e) m[t][e] = W0::rdlane(kk[QT][4 * b + t], QL + e);
+            for (int e = 4 * (b + 1); e < NQ; ++e) m[t][e] = rdlane(kk[QT][4 * b + t], QL + e);
 #pragma unroll
           for (int C = 0; C < CT; ++C)
 #pragma unroll
@@ -1693,7 +1587,7 @@ struct HsFused {
     }
   }
 
-  // The same sweep for the trapezoidal scheme (HsWave::riccati_mfma_trap): y = (dx_s, du_s, du_e), ONE eliminated control per stage, no
+  // The same sweep for the trapezoidal scheme (the three-product stage of riccati_tile.h): y = (dx_s, du_s, du_e), ONE eliminated control per stage, no
   // midpoint part -- three matrix instructions per stage, the single pivot Q[du_e][du_e] read from lane 8 of register 2; the end point
   // of stage k is point k + 1.  CHUNK as in riccati_tile: the plain sweep, or the stages [k_lo, k_hi) of one chunk.
   template <bool CHUNK>
@@ -1704,10 +1598,9 @@ struct HsFused {
     const bool last = CHUNK ? last_ : true;
     const int lane = c.lane;
     const int g = lane >> 4, j = lane & 15;
-    const int scol = j < 4 ? (j < NS ? j : -1) : (j < 6 ? NS : -1);
-    const int ycol = scol >= 0 ? scol : ((j == 8 || j == 9) ? NW : -1);
-    const int cc = j == 6 ? 0 : (j == 7 ? 1 : (j == 10 ? 2 : (j == 11 ? 3 : (j == 14 ? 4 : (j == 15 ? 5 : -1)))));
-    const int rcc = (cc >= 0 && cc < NC) ? cc : -1;
+    const int scol = tile_scol<NS>(j);
+    const int ycol = scol >= 0 ? scol : ((j == 8 || j == 9) ? NW : -1);      // (tile_ycol<NS, false> written out: through the function this sweep's setup compiles to other code)
+    const int rcc = tile_rcc<NC>(j);
     const bool rowx = g < NS;
     const double* he = c.hr + (long)k_hi * HR_N;
     const double* st = c.st + (long)(k_hi - 1) * SG_N;
@@ -1728,9 +1621,8 @@ struct HsFused {
     const double X0i = (pinr && scol == g) ? rho0 : ((pinr && rcc == 2 + g) ? 1.0 : 0.0);
     const double X1i = (!last && g < 2) ? (scol == NS ? rho0 : (rcc == 1 ? 1.0 : 0.0)) : 0.0;
     const double dv0 = (rowx && scol == g) ? delta : 0.0, dv1 = (g < 2 && scol == NS) ? delta : 0.0;
-    const double f_a1 = j < 6 ? 1.0 : 0.0, f_keep = rcc >= 0 ? 1.0 : 0.0, f_she = (j == 8 || j == 9) ? 1.0 : 0.0;
-    const double f_x1 = g < 2 ? 1.0 : 0.0, f_t1 = (CHUNK ? g >= 2 : g == 2) ? 1.0 : 0.0, f_t23 = g >= 2 ? 1.0 : 0.0;
-    const double f_a3 = (g == 0 && (j < 6 || (CHUNK && j == 7) || j == 10 || j == 11 || j == 14 || j == 15)) ? -1.0 : 0.0;
+    const TileMask<CHUNK, false> m(g, j, rcc);
+    const double f_a1 = m.f_a1, f_keep = m.f_keep, f_she = m.f_she, f_x1 = m.f_x1, f_t1 = m.f_t1, f_t23 = m.f_t23, f_a3m = m.f_a3m;      // (copies on purpose: with m.f_* used directly two register moves at the top of the loop of sweep_call / chunk_call swap places)
     const int k_off = (g == 0 && scol >= 0 && j != 5) ? scol : ((g == 0 && rcc >= 0) ? NQ * NW + rcc : -1);
     double* k_ptr = k_off >= 0 ? c.kg + (long)(k_hi - 1) * KSTR + k_off : c.zr + ZR - 2;
     const long k_step = k_off >= 0 ? KSTR : 0;
@@ -1750,27 +1642,11 @@ struct HsFused {
     auto stage = [&](const int u) {
       const double X0 = D3[0] + (in[u][0] + dv0), X1 = fma(D3[1], f_x1, in[u][1] + dv1);
       const double G = in[u][2];
-      const double sh0 = W0::dpp_row_shr4(X0), sh1 = W0::dpp_row_shr4(X1);
-      mfma_d4 C1;
-      C1[0] = fma(sh0, f_she, X0 * f_keep);
-      C1[1] = fma(sh1, f_she, X1 * f_keep);
-      C1[2] = 0.0; C1[3] = 0.0;
-      const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-      mfma_d4 C2;
-      C2[0] = 0.0; C2[1] = D3[1] * f_t1; C2[2] = fma(D3[2], f_t23, D1[1]); C2[3] = D3[3] * f_t23;
-      const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-      const double q11 = W0::rdlane(D2[2], 8);
-      double d = q11;
-      const bool rare_ = !(d > reg_floor);
-      if (uniform_if<(W > 1)>(rare_)) {                                       // rare (same pivot rule as chol_reg); a scalar branch, see riccati_tile
-        d = dmax(fabs(d), reg_floor); ++nreg;
-      }
-      const double kk = D2[2] * fast_rcp(d);
-      k_ptr[0] = kk;
+      const TileEnd e = tile_end_part<false>(D3, X0, X1, G, f_a1, f_keep, f_she, f_t1, f_t23);
+      const TileGain1 gn = tile_gain1<(W > 1)>(e.D2, reg_floor, nreg, TileNoStop());
+      k_ptr[0] = gn.kk;
       k_ptr -= k_step;
-      const double A3 = D2[2] * f_a3;
-      const double B3 = g == 0 ? kk : 0.0;
-      D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+      D3 = tile_update1(e.D2, gn.kk, f_a3m, g);
       // refill slot u (stage k - PF) behind the pivot branch, where the loads land in the ring's own registers (riccati_tile)
 #pragma unroll
       for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
@@ -1794,6 +1670,7 @@ struct HsFused {
     }
     if (uniform_if<true>(nreg > 0 && abort_u)) return nreg;
     if constexpr (!CHUNK) {
+      // (tile_store_first of riccati_tile.h written out, here and for the chunk: through the function the one-state systems' sweeps compile to other code)
       const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
       if (scol >= 0 && j != 5) {
         if (rowx) c.sP[g * NW + scol] = X0;
@@ -1810,8 +1687,8 @@ struct HsFused {
       wave_sync<true>();
       return riccati_first_point(c, o, delta, nreg);
     } else {
-      const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
       double* xP = xo; double* xPc = xo + NW * NW; double* xT = xPc + NW * NC;
+      const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
       if (scol >= 0 && j != 5) {
         if (rowx) xP[g * NW + scol] = X0;
         if (g == 0) xP[NS * NW + scol] = X1;
@@ -2101,8 +1978,8 @@ struct HsFused {
           double a0 = ring[g][NW], a1 = 0.0;
 #pragma unroll
           for (int j = 0; j < NW; j += 2) {
-            a0 = fma(ring[g][j], W0::rdlane(x, j), a0);
-            if (j + 1 < NW) a1 = fma(ring[g][j + 1], W0::rdlane(x, j + 1), a1);
+            a0 = fma(ring[g][j], rdlane(x, j), a0);
+            if (j + 1 < NW) a1 = fma(ring[g][j + 1], rdlane(x, j + 1), a1);
           }
           x = a0 + a1;
           c.dz[zi(c, knot(k + 1), row)] = x;

@@ -18,183 +18,13 @@
 #include <hip/hip_runtime.h>
 #include "hs_solver.h"
 #include "node_mfma.h"
+#include "wave_prims.h"     // barrier, reductions, lane movement, wave scans
+#include "riccati_tile.h"   // the matrix-core tile of one Riccati stage
 
 namespace myriad {
 
 // network dynamics (node_system.h) are evaluated by the matrix-core passes of node_mfma.h inside the wavefront solver (NodeTraits there)
 
-// Barrier of the phases of ONE wavefront.  A workgroup of a single wavefront uses the hardware barrier; network systems pack
-// several independent wavefronts into a workgroup (they share the weights in LDS) and may not meet at a workgroup barrier:
-// there the phases of a wavefront are ordered by a fence (all its LDS / global accesses retired) + the wave barrier.
-template <bool MULTI>
-__device__ inline void wave_sync() {
-  if constexpr (MULTI) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
-  else __syncthreads();
-}
-__device__ inline double wv_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ inline double wv_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double t = __shfl_xor(v, o, 64); v = v > t ? v : t; }
-  return v;
-}
-__device__ inline double wv_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double t = __shfl_xor(v, o, 64); v = v < t ? v : t; }
-  return v;
-}
-// reciprocal from v_rcp_f64 + two Newton steps (the operands here are pivots already known to exceed reg_floor)
-__device__ inline double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  double e = fma(-x, r, 1.0);
-  r = fma(r, e, r);
-  e = fma(-x, r, 1.0);
-  return fma(r, e, r);
-}
-// L D L^T of a small SPD block with the SAME pivot rule as detail::chol_reg (the pivots d_j are the squares of the
-// Cholesky diagonal): a <- unit lower factor (strict lower part), dinv <- 1 / d.  No sqrt, one reciprocal per pivot.
-template <int n>
-__device__ inline int ldl_reg(double* a, double* dinv, double floor_) {
-  int nreg = 0;
-  double d[n];
-#pragma unroll
-  for (int j = 0; j < n; ++j) {
-    double dj = a[j * n + j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) dj -= a[j * n + k] * a[j * n + k] * d[k];
-    if (!(dj > floor_)) { dj = detail::dmax(fabs(dj), floor_); ++nreg; }
-    d[j] = dj;
-    dinv[j] = fast_rcp(dj);
-#pragma unroll
-    for (int i = j + 1; i < n; ++i) {
-      double t = a[i * n + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) t -= a[i * n + k] * a[j * n + k] * d[k];
-      a[i * n + j] = t * dinv[j];
-    }
-  }
-  return nreg;
-}
-template <int n>
-__device__ inline void ldl_solve(const double* a, const double* dinv, double* b) {
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-#pragma unroll
-    for (int k = 0; k < i; ++k) b[i] -= a[i * n + k] * b[k];
-  }
-#pragma unroll
-  for (int i = 0; i < n; ++i) b[i] *= dinv[i];
-#pragma unroll
-  for (int i = n - 1; i >= 0; --i) {
-#pragma unroll
-    for (int k = i + 1; k < n; ++k) b[i] -= a[k * n + i] * b[k];
-  }
-}
-
-// every lane <- lane LANE of its own row of 16 lanes (DPP row_newbcast: stays in the vector pipe, ~10 cycles; v_readlane
-// goes through the scalar register file and costs ~55 cycles before a vector instruction can use the value)
-template <int LANE>
-__device__ inline double wv_row_bcast(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v), rlo, rhi;
-  asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_newbcast:%4 row_mask:0xf bank_mask:0xf\n\t"
-               "v_mov_b32_dpp %1, %3 row_newbcast:%4 row_mask:0xf bank_mask:0xf"
-               : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi), "n"(LANE));
-  return __hiloint2double(rhi, rlo);
-}
-template <int NQ_>
-struct RowBcast {       // q[i] = value of lane i (i < NQ_ <= 16) of the caller's row, for all i
-  template <int I = 0>
-  __device__ static inline void all(double v, double* q) {
-    if constexpr (I < NQ_) { q[I] = wv_row_bcast<I>(v); all<I + 1>(v, q); }
-  }
-};
-
-__device__ inline int wv_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Affine maps x -> A x + b (n x n) in registers, one per lane: composition and the two wave scans built on it.
-// `wv_down(v, d)` = value of lane + d (own value beyond the wave), `wv_up` = lane - d.
-__device__ inline double wv_down(double v, int d) { return __shfl_down(v, d, 64); }
-__device__ inline double wv_up(double v, int d) { return __shfl_up(v, d, 64); }
-template <int n>
-__device__ inline void affine_after(double* A, double* b, const double* A2, const double* b2) {   // (A,b) <- (A,b) o (A2,b2)
-  double R[n * n], r[n];
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-    double v = b[i];
-#pragma unroll
-    for (int k = 0; k < n; ++k) v += A[i * n + k] * b2[k];
-    r[i] = v;
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double w = 0.0;
-#pragma unroll
-      for (int k = 0; k < n; ++k) w += A[i * n + k] * A2[k * n + j];
-      R[i * n + j] = w;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < n * n; ++i) A[i] = R[i];
-#pragma unroll
-  for (int i = 0; i < n; ++i) b[i] = r[i];
-}
-// suffix scan: lane l <- T_l o T_{l+1} o .. o T_63        prefix scan: lane l <- T_l o T_{l-1} o .. o T_0
-template <int n, bool SUFFIX>
-__device__ inline void affine_scan(double* A, double* b) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    double A2[n * n], b2[n];
-#pragma unroll
-    for (int i = 0; i < n * n; ++i) A2[i] = SUFFIX ? wv_down(A[i], d) : wv_up(A[i], d);
-#pragma unroll
-    for (int i = 0; i < n; ++i) b2[i] = SUFFIX ? wv_down(b[i], d) : wv_up(b[i], d);
-    if (SUFFIX ? (lane + d < 64) : (lane >= d)) affine_after<n>(A, b, A2, b2);
-  }
-}
-// The prefix scan with DPP moves instead of ds_bpermute (one VALU move per dword and round): four shifts inside the rows
-// of 16 lanes, then row_bcast:15 (rows 1, 3 take lane 15 / 47) and row_bcast:31 (lanes 32..63 take lane 31) -- the
-// wave-scan idiom of GFX9.  Inline asm, executed by all lanes: a DPP builtin sunk into the divergent branch that consumes
-// it would read 0 from the lanes EXEC has switched off (see dpp_row_shr4 below).
-template <int STEP>
-__device__ inline double dpp_scan_src(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v), rlo, rhi;
-  if constexpr (STEP == 0)
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %1, %3 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-  else if constexpr (STEP == 1)
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %1, %3 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-  else if constexpr (STEP == 2)
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %1, %3 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-  else if constexpr (STEP == 3)
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %1, %3 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-  else if constexpr (STEP == 4)
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_bcast:15 row_mask:0xa bank_mask:0xf\n\tv_mov_b32_dpp %1, %3 row_bcast:15 row_mask:0xa bank_mask:0xf" : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-  else
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_bcast:31 row_mask:0xc bank_mask:0xf\n\tv_mov_b32_dpp %1, %3 row_bcast:31 row_mask:0xc bank_mask:0xf" : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-  return __hiloint2double(rhi, rlo);
-}
-template <int n, int STEP>
-__device__ inline void affine_prefix_round(double* A, double* b) {
-  const int lane = threadIdx.x & 63, l16 = lane & 15;
-  double A2[n * n], b2[n];
-#pragma unroll
-  for (int i = 0; i < n * n; ++i) A2[i] = dpp_scan_src<STEP>(A[i]);
-#pragma unroll
-  for (int i = 0; i < n; ++i) b2[i] = dpp_scan_src<STEP>(b[i]);
-  const bool take = STEP < 4 ? (l16 >= (1 << STEP)) : (STEP == 4 ? ((lane >> 4) & 1) != 0 : lane >= 32);
-  if (take) affine_after<n>(A, b, A2, b2);
-}
-template <int n>
-__device__ inline void affine_prefix_scan_dpp(double* A, double* b) {       // lane l <- T_l o T_{l-1} o .. o T_0
-  affine_prefix_round<n, 0>(A, b); affine_prefix_round<n, 1>(A, b); affine_prefix_round<n, 2>(A, b);
-  affine_prefix_round<n, 3>(A, b); affine_prefix_round<n, 4>(A, b); affine_prefix_round<n, 5>(A, b);
-}
 
 // SCHEME 0: Hermite-Simpson (K = 2N+1 points, stage unknowns y = (dx_s, du_s, du_m, du_e), two eliminated controls);
 // SCHEME 1: trapezoidal collocation (/root/reference/myriad/trajectory_optimizers/collocation/trapezoidal.py:80-163; K = N+1
@@ -858,13 +688,6 @@ struct HsWave {
   // branches); the only shared data per stage are P' (NW x NW, through LDS), Ge|ge (LDS) and a handful of entries of
   // the q columns, which are read with v_readlane.  One barrier per stage.
   // Returns the number of regularised pivots (wave-uniform); aborts at the first one when `abort_on_reg`.
-  __device__ static inline double rdlane(double v, int l) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, l);
-    hi = __builtin_amdgcn_readlane(hi, l);
-    return __hiloint2double(hi, lo);
-  }
-
   // first point: dx_0 = 0; add its control terms, eliminate du_0 (every lane redundantly; tiny).  P, pc, Tnu come from
   // the sweep through LDS (sP, sPc, sTnu).
   __device__ static int riccati_first_point(Ctx& c, const HsSolveOpts& o, double delta, int nreg) {
@@ -1065,56 +888,15 @@ struct HsWave {
   }
 
   // ---- phase 6, matrix-core form (NU == 1, NS <= 4): the SAME stage algebra as riccati() on v_mfma_f64_16x16x4_f64 -------
-  // The stage update is three small dense products,
-  //     R~      = P' [Ge^ | ge^] + [0 | pc']                          (NW x (NY+NC))
-  //     [Q|qc]  = [Qm | qcm] + Ge^^T R~                               (NY x (NY+NC))
-  //     [P|pc]  = [Qss | qc_s] - Qsq (Qqq^-1 [Qqs | qc_q])            (NW x (NW+NC))   (+ the dual bookkeeping rows)
-  // and one 16x16 matrix-core tile holds all of a stage: the SAME slot placement is used for rows and for columns,
-  //     0..3 dx_s | 4,5 du_s (twice) | 6 rhs "1" (where ge enters) | 7 rhs mu | 8,9 du_e (twice) | 10,11,14,15 rhs nu_1..4 |
-  //     12,13 du_m (twice),
-  // chosen for the register layout of the instruction (A[i][k] and B[k][j] one value per lane at lane 16k+i / 16k+j; C/D
-  // element (i,j) at lane 16 (i%4) + j, register i/4 -- probed on the hardware, tools/dev/mfma/probe_f64.hip):
-  //   * rows 0..3 of a result (register 0) ARE the B operand of the next product, and, P and Q being symmetric, also its A
-  //     operand: the three products chain without any data movement between lanes;
-  //   * the rows of the two eliminated controls du_m (12,13) and du_e (8,9) share lanes (registers 3 and 2 of lane groups
-  //     0 and 1), so every column's gain is a per-lane 2x2 solve; keeping du_s, du_m, du_e TWICE gives lane groups 0 and 1
-  //     each their own copy, which is exactly where the rank-2 update wants its two K-slots;
-  //   * the dual bookkeeping Tnu (the rows ge^T pc' and -qc_q^T kc of riccati()) falls out of the same instructions as
-  //     extra result rows (6 and 10,11,14,15) that are otherwise unused.
-  // Per stage: 3 MFMA + ~70 VALU + 6 v_readlane, no LDS, no barrier (riccati(): ~430 instructions, 2 barriers).
+  // One 16x16 matrix-core tile holds all of a stage (layout: riccati_tile.h).  Products, gain rules and epilogue are the functions of that header, shared
+  // with HsFused and ShootWave; the records and streams, the loop and its prefetch ring and the immediate abort are this kernel's.  Slot map, lane factors,
+  // seed and gain address are written out: with all of them behind the header's functions this kernel needs more scratch memory or AGPRs for five systems.
+  // Per stage: 5 MFMA (trapezoidal: 3) + ~70 VALU + 6 v_readlane, no LDS, no barrier (riccati(): ~430 instructions, 2 barriers).
 #ifndef MYR_RICCATI_PF
 #define MYR_RICCATI_PF 4
 #endif
   static_assert(MYR_RICCATI_PF >= 2 && MYR_RICCATI_PF <= 8, "the prefetch ring needs two slots; PADF covers eight");
   static constexpr bool MFMA_RICCATI = (NU == 1 && NS <= 4);
-  typedef double mfma_d4 __attribute__((ext_vector_type(4)));
-  // lane l <- lane l-4 within its row of 16 lanes (0 where l%16 < 4).  Inline asm on purpose: the compiler sinks the
-  // DPP builtin into the divergent branch of the select that consumes it, and a DPP read of a lane that EXEC has
-  // switched off returns 0 -- the shifted value must be produced with every lane enabled.
-  __device__ static inline double dpp_row_shr4(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v), rlo, rhi;
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                 "v_mov_b32_dpp %1, %3 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                 : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-    return __hiloint2double(rhi, rlo);
-  }
-  // every lane <- lane N of its own row of 16 (DPP row_newbcast: stays in the vector pipe, ~10 cycles; v_readlane goes
-  // through the scalar file and costs ~55 cycles before a vector instruction can use the value)
-  template <int LANE>
-  __device__ static inline double dpp_row_bcast(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v), rlo, rhi;
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_newbcast:%4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mov_b32_dpp %1, %3 row_newbcast:%4 row_mask:0xf bank_mask:0xf"
-                 : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi), "n"(LANE));
-    return __hiloint2double(rhi, rlo);
-  }
-  __device__ static inline double dpp_row_shr8(double v) {      // lane l <- lane l-8 within its row of 16
-    int lo = __double2loint(v), hi = __double2hiint(v), rlo, rhi;
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                 "v_mov_b32_dpp %1, %3 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                 : "=&v"(rlo), "=&v"(rhi) : "v"(lo), "v"(hi));
-    return __hiloint2double(rhi, rlo);
-  }
   __device__ static int riccati_mfma(Ctx& c, const HsSolveOpts& o, double delta, bool abort_on_reg) {
     static_assert(!TRAP, "Hermite-Simpson form");
     using namespace detail;
@@ -1152,9 +934,7 @@ struct HsWave {
     const bool pinr = rowx && c.term_pinned[rowx ? g : 0];
     double X0 = (pinr && scol == g) ? o.rho_term - delta : ((pinr && rcc == 2 + g) ? 1.0 : 0.0), X1 = 0.0;
     const double dv0 = (rowx && scol == g) ? delta : 0.0, dv1 = (g < 2 && scol == NS) ? delta : 0.0;
-    // Lane selections are per-lane 0/1 factors folded into multiply-adds (one fp64 instruction instead of two 32-bit
-    // selects plus an add).  A factor 0 meets only finite values: the unused rows / columns of the tile hold finite
-    // combinations of the inputs (if an input is not finite the solve is reported NAN anyway).
+    // per-lane 0/1 factors folded into multiply-adds (TileMask in riccati_tile.h says why they are safe)
     const double f_a1 = j < 6 ? 1.0 : 0.0;                                  // A operand of the R~ products: P' / H_m columns
     const double f_keep = rcc >= 0 ? 1.0 : 0.0;                             // C operand: the right-hand-side columns pass
     const double f_she = (j == 8 || j == 9) ? 1.0 : 0.0, f_shm = (j == 12 || j == 13) ? 1.0 : 0.0;   // selector columns
@@ -1184,16 +964,8 @@ struct HsWave {
     // end-point part with H_m in the place of P'; it depends on loaded data only, so stage k-1's is issued while stage
     // k waits for its pivots (this is what intervals_qm() computes, lanes over intervals, for riccati())
     auto mid_part = [&](double n0, double n1, double Gm) -> mfma_d4 {
-      n0 += dv0; n1 += dv1;
-      const double s0 = dpp_row_shr8(n0), s1 = dpp_row_shr8(n1);
-      mfma_d4 C;
-      C[0] = fma(s0, f_shm, n0 * f_keep);
-      C[1] = fma(s1, f_shm, n1 * f_keep);
-      C[2] = 0.0; C[3] = 0.0;
-      const mfma_d4 R = __builtin_amdgcn_mfma_f64_16x16x4f64(n0 * f_a1, Gm, C, 0, 0, 0);
-      mfma_d4 C2;
-      C2[0] = 0.0; C2[1] = 0.0; C2[2] = 0.0; C2[3] = R[1];          // selector row: the du_m rows take R's row du
-      return __builtin_amdgcn_mfma_f64_16x16x4f64(Gm, R[0], C2, 0, 0, 0);
+      const mfma_d4 R = tile_prod1<8>(n0 + dv0, n1 + dv1, Gm, f_a1, f_keep, f_shm, mfma_d4{0.0, 0.0, 0.0, 0.0});
+      return tile_mfma(Gm, R[0], mfma_d4{0.0, 0.0, 0.0, R[1]});          // selector row: the du_m rows take R's row du
     };
     mfma_d4 Qm = mid_part(in[0][3], in[0][4], in[0][5]);
     mfma_d4 D3 = {X0, X1, 0.0, 0.0};          // previous stage's result: rows 0..5 [P | pc], rows 6, 10, 11, 14, 15 Tnu
@@ -1211,79 +983,22 @@ struct HsWave {
 #pragma unroll
         for (int q = 0; q < 6; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
         // (b) R~ = P' [Ge^ | ge^] + [0 | pc']; the selector row of Ge^ (du_e) is the shifted column du of P'
-        const double sh0 = dpp_row_shr4(X0), sh1 = dpp_row_shr4(X1);
-        mfma_d4 C1;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        C1[2] = 0.0; C1[3] = 0.0;
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
+        const mfma_d4 D1 = tile_prod1<4>(X0, X1, G, f_a1, f_keep, f_she, mfma_d4{0.0, 0.0, 0.0, 0.0});
         // (c) [Q | qc] = Qm^ + Ge^^T R~  (selector row: the du_e rows take R~'s row du); rows 6, 10.. carry Tnu
-        mfma_d4 C2;
-        C2[0] = Qm[0]; C2[1] = fma(D3[1], f_t1, Qm[1]); C2[2] = fma(D3[2], f_t23, Qm[2]) + D1[1]; C2[3] = fma(D3[3], f_t23, Qm[3]);
-        const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-        // (d) this column's gains [K | kc] = Qqq^-1 [Qqs | qc_q].  Pivots of the L D L^T of Qqq as in ldl_reg: d0 = q00,
-        // d1 = q11 - q10^2 / q00 = det / q00, both required > reg_floor.  When they are (always, except inside the inertia
-        // correction's probing), the 2x2 solve is Cramer's rule with ONE reciprocal, 1 / det, whose dependent chain
-        // (product, fma, rcp + Newton, product) is a third of the factor-and-substitute one; the numerators do not depend
-        // on it.
-        const double q00 = rdlane(D2[3], 12), q10 = rdlane(D2[2], 12), q11 = rdlane(D2[2], 8);
-        const double det = fma(q00, q11, -(q10 * q10));
-        const double rdet = fast_rcp(det);
-        const double b0 = D2[3], b1 = D2[2];
-        double kk0 = fma(q11, b0, -(q10 * b1)) * rdet;
-        double kk1 = fma(q00, b1, -(q10 * b0)) * rdet;
-        if (!(q00 > reg_floor) || !(det > reg_floor * q00)) {          // wave-uniform, rare
-          const double u00 = q00, u10 = q10, u11 = q11;
-          double d0 = u00;
-          if (!(d0 > reg_floor)) { d0 = dmax(fabs(d0), reg_floor); ++nreg; }
-          const double i0 = fast_rcp(d0);
-          const double l10 = u10 * i0;
-          double d1 = u11 - l10 * l10 * d0;
-          if (!(d1 > reg_floor)) { d1 = dmax(fabs(d1), reg_floor); ++nreg; }
-          if (nreg > 0 && abort_on_reg) return nreg;
-          const double i1 = fast_rcp(d1);
-          kk0 = b0; kk1 = b1;
-          kk1 -= l10 * kk0;
-          kk0 *= i0; kk1 *= i1;
-          kk0 -= l10 * kk1;
-        }
+        const mfma_d4 D2 = tile_mfma(G, D1[0], tile_c2_hs(D3, D1, Qm, f_t1, f_t23));
+        // (d) this column's gains [K | kc] = Qqq^-1 [Qqs | qc_q] (tile_gain2); a plain branch, wave-uniform and rare, that an abort leaves at once
+        const TileGain2 gn = tile_gain2<false>(D2, reg_floor, nreg, [&]() { return nreg > 0 && abort_on_reg; });
+        if (gn.stop) return nreg;
+        const double kk0 = gn.kk0, kk1 = gn.kk1;
         k_ptr[0] = kk0; k_ptr[k_str] = kk1;                            // (lanes without a gain write a scratch slot)
         k_ptr -= k_step;
         // (e) [P | pc] = [Qss | qc_s] - Qsq [K | kc]; rows 10, 11, 14, 15: Tnu -= qc_q[:, nu]^T kc
-        const double A3 = fma(D2[3], f_a3m, D2[2] * f_a3e);
-        const double B3 = g == 0 ? kk0 : (g == 1 ? kk1 : 0.0);     // (a select: groups 2, 3 may hold non-finite junk)
-        D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
-        // midpoint part of stage k-1, first product: independent of the recursion, both products run behind D3
-        // while the next stage's operands are prepared
-        double m0 = nn0 + dv0, m1 = nn1 + dv1;
-        const double ms0 = dpp_row_shr8(m0), ms1 = dpp_row_shr8(m1);
-        mfma_d4 Cm;
-        Cm[0] = fma(ms0, f_shm, m0 * f_keep);
-        Cm[1] = fma(ms1, f_shm, m1 * f_keep);
-        Cm[2] = 0.0; Cm[3] = 0.0;
-        const mfma_d4 Rm = __builtin_amdgcn_mfma_f64_16x16x4f64(m0 * f_a1, nGm, Cm, 0, 0, 0);
-        // midpoint part of stage k-1, second product (selector row: the du_m rows take Rm's row du)
-        mfma_d4 Cq;
-        Cq[0] = 0.0; Cq[1] = 0.0; Cq[2] = 0.0; Cq[3] = Rm[1];
-        Qm = __builtin_amdgcn_mfma_f64_16x16x4f64(nGm, Rm[0], Cq, 0, 0, 0);
+        D3 = tile_update2(D2, kk0, kk1, f_a3m, f_a3e, g);
+        // midpoint part of stage k-1: independent of the recursion, both products run behind D3 while the next stage's operands are prepared
+        Qm = mid_part(nn0, nn1, nGm);
       }
     }
-    X0 = D3[0]; X1 = D3[1];                                          // (X1 is read below in group 0 only)
-    const double T1 = D3[1], T2 = D3[2], T3 = D3[3];                 // read in groups 2, 3 only
-    // hand P, pc, Tnu to the first-point step through LDS (layouts of riccati())
-    if (scol >= 0 && j != 5) {
-      if (rowx) c.sP[g * NW + scol] = X0;
-      if (g == 0) c.sP[NS * NW + scol] = X1;
-    }
-    if (rcc >= 0) {
-      if (rowx) c.sPc[g * NC + rcc] = X0;
-      if (g == 0) c.sPc[NS * NC + rcc] = X1;
-      if (g >= 2 && g - 2 < NS) c.sTnu[(g - 2) * NC + rcc] = T2;
-      if (g >= 2 && g < NS) c.sTnu[g * NC + rcc] = T3;
-    }
-    wsync();
-    if (g == 2 && rcc >= 2) c.sTnu[(rcc - 2) * NC + 0] += T1;       // row 6: ge^T pc'[:, nu_i], summed over the stages
-    wsync();
+    tile_store_first<false, NS, NC>(D3, g, j, scol, rcc, rowx, c.sP, c.sPc, c.sTnu, [] { wsync(); });
     return riccati_first_point(c, o, delta, nreg);
   }
 
@@ -1343,43 +1058,17 @@ struct HsWave {
         const double G = in[u][2];
 #pragma unroll
         for (int q = 0; q < 3; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-        const double sh0 = dpp_row_shr4(X0), sh1 = dpp_row_shr4(X1);
-        mfma_d4 C1;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        C1[2] = 0.0; C1[3] = 0.0;
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-        mfma_d4 C2;
-        C2[0] = 0.0; C2[1] = D3[1] * f_t1; C2[2] = fma(D3[2], f_t23, D1[1]); C2[3] = D3[3] * f_t23;
-        const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-        const double q11 = rdlane(D2[2], 8);
-        double d = q11;
-        if (!(d > reg_floor)) {                                        // wave-uniform, rare (same pivot rule as chol_reg)
-          d = dmax(fabs(d), reg_floor); ++nreg;
-          if (abort_on_reg) return nreg;
-        }
-        const double kk = D2[2] * fast_rcp(d);
+        const TileEnd e = tile_end_part<false>(D3, X0, X1, G, f_a1, f_keep, f_she, f_t1, f_t23);
+        const mfma_d4& D2 = e.D2;
+        const TileGain1 gn = tile_gain1<false>(D2, reg_floor, nreg, [&]() { return abort_on_reg; });
+        if (gn.stop) return nreg;
+        const double kk = gn.kk;
         k_ptr[0] = kk;
         k_ptr -= k_step;
-        const double A3 = D2[2] * f_a3;
-        const double B3 = g == 0 ? kk : 0.0;
-        D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+        D3 = tile_update1(D2, kk, f_a3, g);
       }
     }
-    const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];
-    if (scol >= 0 && j != 5) {
-      if (rowx) c.sP[g * NW + scol] = X0;
-      if (g == 0) c.sP[NS * NW + scol] = X1;
-    }
-    if (rcc >= 0) {
-      if (rowx) c.sPc[g * NC + rcc] = X0;
-      if (g == 0) c.sPc[NS * NC + rcc] = X1;
-      if (g >= 2 && g - 2 < NS) c.sTnu[(g - 2) * NC + rcc] = T2;
-      if (g >= 2 && g < NS) c.sTnu[g * NC + rcc] = T3;
-    }
-    wsync();
-    if (g == 2 && rcc >= 2) c.sTnu[(rcc - 2) * NC + 0] += T1;
-    wsync();
+    tile_store_first<false, NS, NC>(D3, g, j, scol, rcc, rowx, c.sP, c.sPc, c.sTnu, [] { wsync(); });
     return riccati_first_point(c, o, delta, nreg);
   }
 

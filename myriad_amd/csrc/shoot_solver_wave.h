@@ -444,14 +444,13 @@ struct ShootWave {
   }
 
   // ---- Riccati recursion on the matrix cores (one control, NS <= 4, one control row per step) --------------------------
-  // The stage algebra of os_riccati_stage as three v_mfma_f64_16x16x4_f64 per step -- the sweep of the trapezoidal wavefront
-  // solver (HsWave<Sys, 1>::riccati_mfma_trap: same tile slots, same chaining of the products through the result
-  // registers, same pivot and gain rule) with the step map Fy | c in the place of the eliminated collocation rows and
-  // the FULL step Hessian Hs | gy as the C operand of the second product (where Hermite-Simpson feeds its midpoint terms).
+  // The stage algebra of os_riccati_stage as three v_mfma_f64_16x16x4_f64 per step: the three-product stage of riccati_tile.h
+  // (the tile of the trapezoidal wavefront solver, HsWave<Sys, 1>::riccati_mfma_trap) with the step map Fy | c in the place of
+  // the eliminated collocation rows and the FULL step Hessian Hs | gy as the C operand of the second product (where
+  // Hermite-Simpson feeds its midpoint terms).
   // Own (bound) terms are diagonal here: sigma + delta of the control row of every point, of the state rows at nodes only.
+  // (tile_end_part / tile_update1 are shared; slot map, factors, gain rule and epilogue are written out: behind the shared functions this kernel's private segment grows for nine systems)
   static constexpr bool MFMA_RICCATI = (M == 1 && NU == 1 && NS <= 4);
-  using HW = HsWave<Sys, NodeTraits<Sys>::mlp ? 0 : 1>;      // (only its lane-movement helpers are used; the trapezoidal form of HsWave is not built for network dynamics)
-  typedef double mfma_d4 __attribute__((ext_vector_type(4)));
 #ifndef MYR_SHOOT_RICCATI_PF
 #define MYR_SHOOT_RICCATI_PF 2
 #endif
@@ -517,16 +516,9 @@ struct ShootWave {
         const double G = in[u][1], H0 = in[u][2], H1 = in[u][3], H2 = in[u][4];
 #pragma unroll
         for (int q = 0; q < 5; ++q) { in[u][q] = *ptr[q]; ptr[q] -= stp[q]; }
-        const double sh0 = HW::dpp_row_shr4(X0), sh1 = HW::dpp_row_shr4(X1);
-        mfma_d4 C1;
-        C1[0] = fma(sh0, f_she, X0 * f_keep);
-        C1[1] = fma(sh1, f_she, X1 * f_keep);
-        C1[2] = 0.0; C1[3] = 0.0;
-        const mfma_d4 D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(X0 * f_a1, G, C1, 0, 0, 0);
-        mfma_d4 C2;
-        C2[0] = H0; C2[1] = fma(D3[1], f_t1, H1); C2[2] = fma(D3[2], f_t23, D1[1]) + H2; C2[3] = D3[3] * f_t23;
-        const mfma_d4 D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(G, D1[0], C2, 0, 0, 0);
-        const double q11 = HW::rdlane(D2[2], 8);
+        const TileEnd e = tile_end_part<true>(D3, X0, X1, G, f_a1, f_keep, f_she, f_t1, f_t23, H0, H1, H2);
+        const mfma_d4& D2 = e.D2;
+        const double q11 = rdlane(D2[2], 8);
         const bool bad = !(q11 > reg_floor);                           // wave-uniform, rare (same pivot rule as chol_reg)
         if (bad) {
           ++nreg;
@@ -536,9 +528,7 @@ struct ShootWave {
         const double kk = D2[2] * fast_rcp(d);
         k_ptr[0] = kk;
         k_ptr -= k_step;
-        const double A3 = D2[2] * f_a3;
-        const double B3 = g == 0 ? kk : 0.0;
-        D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(A3, B3, D2, 0, 0, 0);
+        D3 = tile_update1(D2, kk, f_a3, g);
       }
     }
     const double X0 = D3[0], X1 = D3[1], T1 = D3[1], T2 = D3[2], T3 = D3[3];

@@ -163,6 +163,45 @@ def test_lane_kernel_agrees_with_the_wavefront_kernel(monkeypatch, system, rule)
         np.testing.assert_allclose(w["cost"][short], l["cost"][short], rtol=1e-8, atol=1e-10)
 
 
+_EDGE_FORMS = {"fused1": {"MYRIAD_FUSED_WAVES": "1"}, "fused2": {"MYRIAD_FUSED_WAVES": "2"}, "wave1": {"MYRIAD_SOLVE_MODE": "wave1"}}
+_edge_lane = {}      # the lane kernel's results, computed once per (system, rule, N, iteration limit) and shared by the three forms
+
+
+# OPEN (follow-up recorded in profiles/r12_riccati_tile/README.md, "Open: short trapezoidal horizons"): at these three trapezoidal horizons every
+# wavefront form parts from the lane kernel within the first two iterations (relative differences of the iterates 0.07 - 5.9), with the library of the
+# commit before the shared tile as well.  The cause is not known -- it may be code the wavefront forms share (the ring's reads below stage 0, the first
+# point) or the lane kernel.  Left out here only because this test is about the tile sweeps keeping what they computed; put back when it is found.
+_EDGE_OUT = {("VANDERPOL", "TRAPEZOIDAL", 1), ("CARTPOLE", "TRAPEZOIDAL", 2), ("CARTPOLE", "TRAPEZOIDAL", 3)}
+_EDGE_CASES = [(s, r, n, f) for s in ("VANDERPOL", "CARTPOLE") for r in ("HERMITE_SIMPSON", "TRAPEZOIDAL") for n in (1, 2, 3, 4, 5, 8, 9) for f in _EDGE_FORMS
+               if (s, r, n) not in _EDGE_OUT]
+
+
+@pytest.mark.parametrize("system,rule,N,form", _EDGE_CASES, ids=["-".join(map(str, c)) for c in _EDGE_CASES])
+def test_tile_sweeps_at_ring_edge_horizons(monkeypatch, system, rule, N, form):
+  """The matrix-core tile sweeps (csrc/riccati_tile.h) treat whole groups of MYR_RICCATI_PF = 4 stages, a remainder and an empty main loop
+  differently, and the other tests run them at N = 6, 20, 50, 100 only.  Horizons around the ring depth -- fewer stages than the ring has slots, exactly one
+  group, one group and a remainder, two groups, two groups and one -- on a two-state and a four-state system, both rules, B = 3: the fused kernel with
+  one and with two wavefronts (plain sweep and two-level chunks) and round 2's wavefront kernel against the lane kernel's scalar recursion, with the
+  assertions of test_lane_kernel_agrees_with_the_wavefront_kernel: after two iterations the same finiteness pattern and iterates within 1e-7
+  relative; whole solves: equal status and cost to 1e-8 relative on the short ones."""
+  def lane(lim):
+    key = (system, rule, N, lim)
+    if key not in _edge_lane:
+      _edge_lane[key] = _solve(monkeypatch, {"MYRIAD_SOLVE_MODE": "lane"}, system, rule, N, 3, max_iter=lim)
+    return _edge_lane[key]
+  w, l = _solve(monkeypatch, _EDGE_FORMS[form], system, rule, N, 3, max_iter=2), lane(2)
+  fin = np.isfinite(w["xs_and_us"]) & np.isfinite(l["xs_and_us"])
+  d = np.abs(w["xs_and_us"] - l["xs_and_us"])[fin] / np.maximum(1.0, np.abs(l["xs_and_us"])[fin])
+  print(system, rule, N, form, "iterates after 2 iterations: max relative difference", d.max(initial=0.0))
+  assert d.max(initial=0.0) <= 1e-7, (system, rule, N, form, d.max())
+  assert np.array_equal(np.isfinite(w["xs_and_us"]), np.isfinite(l["xs_and_us"]))
+  w, l = _solve(monkeypatch, _EDGE_FORMS[form], system, rule, N, 3), lane(300)
+  short = (w["iters"] <= LONG) & (w["status"] == 0)
+  print(system, rule, N, form, "status", w["status"], l["status"], "iters", w["iters"], l["iters"], "cost", w["cost"], l["cost"])
+  assert np.array_equal(w["status"][short], l["status"][short]), (system, rule, N, form, w["status"], l["status"], w["iters"], l["iters"])
+  np.testing.assert_allclose(w["cost"][short], l["cost"][short], rtol=1e-8, atol=0.0)
+
+
 @pytest.mark.parametrize("rule", ["HERMITE_SIMPSON", "TRAPEZOIDAL"])
 @pytest.mark.parametrize("system", _systems())
 def test_two_phase_launch_returns_the_bits_of_whole_solves(monkeypatch, system, rule):
