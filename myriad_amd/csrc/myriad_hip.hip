@@ -28,6 +28,7 @@
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
+#include "host_stage.h"
 
 // closed-form systems (tools/gen_systems.py): X(NAME) expands once per system; the enum values are MYR_SYS_<NAME>
 #define MYR_CLOSED_FORM_SYSTEMS(X)                                                                               \
@@ -58,16 +59,25 @@ static int fail(int code, const std::string& msg) {
       return fail(MYR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
   } while (0)
 
-struct SysInfo { int ns, nu, np; bool cost_dep_x; };
-static bool sys_info(int id, SysInfo* s) {
+// The one switch over the systems: f(SysTag<Sys>{}) for a closed-form system, for the network system where `node` says so; unknown() for every other id
+// (each caller has its own answer).  A caller names the type as SYS_OF(tag).
+template <class S> struct SysTag { using type = S; };
+#define SYS_OF(tag) typename decltype(tag)::type
+template <class F, class U>
+static auto for_system(int id, bool node, F&& f, U&& unknown) -> decltype(unknown()) {
   switch (id) {
-#define X(N) case MYR_SYS_##N: *s = {Sys##N::NS, Sys##N::NU, Sys##N::NP, Sys##N::COST_DEP_X}; return true;
+#define X(N) case MYR_SYS_##N: return f(SysTag<Sys##N>{});
     MYR_CLOSED_FORM_SYSTEMS(X)
 #undef X
-    case MYR_SYS_NODE_CARTPOLE: *s = {SysNODE_CARTPOLE::NS, SysNODE_CARTPOLE::NU, SysNODE_CARTPOLE::NP, SysNODE_CARTPOLE::COST_DEP_X}; return true;
-    case MYR_SYS_INVASIVEPLANT: *s = {DiscINVASIVEPLANT::NS, DiscINVASIVEPLANT::NU, DiscINVASIVEPLANT::NP, false}; return true;   // myr_fbsm only
+    case MYR_SYS_NODE_CARTPOLE: if (node) return f(SysTag<SysNODE_CARTPOLE>{}); break;
   }
-  return false;
+  return unknown();
+}
+
+struct SysInfo { int ns, nu, np; bool cost_dep_x; };
+static bool sys_info(int id, SysInfo* s) {
+  if (id == MYR_SYS_INVASIVEPLANT) { *s = {DiscINVASIVEPLANT::NS, DiscINVASIVEPLANT::NU, DiscINVASIVEPLANT::NP, false}; return true; }   // myr_fbsm only
+  return for_system(id, true, [&](auto t) { using S = SYS_OF(t); *s = {S::NS, S::NU, S::NP, S::COST_DEP_X}; return true; }, [] { return false; });
 }
 
 struct KTimer {
@@ -212,6 +222,30 @@ static int ensure_buf(void** buf, size_t* have, size_t need) {
   return MYR_OK;
 }
 
+// Stage (host_stage.h) on the HIP runtime: the arrays of one call in one of the handle's growing buffers, copies on the handle's stream
+struct HipStage {
+  myr_handle h; void** buf; size_t* have;
+  int grow(size_t need, void** base) { const int rc = ensure_buf(buf, have, need); *base = *buf; return rc; }
+  int upload(void* dev, const void* host, size_t bytes) { HIPCHK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream)); return MYR_OK; }
+  int download(void* host, const void* dev, size_t bytes) { HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream)); return MYR_OK; }
+  int sync() { HIPCHK(hipStreamSynchronize(h->stream)); return MYR_OK; }
+};
+using DevStage = Stage<HipStage>;
+// the arrays of a C-ABI call of memory kind `mem`, in dbuf
+static DevStage call_stage(myr_handle h, int mem) { return DevStage(HipStage{h, &h->dbuf, &h->dbuf_bytes}, mem == MYR_MEM_HOST); }
+// device scratch of a launcher in `buf`: scratch items only
+static DevStage scratch_stage(myr_handle h, void** buf, size_t* have) { return DevStage(HipStage{h, buf, have}, false); }
+
+// grid of an elementwise kernel with a grid-stride loop, 256 threads per workgroup: one thread per element up to 64 workgroups per CU
+static unsigned grid_for(long total) { long b = (total + 255) / 256; if (b > 16384) b = 16384; if (b < 1) b = 1; return (unsigned)b; }
+// leading dimension of a batch-minor array: whole wavefronts of 64 lanes, an ODD number of them, so that consecutive elements of a trajectory
+// (stride Bp * 8 bytes) rotate over the HBM channels / L2 sets instead of camping on one (a power-of-two stride would)
+static long padded_lanes(int B) {
+  long Bp = ((long)B + 63) / 64 * 64;
+  if (((Bp / 64) & 1) == 0) Bp += 64;
+  return Bp;
+}
+
 // ---- the steps the launchers share -----------------------------------------------------------------------------------------
 // A timed launch on KTimer slot `k` (MYR_K_*): timed_begin -- the test fills, then the start event -- directly in front of the kernels,
 // timed_end behind them.  A launcher that has work between the stop event and the account calls the parts of timed_end itself.
@@ -265,12 +299,33 @@ static void set_plan(myr_handle h, int form, int waves, int k1, int phases, int 
   if (!h->plan_frozen) memcpy(h->plan, pl, sizeof(pl));      // (second starts re-launch on this handle: they leave the first attempt's record alone)
 }
 
+// ---- one record per entry point: the batch in device memory, as the launchers see it ------------------------------------------
+struct EvalArgs { int B; const double *z, *params; int pstride; double *f, *g, *c, *j; };      // each output may be null
+enum { PRODOP_VJP = 0, PRODOP_JVP = 1, PRODOP_EXGD = 2 };
+struct ProdArgs {
+  int op, B;
+  const double *z, *w, *params; int pstride;     // w: lam (vjp) or v (jvp)
+  double* out; int add_gradf;
+  double *zio, *lamio; const double *lb, *ub; double eta_x, eta_v; int nsteps;   // exgd
+};
+struct SolveCall {
+  int B; double* z; const double *lb, *ub, *params; int pstride; myr_solve_opts so;
+  double *lam, *cost; int32_t *status, *iters; double* kkt;      // each may be null
+};
+struct RolloutArgs { int B, num_steps, u_rows; const double *x0, *us, *params; int pstride; double *xs, *cost; };      // xs, cost may be null
+struct FitArgs {      // xh: [num_steps+1][NS][Bp] state scratch; loss [B] or null; grad [B][NP] rows
+  int B; long Bp; int num_steps, u_rows; const double *xs_obs, *us, *wt, *params; int pstride; double *xh, *loss, *grad;
+};
+struct FbsmArgs {      // X, A [N+1][NS][Bp], U [N+1 | N][NU][Bp]: batch-minor
+  int B; long Bp; int N; const double *x0, *adjT, *params; int pstride; VarScale lo, hi; double bang, delta; int max_sweeps;
+  double *X, *U, *A; int32_t* sweeps;
+};
+
 // ------------------------------------------------------------------------------------------------
 // eval
 // ------------------------------------------------------------------------------------------------
 template <class Sys, int SCHEME>
-static int launch_hs_eval(myr_handle h, int B, const double* z, const double* params, int pstride,
-                          double* f, double* g, double* c, double* j) {
+static int launch_hs_eval(myr_handle h, const EvalArgs& a) {
   const int N = h->d.intervals;
   const double hstep = h->d.T / N;
   int wpt = h->eval_wpt;
@@ -291,7 +346,7 @@ static int launch_hs_eval(myr_handle h, int B, const double* z, const double* pa
       h->eval_attr_lds[(W == 1 ? 0 : (W == 4 ? 1 : 2)) + (NTV ? 3 : 0)] = 1;                                     \
     }                                                                                                             \
     if (int rc = timed_begin(h, MYR_K_EVAL)) return rc;                                                           \
-    hipLaunchKernelGGL(kern, dim3(B), dim3(64 * W), lds, h->stream, N, hstep, z, params, pstride, f, g, c, j);    \
+    hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * W), lds, h->stream, N, hstep, a.z, a.params, a.pstride, a.f, a.g, a.c, a.j); \
   }
   const bool nt = h->eval_nt != 0;
   switch (wpt) {
@@ -304,33 +359,31 @@ static int launch_hs_eval(myr_handle h, int B, const double* z, const double* pa
 }
 
 template <class Sys>
-static int launch_shoot_eval(myr_handle h, int B, const double* z, const double* params, int pstride,
-                             double* f, double* g, double* c, double* j) {
-  const int I = h->d.intervals, cpi = h->d.controls_per_interval, method = h->d.integration_method;
+static int launch_shoot_eval(myr_handle h, const EvalArgs& a) {
+  const int I = h->d.intervals, cpi = h->d.controls_per_interval, method = h->d.integration_method, B = a.B;
   if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, (size_t)B * (size_t)(cpi + 1) * Sys::NS * 8)) return rc;
   if (int rc = timed_begin(h, MYR_K_EVAL)) return rc;
   if (method == MYR_INT_RK4)
     hipLaunchKernelGGL((shoot_eval_kernel<Sys, 2>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, I, cpi, method, h->d.T,
-                       z, params, pstride, f, g, c, j, (double*)h->sbuf, (const double*)nullptr, 1);
+                       a.z, a.params, a.pstride, a.f, a.g, a.c, a.j, (double*)h->sbuf, (const double*)nullptr, 1);
   else
     hipLaunchKernelGGL((shoot_eval_kernel<Sys, 1>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, I, cpi, method, h->d.T,
-                       z, params, pstride, f, g, c, j, (double*)h->sbuf, (const double*)nullptr, 1);
+                       a.z, a.params, a.pstride, a.f, a.g, a.c, a.j, (double*)h->sbuf, (const double*)nullptr, 1);
   return timed_end(h, MYR_K_EVAL);
 }
 
 template <class Sys>
-int eval_for_system(myr_handle h, int B, const double* z, const double* params, int pstride,
-                           double* f, double* g, double* c, double* j) {
+int eval_for_system(myr_handle h, const EvalArgs& a) {
   if constexpr (Sys::PARAMS_BY_POINTER) {   // neural-ODE systems: Hermite-Simpson (config 5) and shooting (the reference's default route for a NodeSystem,
                                             // config.py:66 + shooting.py:144-167, 212-228); its parametrised trapezoid is dead code (trapezoidal.py:204-206, quirk Q8)
-    if (h->d.transcription == MYR_TR_SHOOTING) return launch_shoot_eval<Sys>(h, B, z, params, pstride, f, g, c, j);
+    if (h->d.transcription == MYR_TR_SHOOTING) return launch_shoot_eval<Sys>(h, a);
     if (h->d.transcription != MYR_TR_HERMITE_SIMPSON) return fail(MYR_E_UNSUPPORTED, "myr_eval: NODE systems are built for HERMITE_SIMPSON and SHOOTING");
-    return launch_hs_eval<Sys, EVAL_HS>(h, B, z, params, pstride, f, g, c, j);
+    return launch_hs_eval<Sys, EVAL_HS>(h, a);
   } else {
     switch (h->d.transcription) {
-      case MYR_TR_HERMITE_SIMPSON: return launch_hs_eval<Sys, EVAL_HS>(h, B, z, params, pstride, f, g, c, j);
-      case MYR_TR_TRAPEZOIDAL: return launch_hs_eval<Sys, EVAL_TRAP>(h, B, z, params, pstride, f, g, c, j);
-      case MYR_TR_SHOOTING: return launch_shoot_eval<Sys>(h, B, z, params, pstride, f, g, c, j);
+      case MYR_TR_HERMITE_SIMPSON: return launch_hs_eval<Sys, EVAL_HS>(h, a);
+      case MYR_TR_TRAPEZOIDAL: return launch_hs_eval<Sys, EVAL_TRAP>(h, a);
+      case MYR_TR_SHOOTING: return launch_shoot_eval<Sys>(h, a);
     }
   }
   return fail(MYR_E_ARG, "eval: unknown transcription");
@@ -339,18 +392,6 @@ int eval_for_system(myr_handle h, int B, const double* z, const double* params, 
 // ------------------------------------------------------------------------------------------------
 // Lagrangian products and the extragradient step (collocation transcriptions)
 // ------------------------------------------------------------------------------------------------
-enum { PRODOP_VJP = 0, PRODOP_JVP = 1, PRODOP_EXGD = 2 };
-struct ProdArgs {
-  int op, B;
-  const double *z, *w, *params; int pstride;     // w: lam (vjp) or v (jvp)
-  double* out; int add_gradf;
-  double *zio, *lamio; const double *lb, *ub; double eta_x, eta_v; int nsteps;   // exgd
-};
-struct SolveCall {      // one batch in device memory, as the solver launchers see it
-  int B; double* z; const double *lb, *ub, *params; int pstride; myr_solve_opts so;
-  double *lam, *cost; int32_t *status, *iters; double* kkt;      // each may be null
-};
-
 template <class Sys, int SCHEME>
 static int launch_products(myr_handle h, const ProdArgs& a) {
   const int N = h->d.intervals;
@@ -366,13 +407,12 @@ static int launch_products(myr_handle h, const ProdArgs& a) {
                        a.params, a.pstride, a.eta_x, a.eta_v, a.nsteps);
   } else {
     const long units = (long)a.B * (a.op == PRODOP_VJP ? P::points(N) : N);
-    long blocks = (units + 255) / 256;
-    if (blocks > 256L * 64) blocks = 256L * 64;       // grid-stride beyond 64 workgroups per CU
+    const unsigned blocks = grid_for(units);
     if (a.op == PRODOP_VJP)
-      hipLaunchKernelGGL((colloc_vjp_kernel<Sys, SCHEME>), dim3((unsigned)blocks), dim3(256), 0, h->stream, a.B, N, hstep, a.z, a.w,
+      hipLaunchKernelGGL((colloc_vjp_kernel<Sys, SCHEME>), dim3(blocks), dim3(256), 0, h->stream, a.B, N, hstep, a.z, a.w,
                          a.params, a.pstride, a.out, a.add_gradf);
     else
-      hipLaunchKernelGGL((colloc_jvp_kernel<Sys, SCHEME>), dim3((unsigned)blocks), dim3(256), 0, h->stream, a.B, N, hstep, a.z, a.w,
+      hipLaunchKernelGGL((colloc_jvp_kernel<Sys, SCHEME>), dim3(blocks), dim3(256), 0, h->stream, a.B, N, hstep, a.z, a.w,
                          a.params, a.pstride, a.out);
   }
   return timed_end(h, MYR_K_PROD);
@@ -398,14 +438,14 @@ static int launch_shoot_products_m(myr_handle h, const ProdArgs& a) {
   } else {
     double* g = scr + sweep / 8; double* zbar = g + (size_t)a.B * dm.n; double* cbuf = zbar + (size_t)a.B * dm.n;
     const long tz = (long)a.B * dm.n, tl = (long)a.B * dm.m;
-    long ub_ = (tz + 255) / 256; if (ub_ > 16384) ub_ = 16384;
+    const unsigned ub_ = grid_for(tz);
     for (int s = 0; s < a.nsteps; ++s) {
       hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, (const double*)a.zio, a.params, a.pstride,
                          (double*)nullptr, g, (double*)nullptr, (double*)nullptr, scr, (const double*)a.lamio, 1);
-      hipLaunchKernelGGL(exgd_update_kernel, dim3((unsigned)ub_), dim3(256), 0, h->stream, tz, (const double*)a.zio, (const double*)g, a.lb, a.ub, a.eta_x, zbar);
+      hipLaunchKernelGGL(exgd_update_kernel, dim3(ub_), dim3(256), 0, h->stream, tz, (const double*)a.zio, (const double*)g, a.lb, a.ub, a.eta_x, zbar);
       hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, (const double*)zbar, a.params, a.pstride,
                          (double*)nullptr, g, (double*)nullptr, (double*)nullptr, scr, (const double*)a.lamio, 1);
-      hipLaunchKernelGGL(exgd_update_kernel, dim3((unsigned)ub_), dim3(256), 0, h->stream, tz, (const double*)a.zio, (const double*)g, a.lb, a.ub, a.eta_x, a.zio);
+      hipLaunchKernelGGL(exgd_update_kernel, dim3(ub_), dim3(256), 0, h->stream, tz, (const double*)a.zio, (const double*)g, a.lb, a.ub, a.eta_x, a.zio);
       hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, (const double*)a.zio, a.params, a.pstride,
                          (double*)nullptr, (double*)nullptr, cbuf, (double*)nullptr, scr, (const double*)nullptr, 1);
       hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, h->stream, tl, a.eta_v, (const double*)cbuf, a.lamio);
@@ -823,10 +863,7 @@ template <class Core, class Sys>
 static int launch_lane_solve(myr_handle h, const SolveCall& a, long nst) {
   const myr_dims& dm = h->dims;
   const int B = a.B;
-  // batch-minor leading dimension: a multiple of 64 lanes, but an ODD multiple so that consecutive elements of a
-  // trajectory (stride Bp*8 bytes) rotate over HBM channels / L2 sets instead of camping on one (power-of-two stride)
-  long Bp = ((long)B + 63) / 64 * 64;
-  if (((Bp / 64) & 1) == 0) Bp += 64;
+  const long Bp = padded_lanes(B);
   const long n = dm.n, m = dm.m;
   if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, (size_t)Bp * (size_t)(6 * n + m + nst) * 8)) return rc;
   double* sz = (double*)h->sbuf;
@@ -964,56 +1001,50 @@ void rollout_kernel(int B, int method, int num_steps, double h, int u_rows, cons
 // batched Forward-Backward Sweep (indirect method)
 // ------------------------------------------------------------------------------------------------
 template <class Sys>
-int launch_fbsm(myr_handle h, int B, long Bp, int N, const double* x0, const double* adjT, const double* params, int pstride,
-                       const VarScale& lo, const VarScale& hi, double bang, double delta, int max_sweeps, double* X, double* U, double* A, int32_t* sweeps) {
+int launch_fbsm(myr_handle h, const FbsmArgs& a) {
   if constexpr (!Indirect<Sys>::SUPPORTED) {
     return fail(MYR_E_UNSUPPORTED, "myr_fbsm: this system has no adjoint dynamics (not an IndirectFHCS on the path)");
   } else {
     if (int rc = timed_begin(h, MYR_K_FBSM)) return rc;
-    hipLaunchKernelGGL(fbsm_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, Bp, N, h->d.T, x0, adjT, params,
-                       pstride, lo, hi, bang, delta, max_sweeps, X, U, A, sweeps);
+    hipLaunchKernelGGL(fbsm_kernel<Sys>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, h->stream, a.B, a.Bp, a.N, h->d.T, a.x0, a.adjT, a.params,
+                       a.pstride, a.lo, a.hi, a.bang, a.delta, a.max_sweeps, a.X, a.U, a.A, a.sweeps);
     return timed_end(h, MYR_K_FBSM);
   }
 }
 
 template <class Sys>
-int rollout_for_system(myr_handle h, int B, int num_steps, int u_rows, const double* x0, const double* us, const double* params,
-                       int pstride, double* xs, double* cost) {
-  hipLaunchKernelGGL(rollout_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, (int)h->d.integration_method, num_steps,
-                     h->d.T / num_steps, u_rows, x0, us, params, pstride, xs, cost);
+int rollout_for_system(myr_handle h, const RolloutArgs& a) {
+  hipLaunchKernelGGL(rollout_kernel<Sys>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, h->stream, a.B, (int)h->d.integration_method, a.num_steps,
+                     h->d.T / a.num_steps, a.u_rows, a.x0, a.us, a.params, a.pstride, a.xs, a.cost);
   return MYR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
 // trajectory-matching loss and its parameter gradient (fit.h: fit_lane_kernel, node_fit_kernel)
 // ------------------------------------------------------------------------------------------------
-// xh: [num_steps+1][NS][Bp] state scratch; loss [B] or null; grad [B][NP] rows
 template <class Sys>
-int fit_for_system(myr_handle h, int B, long Bp, int num_steps, int u_rows, const double* xs_obs, const double* us, const double* wt,
-                   const double* params, int pstride, double* xh, double* loss, double* grad) {
+int fit_for_system(myr_handle h, const FitArgs& a) {
   if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // shared weights only (myr_fit_grad has checked): one wavefront per trajectory
-    (void)pstride;
-    hipLaunchKernelGGL(node_fit_kernel<NodeFit>, dim3((unsigned)((B + NodeFit::WPB - 1) / NodeFit::WPB)), dim3(64 * NodeFit::WPB), 0, h->stream, B, Bp,
-                       (int)h->d.integration_method, num_steps, h->d.T / num_steps, u_rows, xs_obs, us, wt, params, xh, loss, grad);
+    hipLaunchKernelGGL(node_fit_kernel<NodeFit>, dim3((unsigned)((a.B + NodeFit::WPB - 1) / NodeFit::WPB)), dim3(64 * NodeFit::WPB), 0, h->stream, a.B, a.Bp,
+                       (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.xh, a.loss, a.grad);
     return MYR_OK;
   } else if constexpr (!SysDp<Sys>::SUPPORTED) {
     return fail(MYR_E_UNSUPPORTED, std::string("myr_fit_grad: no parameter derivatives are generated for ") + Sys::NAME);
   } else {
-    hipLaunchKernelGGL(fit_lane_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, Bp, (int)h->d.integration_method, num_steps,
-                       h->d.T / num_steps, u_rows, xs_obs, us, wt, params, pstride, xh, loss, grad);
+    hipLaunchKernelGGL(fit_lane_kernel<Sys>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, h->stream, a.B, a.Bp, (int)h->d.integration_method, a.num_steps,
+                       h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.pstride, a.xh, a.loss, a.grad);
     return MYR_OK;
   }
 }
 
 // ---- per-system entry points: explicit instantiation (system objects) / extern declaration (main object) -----------------
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
-  LINK template int eval_for_system<S>(myr_handle, int, const double*, const double*, int, double*, double*, double*, double*);   \
-  LINK template int products_for_system<S>(myr_handle, const ProdArgs&);                                                          \
-  LINK template int solve_for_system<S>(myr_handle, const SolveCall&);                                                            \
-  LINK template int rollout_for_system<S>(myr_handle, int, int, int, const double*, const double*, const double*, int, double*, double*); \
-  LINK template int fit_for_system<S>(myr_handle, int, long, int, int, const double*, const double*, const double*, const double*, int, double*, double*, double*); \
-  LINK template int launch_fbsm<S>(myr_handle, int, long, int, const double*, const double*, const double*, int, const VarScale&,  \
-                                   const VarScale&, double, double, int, double*, double*, double*, int32_t*);
+  LINK template int eval_for_system<S>(myr_handle, const EvalArgs&);          \
+  LINK template int products_for_system<S>(myr_handle, const ProdArgs&);      \
+  LINK template int solve_for_system<S>(myr_handle, const SolveCall&);        \
+  LINK template int rollout_for_system<S>(myr_handle, const RolloutArgs&);    \
+  LINK template int fit_for_system<S>(myr_handle, const FitArgs&);            \
+  LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
 // a system's object in parts (the build splits the slow ones): -DMYR_TU_PART=1 the Hermite-Simpson wavefront solvers and the dispatch, 3 the trapezoidal
 // wavefront solvers, 4 the shooting solvers, 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
@@ -1030,12 +1061,11 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, 
 template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, const SolveCall&);
 #else
 #define MYR_SYSTEM_ENTRY_POINTS_REST(S)                                                                                            \
-  template int eval_for_system<S>(myr_handle, int, const double*, const double*, int, double*, double*, double*, double*);         \
-  template int products_for_system<S>(myr_handle, const ProdArgs&);                                                                \
-  template int rollout_for_system<S>(myr_handle, int, int, int, const double*, const double*, const double*, int, double*, double*); \
-  template int fit_for_system<S>(myr_handle, int, long, int, int, const double*, const double*, const double*, const double*, int, double*, double*, double*); \
-  template int launch_fbsm<S>(myr_handle, int, long, int, const double*, const double*, const double*, int, const VarScale&,        \
-                              const VarScale&, double, double, int, double*, double*, double*, int32_t*);
+  template int eval_for_system<S>(myr_handle, const EvalArgs&);               \
+  template int products_for_system<S>(myr_handle, const ProdArgs&);           \
+  template int rollout_for_system<S>(myr_handle, const RolloutArgs&);         \
+  template int fit_for_system<S>(myr_handle, const FitArgs&);                 \
+  template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 MYR_SYSTEM_ENTRY_POINTS_REST(myriad::MYR_TU_SYSTEM)
 #endif
 #elif defined(MYR_TU_SYSTEM)
@@ -1198,112 +1228,86 @@ extern "C" int myr_kernel_time_reset(myr_handle h) {
 
 // systems without a direct-transcription path: INVASIVEPLANT is discrete-time (the reference refuses it in its direct
 // optimisers too, trajectory_optimizers/base.py:66-67) and only has the discrete FBSM
+static int arg_fail(const char* who, int code, const char* what) { return fail(code, std::string(who) + ": " + what); }
 static int no_such_path(myr_handle h, const char* who) {
   if (h->d.system_id == MYR_SYS_INVASIVEPLANT)
-    return fail(MYR_E_UNSUPPORTED, std::string(who) + ": INVASIVEPLANT is a discrete-time system; only myr_fbsm is available for it");
-  return fail(MYR_E_ARG, std::string(who) + ": unknown system");
+    return arg_fail(who, MYR_E_UNSUPPORTED, "INVASIVEPLANT is a discrete-time system; only myr_fbsm is available for it");
+  return arg_fail(who, MYR_E_ARG, "unknown system");
 }
 
-// carves of the host-call staging buffer (dbuf) and of the restoration buffers, in doubles: every carve keeps 16-byte alignment
-static size_t al(size_t v) { return (v + 1) & ~(size_t)1; }
+// ---- the argument checks the entry points share: one text each; every entry point makes them in its own order ------------------
+static int check_batch(const char* who, int B) { return B < 0 ? arg_fail(who, MYR_E_ARG, "negative batch") : MYR_OK; }
+static int check_stride(myr_handle h, const char* who, const double* params, int stride) {
+  return params && stride != 0 && stride != h->dims.np ? arg_fail(who, MYR_E_ARG, "params_stride must be 0 (shared) or np") : MYR_OK;
+}
+static int check_node_weights(myr_handle h, const char* who, const double* params) {
+  return !params && h->d.system_id == MYR_SYS_NODE_CARTPOLE ? arg_fail(who, MYR_E_ARG, "a NODE system needs its weights in `params`") : MYR_OK;
+}
+static int check_mem(const char* who, int mem) { return mem != MYR_MEM_HOST && mem != MYR_MEM_DEVICE ? arg_fail(who, MYR_E_ARG, "bad mem kind") : MYR_OK; }
+// doubles behind `params`: none, one shared set, or a set per instance
+static size_t n_params(myr_handle h, const double* params, int stride, int B) { return params ? (stride ? (size_t)B * h->dims.np : (size_t)h->dims.np) : 0; }
 
-static int dispatch_eval(myr_handle h, int B, const double* z, const double* params, int pstride,
-                         double* f, double* g, double* c, double* j) {
-  switch (h->d.system_id) {
-#define X(N) case MYR_SYS_##N: return eval_for_system<Sys##N>(h, B, z, params, pstride, f, g, c, j);
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-    case MYR_SYS_NODE_CARTPOLE: return eval_for_system<SysNODE_CARTPOLE>(h, B, z, params, pstride, f, g, c, j);
-  }
-  return no_such_path(h, "eval");
+static int dispatch_eval(myr_handle h, const EvalArgs& a) {
+  return for_system(h->d.system_id, true, [&](auto t) { return eval_for_system<SYS_OF(t)>(h, a); }, [&] { return no_such_path(h, "eval"); });
 }
 
 extern "C" int myr_eval(myr_handle h, int32_t B, const double* z, const double* params, int32_t params_stride,
                         double* f, double* gradf, double* c, double* jblk, int32_t mem) {
+  const char* who = "myr_eval";
   if (!h || !z) return fail(MYR_E_ARG, "myr_eval: null handle or z");
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, "myr_eval");
-  if (B < 0) return fail(MYR_E_ARG, "myr_eval: negative batch");
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
+  if (int rc = check_batch(who, B)) return rc;
   if (B == 0) return MYR_OK;
-  if (params && params_stride != 0 && params_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_eval: params_stride must be 0 (shared) or np");
-  if (!params && h->d.system_id == MYR_SYS_NODE_CARTPOLE) return fail(MYR_E_ARG, "myr_eval: a NODE system needs its weights in `params`");
+  if (int rc = check_stride(h, who, params, params_stride)) return rc;
+  if (int rc = check_node_weights(h, who, params)) return rc;
   HIPCHK(hipSetDevice(h->d.device));
+  if (int rc = check_mem(who, mem)) return rc;
   const myr_dims& dm = h->dims;
-  if (mem == MYR_MEM_DEVICE) return dispatch_eval(h, B, z, params, params_stride, f, gradf, c, jblk);
-  if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_eval: bad mem kind");
-  // host pointers: stage through device scratch
-  const size_t nz = (size_t)B * dm.n, npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  const size_t nf = f ? (size_t)B : 0, ng = gradf ? (size_t)B * dm.ngrad : 0;
-  const size_t nc = c ? (size_t)B * dm.m : 0, nj = jblk ? (size_t)B * dm.jblk : 0;
-  const size_t total = al(nz) + al(npar) + al(nf) + al(ng) + al(nc) + al(nj);
-  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * 8);
-  if (rc) return rc;
-  double* dz = (double*)h->dbuf;
-  double* dp = dz + al(nz);
-  double* df = dp + al(npar);
-  double* dg = df + al(nf);
-  double* dc = dg + al(ng);
-  double* dj = dc + al(nc);
-  HIPCHK(hipMemcpyAsync(dz, z, nz * 8, hipMemcpyHostToDevice, h->stream));
-  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  rc = dispatch_eval(h, B, dz, npar ? dp : nullptr, params_stride, nf ? df : nullptr, ng ? dg : nullptr,
-                     nc ? dc : nullptr, nj ? dj : nullptr);
-  if (rc) return rc;
-  if (nf) HIPCHK(hipMemcpyAsync(f, df, nf * 8, hipMemcpyDeviceToHost, h->stream));
-  if (ng) HIPCHK(hipMemcpyAsync(gradf, dg, ng * 8, hipMemcpyDeviceToHost, h->stream));
-  if (nc) HIPCHK(hipMemcpyAsync(c, dc, nc * 8, hipMemcpyDeviceToHost, h->stream));
-  if (nj) HIPCHK(hipMemcpyAsync(jblk, dj, nj * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return MYR_OK;
+  const size_t nB = (size_t)B;
+  EvalArgs a{B, nullptr, nullptr, params_stride, nullptr, nullptr, nullptr, nullptr};
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nB * dm.n);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.out(a.f, f, nB);
+  st.out(a.g, gradf, nB * dm.ngrad);
+  st.out(a.c, c, nB * dm.m);
+  st.out(a.j, jblk, nB * dm.jblk);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_eval(h, a)) return rc;
+  return st.finish();
 }
 
 static int dispatch_products(myr_handle h, const ProdArgs& a) {
-  switch (h->d.system_id) {
-#define X(N) case MYR_SYS_##N: return products_for_system<Sys##N>(h, a);
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-    case MYR_SYS_NODE_CARTPOLE: return products_for_system<SysNODE_CARTPOLE>(h, a);
-  }
-  return no_such_path(h, "products");
+  return for_system(h->d.system_id, true, [&](auto t) { return products_for_system<SYS_OF(t)>(h, a); }, [&] { return no_such_path(h, "products"); });
 }
 
 static int check_products_args(myr_handle h, const char* who, int32_t B, const void* p0, const void* p1, const void* p2,
                                const double* params, int32_t params_stride) {
-  if (!h || !p0 || !p1 || !p2) return fail(MYR_E_ARG, std::string(who) + ": null handle or array");
+  if (!h || !p0 || !p1 || !p2) return arg_fail(who, MYR_E_ARG, "null handle or array");
   if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
-  if (B < 0) return fail(MYR_E_ARG, std::string(who) + ": negative batch");
-  if (params && params_stride != 0 && params_stride != h->dims.np)
-    return fail(MYR_E_ARG, std::string(who) + ": params_stride must be 0 (shared) or np");
-  if (!params && h->d.system_id == MYR_SYS_NODE_CARTPOLE) return fail(MYR_E_ARG, std::string(who) + ": a NODE system needs its weights in `params`");
-  return MYR_OK;
+  if (int rc = check_batch(who, B)) return rc;
+  if (int rc = check_stride(h, who, params, params_stride)) return rc;
+  return check_node_weights(h, who, params);
 }
 
 // one implementation for J^T lam / grad L (in_w = m, out = n) and J v (in_w = n, out = m)
 static int products_call(myr_handle h, int op, const char* who, int32_t B, const double* z, const double* w, const double* params,
                          int32_t params_stride, double* out, int32_t add_gradf, int32_t mem) {
-  int rc = check_products_args(h, who, B, z, w, out, params, params_stride);
-  if (rc) return rc;
+  if (int rc = check_products_args(h, who, B, z, w, out, params, params_stride)) return rc;
   if (B == 0) return MYR_OK;
   HIPCHK(hipSetDevice(h->d.device));
+  if (int rc = check_mem(who, mem)) return rc;
   const myr_dims& dm = h->dims;
   ProdArgs a{};
   a.op = op; a.B = B; a.pstride = params_stride; a.add_gradf = add_gradf;
-  if (mem == MYR_MEM_DEVICE) { a.z = z; a.w = w; a.params = params; a.out = out; return dispatch_products(h, a); }
-  if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, std::string(who) + ": bad mem kind");
-  const size_t nz = (size_t)B * dm.n, nw = (size_t)B * (op == PRODOP_VJP ? dm.m : dm.n), no = (size_t)B * (op == PRODOP_VJP ? dm.n : dm.m);
-  const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nz) + al(nw) + al(no) + al(npar)) * 8);
-  if (rc) return rc;
-  double* dz = (double*)h->dbuf; double* dw = dz + al(nz); double* dout = dw + al(nw); double* dp = dout + al(no);
-  HIPCHK(hipMemcpyAsync(dz, z, nz * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dw, w, nw * 8, hipMemcpyHostToDevice, h->stream));
-  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  a.z = dz; a.w = dw; a.params = npar ? dp : nullptr; a.out = dout;
-  rc = dispatch_products(h, a);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, dout, no * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return MYR_OK;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, (size_t)B * dm.n);
+  st.in(a.w, w, (size_t)B * (op == PRODOP_VJP ? dm.m : dm.n));
+  st.out(a.out, out, (size_t)B * (op == PRODOP_VJP ? dm.n : dm.m));
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_products(h, a)) return rc;
+  return st.finish();
 }
 
 extern "C" int myr_vjp(myr_handle h, int32_t B, const double* z, const double* lam, const double* params, int32_t params_stride,
@@ -1318,44 +1322,28 @@ extern "C" int myr_jvp(myr_handle h, int32_t B, const double* z, const double* v
 
 extern "C" int myr_exgd(myr_handle h, int32_t B, double* z, double* lam, const double* lb, const double* ub, const double* params,
                         int32_t params_stride, double eta_x, double eta_v, int32_t nsteps, int32_t mem) {
-  int rc = check_products_args(h, "myr_exgd", B, z, lam, lb, params, params_stride);
-  if (rc) return rc;
+  if (int rc = check_products_args(h, "myr_exgd", B, z, lam, lb, params, params_stride)) return rc;
   if (!ub) return fail(MYR_E_ARG, "myr_exgd: null ub");
   if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd: negative nsteps");
   if (B == 0 || nsteps == 0) return MYR_OK;
   HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
+  if (int rc = check_mem("myr_exgd", mem)) return rc;
+  const size_t nz = (size_t)B * h->dims.n;
   ProdArgs a{};
   a.op = PRODOP_EXGD; a.B = B; a.pstride = params_stride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
-  if (mem == MYR_MEM_DEVICE) { a.zio = z; a.lamio = lam; a.lb = lb; a.ub = ub; a.params = params; return dispatch_products(h, a); }
-  if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_exgd: bad mem kind");
-  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
-  const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (3 * al(nz) + al(nl) + al(npar)) * 8);
-  if (rc) return rc;
-  double* dz = (double*)h->dbuf; double* dlb = dz + al(nz); double* dub = dlb + al(nz); double* dl = dub + al(nz); double* dp = dl + al(nl);
-  HIPCHK(hipMemcpyAsync(dz, z, nz * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dlb, lb, nz * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dub, ub, nz * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dl, lam, nl * 8, hipMemcpyHostToDevice, h->stream));
-  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  a.zio = dz; a.lamio = dl; a.lb = dlb; a.ub = dub; a.params = npar ? dp : nullptr;
-  rc = dispatch_products(h, a);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(z, dz, nz * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(lam, dl, nl * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return MYR_OK;
+  DevStage st = call_stage(h, mem);
+  st.inout(a.zio, z, nz);
+  st.in(a.lb, lb, nz);
+  st.in(a.ub, ub, nz);
+  st.inout(a.lamio, lam, (size_t)B * h->dims.m);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_products(h, a)) return rc;
+  return st.finish();
 }
 
 static int dispatch_solve(myr_handle h, const SolveCall& a) {
-  switch (h->d.system_id) {
-#define X(N) case MYR_SYS_##N: return solve_for_system<Sys##N>(h, a);
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-    case MYR_SYS_NODE_CARTPOLE: return solve_for_system<SysNODE_CARTPOLE>(h, a);
-  }
-  return no_such_path(h, "solve");
+  return for_system(h->d.system_id, true, [&](auto t) { return solve_for_system<SYS_OF(t)>(h, a); }, [&] { return no_such_path(h, "solve"); });
 }
 
 // ---- variable scaling of the solve path ----------------------------------------------------------------------
@@ -1392,13 +1380,13 @@ static int dispatch_solve_scaled(myr_handle h, const SolveCall& a) {
   scaled.lb = lbs; scaled.ub = ubs;
   const long tz = (long)a.B * dm.n, tl = a.lam ? (long)a.B * dm.m : 0;
   const int xcount = dm.x_rows * dm.ns;
-  long blocks = (tz + 255) / 256; if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(scale_in_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, dm.n, xcount, dm.ns, dm.nu, h->vscale, a.z, a.lb, a.ub, lbs, ubs);
+  const unsigned blocks = grid_for(tz);
+  hipLaunchKernelGGL(scale_in_kernel, dim3(blocks), dim3(256), 0, h->stream, tz, dm.n, xcount, dm.ns, dm.nu, h->vscale, a.z, a.lb, a.ub, lbs, ubs);
   HIPCHK(hipGetLastError());
   int rc = dispatch_solve(h, scaled);
   // unscale even after a failed launch sequence is pointless: return the error as is
   if (rc) return rc;
-  hipLaunchKernelGGL(scale_out_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, tl, dm.n, xcount, dm.ns, dm.nu, dm.m, h->vscale, a.z, a.lam);
+  hipLaunchKernelGGL(scale_out_kernel, dim3(blocks), dim3(256), 0, h->stream, tz, tl, dm.n, xcount, dm.ns, dm.nu, dm.m, h->vscale, a.z, a.lam);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   return MYR_OK;
@@ -1414,8 +1402,7 @@ static int dispatch_solve_scaled(myr_handle h, const SolveCall& a) {
 // Host logic over device arrays: the failed rows are gathered into a working set, solved, and scattered back where they converged.
 // (Rounds 2-3 had this in the Python host only: myriad_amd/trajectory_optimizers/__init__.py, removed in round 4.)
 // ------------------------------------------------------------------------------------------------------------------------------
-static int dispatch_rollout(myr_handle h, int B, int num_steps, int u_rows, const double* x0, const double* us,
-                            const double* params, int pstride, double* xs, double* cost);
+static int dispatch_rollout(myr_handle h, const RolloutArgs& a);
 extern "C" int myr_set_var_scale(myr_handle h, const double* scale);
 
 __global__ void gather_rows_kernel(long total, int w, const int32_t* __restrict__ idx, const double* __restrict__ src, double* __restrict__ dst) {
@@ -1518,16 +1505,8 @@ __global__ void count_failed_kernel(int B, const int32_t* __restrict__ status, i
 }
 
 static bool twin_defaults(int twin_id, double* buf) {
-  switch (twin_id) {
-#define X(N) case MYR_SYS_##N: Sys##N::default_params(buf); return true;
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-  }
-  return false;
+  return for_system(twin_id, false, [&](auto t) { using S = SYS_OF(t); S::default_params(buf); return true; }, [] { return false; });
 }
-
-static unsigned grid_for(long total) { long b = (total + 255) / 256; if (b > 16384) b = 16384; if (b < 1) b = 1; return (unsigned)b; }
-
 
 struct RestoreCfg { bool elastic, starts; std::vector<int> cycles; };
 static RestoreCfg restore_cfg(const myr_solve_opts& so) {
@@ -1579,10 +1558,13 @@ static int solve_restored(myr_handle h, const SolveCall& a) {
   const myr_dims& dm = h->dims;
   const int n = dm.n, m = dm.m, ns = dm.ns, nu = dm.nu, np = dm.np;
   // the caller's guess is overwritten by the first attempt: keep it
-  if (int rc = ensure_buf(&h->rbuf, &h->rbuf_bytes, (al((size_t)B * n) + 2 * al((size_t)B)) * 8)) return rc;
-  double* z0c = (double*)h->rbuf;
-  int32_t* dstat = a.status ? a.status : (int32_t*)(z0c + al((size_t)B * n));
-  int32_t* dit = a.iters ? a.iters : (int32_t*)(z0c + al((size_t)B * n) + al((size_t)B));
+  double* z0c = nullptr;
+  int32_t *dstat = a.status, *dit = a.iters;
+  DevStage keep = scratch_stage(h, &h->rbuf, &h->rbuf_bytes);
+  keep.scratch(z0c, (size_t)B * n);
+  if (!a.status) keep.scratch(dstat, (size_t)B);
+  if (!a.iters) keep.scratch(dit, (size_t)B);
+  if (int rc = keep.commit()) return rc;
   HIPCHK(hipMemcpyAsync(z0c, z, (size_t)B * n * 8, hipMemcpyDeviceToDevice, h->stream));
   SolveCall first = a;      // status and iterations are needed here whether the caller asked for them or not
   first.status = dstat; first.iters = dit;
@@ -1615,28 +1597,19 @@ static int solve_restored(myr_handle h, const SolveCall& a) {
   const int mc = (h->d.transcription == MYR_TR_SHOOTING && h->d.integration_method == MYR_INT_RK4) ? 2 : 1;
   const int steps = (dm.u_rows - 1) / mc;
   const int rr = (h->d.integration_method == MYR_INT_RK4) ? 2 * steps + 1 : steps + 1;
-  size_t words = 2 * al((size_t)nf0) + 4 * al((size_t)nf0 * n) + al((size_t)nf0 * (np > 0 ? np : 1)) + al((size_t)nf0 * m) + al((size_t)nf0) + al((size_t)nf0 * 3) + 2 * al((size_t)nf0);
-  if (twin) words += 3 * al((size_t)nf0 * nt) + al((size_t)nf0 * (np + 1)) + al((size_t)nf0) + al(64);
-  if (cfg.starts) words += al((size_t)nf0 * rr * nu) + al((size_t)nf0 * ns) + al((size_t)nf0 * (steps + 1) * ns);
-  if (int rc = ensure_buf(&h->fbuf, &h->fbuf_bytes, words * 8)) return rc;
-  double* q = (double*)h->fbuf;
-  int32_t* didx = (int32_t*)q; q += al((size_t)nf0);
-  int32_t* dtake = (int32_t*)q; q += al((size_t)nf0);
-  double* z0f = q; q += al((size_t)nf0 * n);
-  double* zf = q; q += al((size_t)nf0 * n);
-  double* lbf = q; q += al((size_t)nf0 * n);
-  double* ubf = q; q += al((size_t)nf0 * n);
-  double* pf = q; q += al((size_t)nf0 * (np > 0 ? np : 1));
-  double* lamf = q; q += al((size_t)nf0 * m);
-  double* costf = q; q += al((size_t)nf0);
-  double* kktf = q; q += al((size_t)nf0 * 3);
-  int32_t* statf = (int32_t*)q; q += al((size_t)nf0);
-  int32_t* itf = (int32_t*)q; q += al((size_t)nf0);
+  const size_t F = (size_t)nf0;
+  int32_t *didx, *dtake, *statf, *itf;
+  double *z0f, *zf, *lbf, *ubf, *pf, *lamf, *costf, *kktf;
   double *zt = nullptr, *lbt = nullptr, *ubt = nullptr, *pt = nullptr, *dslack = nullptr, *ddef = nullptr;
-  if (twin) { zt = q; q += al((size_t)nf0 * nt); lbt = q; q += al((size_t)nf0 * nt); ubt = q; q += al((size_t)nf0 * nt); pt = q; q += al((size_t)nf0 * (np + 1));
-              dslack = q; q += al((size_t)nf0); ddef = q; q += al(64); }
   double *dus = nullptr, *dx0 = nullptr, *dxs = nullptr;
-  if (cfg.starts) { dus = q; q += al((size_t)nf0 * rr * nu); dx0 = q; q += al((size_t)nf0 * ns); dxs = q; q += al((size_t)nf0 * (steps + 1) * ns); }
+  DevStage ws = scratch_stage(h, &h->fbuf, &h->fbuf_bytes);
+  ws.scratch(didx, F); ws.scratch(dtake, F);
+  ws.scratch(z0f, F * n); ws.scratch(zf, F * n); ws.scratch(lbf, F * n); ws.scratch(ubf, F * n);
+  ws.scratch(pf, F * (np > 0 ? np : 1));
+  ws.scratch(lamf, F * m); ws.scratch(costf, F); ws.scratch(kktf, F * 3); ws.scratch(statf, F); ws.scratch(itf, F);
+  if (twin) { ws.scratch(zt, F * nt); ws.scratch(lbt, F * nt); ws.scratch(ubt, F * nt); ws.scratch(pt, F * (np + 1)); ws.scratch(dslack, F); ws.scratch(ddef, 64); }
+  if (cfg.starts) { ws.scratch(dus, F * rr * nu); ws.scratch(dx0, F * ns); ws.scratch(dxs, F * (steps + 1) * ns); }
+  if (int rc = ws.commit()) return rc;
   const bool per_row_params = params && pstride != 0;
   const int nx = dm.x_rows * ns;
 
@@ -1757,7 +1730,7 @@ static int solve_restored(myr_handle h, const SolveCall& a) {
       if (int rc = gather(fail_)) return rc;
       hipLaunchKernelGGL(excitation_controls_kernel, dim3(grid_for((long)nf * rr * nu)), dim3(256), 0, h->stream, nf, rr, dm.u_rows, nu, ns, nx, n, (double)c, lbf, ubf, z0f, dus, dx0);
       HIPCHK(hipGetLastError());
-      if (int rc = dispatch_rollout(h, nf, steps, rr, dx0, dus, pfp, per_row_params ? np : pstride, dxs, nullptr)) return rc;
+      if (int rc = dispatch_rollout(h, RolloutArgs{nf, steps, rr, dx0, dus, pfp, per_row_params ? np : pstride, dxs, nullptr})) return rc;
       hipLaunchKernelGGL(excitation_pack_kernel, dim3(grid_for((long)nf * n)), dim3(256), 0, h->stream, (long)nf * n, n, nx, ns, nu, steps, xstride, rr, ustride, dxs, dus, lbf, ubf, zf);
       HIPCHK(hipGetLastError());
       again.B = nf;
@@ -1823,33 +1796,31 @@ extern "C" int myr_set_var_scale(myr_handle h, const double* scale) {
 // (myr_solve_x0; myr_solve tests it after hipSetDevice).  *empty: a batch of zero instances -- nothing to do, and nothing further is checked.
 static int check_solve_args(myr_handle h, const char* who, const char* arrays, bool null, const int32_t* mem_early, const myr_solve_opts* opts,
                             SolveCall* c, bool* empty) {
-  const std::string w(who);
   *empty = false;
-  if (!h || null) return fail(MYR_E_ARG, w + ": null handle, " + arrays);
+  if (!h || null) return arg_fail(who, MYR_E_ARG, (std::string("null handle, ") + arrays).c_str());
   if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
-  if (c->B < 0) return fail(MYR_E_ARG, w + ": negative batch");
+  if (int rc = check_batch(who, c->B)) return rc;
   if (c->B == 0) { h->info_start.clear(); h->info_attempts.clear(); h->info_restored.clear(); *empty = true; return MYR_OK; }
-  if (c->params && c->pstride != 0 && c->pstride != h->dims.np)
-    return fail(MYR_E_ARG, w + ": params_stride must be 0 (shared) or np");
-  if (!c->params && h->d.system_id == MYR_SYS_NODE_CARTPOLE) return fail(MYR_E_ARG, w + ": a NODE system needs its weights in `params`");
-  if (mem_early && *mem_early != MYR_MEM_HOST && *mem_early != MYR_MEM_DEVICE) return fail(MYR_E_ARG, w + ": bad mem kind");
+  if (int rc = check_stride(h, who, c->params, c->pstride)) return rc;
+  if (int rc = check_node_weights(h, who, c->params)) return rc;
+  if (mem_early)
+    if (int rc = check_mem(who, *mem_early)) return rc;
   myr_solve_opts& so = c->so;
   if (opts) so = *opts; else myr_default_solve_opts(&so);
   if (so.max_iter < 0 || !(so.tol_feas > 0) || !(so.tol_stat > 0) || !(so.tol_compl > 0) || !(so.mu_init > 0))
-    return fail(MYR_E_ARG, w + ": bad options");
+    return arg_fail(who, MYR_E_ARG, "bad options");
   return MYR_OK;
 }
-// the results of a solve, from the staging arrays `d` to the host caller's `user` (all but z optional)
-static int download_solve(myr_handle h, const SolveCall& d, const SolveCall& user) {
-  const size_t B = (size_t)d.B;
-  HIPCHK(hipMemcpyAsync(user.z, d.z, B * h->dims.n * 8, hipMemcpyDeviceToHost, h->stream));
-  if (user.lam) HIPCHK(hipMemcpyAsync(user.lam, d.lam, B * h->dims.m * 8, hipMemcpyDeviceToHost, h->stream));
-  if (user.cost) HIPCHK(hipMemcpyAsync(user.cost, d.cost, B * 8, hipMemcpyDeviceToHost, h->stream));
-  if (user.status) HIPCHK(hipMemcpyAsync(user.status, d.status, B * 4, hipMemcpyDeviceToHost, h->stream));
-  if (user.iters) HIPCHK(hipMemcpyAsync(user.iters, d.iters, B * 4, hipMemcpyDeviceToHost, h->stream));
-  if (user.kkt) HIPCHK(hipMemcpyAsync(user.kkt, d.kkt, B * 24, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return MYR_OK;
+// What the two entry points stage alike behind their own inputs: lam, the parameters, and the four per-instance results.  Those four are device arrays
+// whether or not a host caller asked for them (the two-phase launch orders its resume by kkt; solve_restored reads status and iterations), downloaded when asked.
+static void stage_solve_tail(DevStage& st, myr_handle h, SolveCall& d, const SolveCall& user) {
+  const size_t B = (size_t)user.B;
+  st.out(d.lam, user.lam, B * h->dims.m);
+  st.in(d.params, user.params, n_params(h, user.params, user.pstride, user.B));
+  st.out(d.cost, user.cost, B, true);
+  st.out(d.status, user.status, B, true);
+  st.out(d.iters, user.iters, B, true);
+  st.out(d.kkt, user.kkt, 3 * B, true);
 }
 
 extern "C" int myr_solve(myr_handle h, int32_t B, double* z, const double* lb, const double* ub,
@@ -1860,29 +1831,17 @@ extern "C" int myr_solve(myr_handle h, int32_t B, double* z, const double* lb, c
   if (int rc = check_solve_args(h, "myr_solve", "z, lb or ub", !z || !lb || !ub, nullptr, opts, &user, &empty)) return rc;
   if (empty) return MYR_OK;
   HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  if (mem == MYR_MEM_DEVICE) return solve_restored(h, user);
-  if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_solve: bad mem kind");
-  const size_t nz = (size_t)B * dm.n, nl = lam ? (size_t)B * dm.m : 0;
-  const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  const size_t total = 3 * al(nz) + al(nl) + al(npar) + al(B) /*cost*/ + al(B) /*status+iters as int32 pairs*/ + al(3 * (size_t)B);
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * 8)) return rc;
-  double* dz = (double*)h->dbuf;
-  double* dlb = dz + al(nz);
-  double* dub = dlb + al(nz);
-  double* dlam = dub + al(nz);
-  double* dp = dlam + al(nl);
-  double* dcost = dp + al(npar);
-  int32_t* dstat = (int32_t*)(dcost + al(B));
-  int32_t* dit = dstat + B;
-  double* dkkt = (double*)(dstat) + al(B);
-  HIPCHK(hipMemcpyAsync(dz, z, nz * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dlb, lb, nz * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dub, ub, nz * 8, hipMemcpyHostToDevice, h->stream));
-  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  const SolveCall d{B, dz, dlb, dub, npar ? dp : nullptr, params_stride, user.so, nl ? dlam : nullptr, dcost, dstat, dit, dkkt};      // the batch in the staging buffer
+  if (int rc = check_mem("myr_solve", mem)) return rc;
+  const size_t nz = (size_t)B * h->dims.n;
+  SolveCall d = user;      // the batch the solver sees: a device caller's own arrays, a host caller's staged
+  DevStage st = call_stage(h, mem);
+  st.inout(d.z, z, nz);
+  st.in(d.lb, lb, nz);
+  st.in(d.ub, ub, nz);
+  stage_solve_tail(st, h, d, user);
+  if (int rc = st.commit()) return rc;
   if (int rc = solve_restored(h, d)) return rc;
-  return download_solve(h, d, user);
+  return st.finish();
 }
 
 // ---- myr_solve_x0: B instances that differ in their START STATE only ------------------------------------------------
@@ -1919,92 +1878,54 @@ extern "C" int myr_solve_x0(myr_handle h, int32_t B, const double* x0s, const do
   if (empty) return MYR_OK;
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
-  const bool host = mem == MYR_MEM_HOST;
-  const size_t nz = (size_t)B * dm.n, nl = lam ? (size_t)B * dm.m : 0, nx0 = (size_t)B * dm.ns;
-  const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  // device scratch: the expanded bounds always; for host callers also the iterate, the inputs and the results
-  size_t total = 2 * al(nz);
-  if (host) total += al(nz) + al(nx0) + 4 * al((size_t)dm.n) + al(nl) + al(npar) + al(B) + al(B) + al(3 * (size_t)B);
-  if (int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, total * 8)) return rc;
-  double* dlb = (double*)h->dbuf;
-  double* dub = dlb + al(nz);
-  SolveCall d = user;      // the batch the solver sees: a device caller's own arrays with the expanded bounds; a host caller's all staged
+  const size_t nz = (size_t)B * dm.n, n1 = (size_t)dm.n;
+  // the expanded bounds are device scratch for every caller; a host caller's iterate, inputs and results are staged too
+  SolveCall d = user;
+  double *dlb = nullptr, *dub = nullptr;
+  const double *dx0 = nullptr, *dg0 = nullptr, *dg1 = nullptr, *dlt = nullptr, *dut = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.scratch(dlb, nz);
+  st.scratch(dub, nz);
+  st.out(d.z, z, nz);
+  st.in(dx0, x0s, (size_t)B * dm.ns);
+  st.in(dg0, g0, n1); st.in(dg1, g1, n1); st.in(dlt, lb, n1); st.in(dut, ub, n1);
+  stage_solve_tail(st, h, d, user);
+  if (int rc = st.commit()) return rc;
   d.lb = dlb; d.ub = dub;
-  const double* dx0 = x0s; const double* dg0 = g0; const double* dg1 = g1; const double* dlt = lb; const double* dut = ub;
-  if (host) {
-    double* q = dub + al(nz);
-    d.z = q; q += al(nz);
-    double* hx0 = q; q += al(nx0);
-    double* tpl = q; q += 4 * al((size_t)dm.n);
-    d.lam = nl ? q : nullptr; q += al(nl);
-    double* hp = q; q += al(npar);
-    d.cost = q; q += al(B);
-    d.status = (int32_t*)q; d.iters = d.status + B; q += al(B);
-    d.kkt = q;
-    HIPCHK(hipMemcpyAsync(hx0, x0s, nx0 * 8, hipMemcpyHostToDevice, h->stream));
-    const double* src[4] = {g0, g1, lb, ub};
-    for (int k = 0; k < 4; ++k) HIPCHK(hipMemcpyAsync(tpl + k * al((size_t)dm.n), src[k], (size_t)dm.n * 8, hipMemcpyHostToDevice, h->stream));
-    if (npar) HIPCHK(hipMemcpyAsync(hp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-    dx0 = hx0; dg0 = tpl; dg1 = tpl + al((size_t)dm.n); dlt = tpl + 2 * al((size_t)dm.n); dut = tpl + 3 * al((size_t)dm.n);
-    d.params = npar ? hp : nullptr;
-  }
-  {
-    const long tz = (long)nz;
-    long blocks = (tz + 255) / 256; if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(pack_x0_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, tz, dm.n, dm.ns, dm.x_rows * dm.ns, dx0, dg0, dg1, dlt, dut, d.z, dlb, dub);
-    HIPCHK(hipGetLastError());
-  }
+  hipLaunchKernelGGL(pack_x0_kernel, dim3(grid_for((long)nz)), dim3(256), 0, h->stream, (long)nz, dm.n, dm.ns, dm.x_rows * dm.ns, dx0, dg0, dg1, dlt, dut, d.z, dlb, dub);
+  HIPCHK(hipGetLastError());
   if (int rc = solve_restored(h, d)) return rc;
-  return host ? download_solve(h, d, user) : MYR_OK;
+  return st.finish();
 }
 
-static int dispatch_rollout(myr_handle h, int B, int num_steps, int u_rows, const double* x0, const double* us,
-                            const double* params, int pstride, double* xs, double* cost) {
-  int rc = timed_begin(h, MYR_K_ROLLOUT);
-  if (rc) return rc;
-  switch (h->d.system_id) {
-#define X(N) case MYR_SYS_##N: rc = rollout_for_system<Sys##N>(h, B, num_steps, u_rows, x0, us, params, pstride, xs, cost); break;
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-    case MYR_SYS_NODE_CARTPOLE: rc = rollout_for_system<SysNODE_CARTPOLE>(h, B, num_steps, u_rows, x0, us, params, pstride, xs, cost); break;
-    default: return no_such_path(h, "rollout");
-  }
-  if (rc) return rc;
+static int dispatch_rollout(myr_handle h, const RolloutArgs& a) {
+  if (int rc = timed_begin(h, MYR_K_ROLLOUT)) return rc;
+  if (int rc = for_system(h->d.system_id, true, [&](auto t) { return rollout_for_system<SYS_OF(t)>(h, a); }, [&] { return no_such_path(h, "rollout"); })) return rc;
   return timed_end(h, MYR_K_ROLLOUT);
 }
 
 extern "C" int myr_rollout(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* x0, const double* us,
                            const double* params, int32_t params_stride, double* xs, double* cost, int32_t mem) {
+  const char* who = "myr_rollout";
   if (!h || !x0 || !us) return fail(MYR_E_ARG, "myr_rollout: null handle, x0 or us");
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, "myr_rollout");
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
   if (B < 0 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_rollout: bad sizes");
   if (B == 0) return MYR_OK;
-  if (params && params_stride != 0 && params_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_rollout: params_stride must be 0 (shared) or np");
-  if (!params && h->d.system_id == MYR_SYS_NODE_CARTPOLE) return fail(MYR_E_ARG, "myr_rollout: a NODE system needs its weights in `params`");
+  if (int rc = check_stride(h, who, params, params_stride)) return rc;
+  if (int rc = check_node_weights(h, who, params)) return rc;
   HIPCHK(hipSetDevice(h->d.device));
+  if (int rc = check_mem(who, mem)) return rc;
   const myr_dims& dm = h->dims;
-  if (mem == MYR_MEM_DEVICE) return dispatch_rollout(h, B, num_steps, u_rows, x0, us, params, params_stride, xs, cost);
-  if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_rollout: bad mem kind");
-  const size_t nx0 = (size_t)B * dm.ns, nus = (size_t)B * u_rows * dm.nu;
-  const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  const size_t nxs = xs ? (size_t)B * (num_steps + 1) * dm.ns : 0, nc = cost ? (size_t)B : 0;
-  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nx0) + al(nus) + al(npar) + al(nxs) + al(nc)) * 8);
-  if (rc) return rc;
-  double* dx0 = (double*)h->dbuf;
-  double* dus = dx0 + al(nx0);
-  double* dp = dus + al(nus);
-  double* dxs = dp + al(npar);
-  double* dc = dxs + al(nxs);
-  HIPCHK(hipMemcpyAsync(dx0, x0, nx0 * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dus, us, nus * 8, hipMemcpyHostToDevice, h->stream));
-  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  rc = dispatch_rollout(h, B, num_steps, u_rows, dx0, dus, npar ? dp : nullptr, params_stride, nxs ? dxs : nullptr, nc ? dc : nullptr);
-  if (rc) return rc;
-  if (nxs) HIPCHK(hipMemcpyAsync(xs, dxs, nxs * 8, hipMemcpyDeviceToHost, h->stream));
-  if (nc) HIPCHK(hipMemcpyAsync(cost, dc, nc * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return MYR_OK;
+  RolloutArgs a{B, num_steps, u_rows, nullptr, nullptr, nullptr, params_stride, nullptr, nullptr};
+  DevStage st = call_stage(h, mem);
+  st.in(a.x0, x0, (size_t)B * dm.ns);
+  st.in(a.us, us, (size_t)B * u_rows * dm.nu);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.out(a.xs, xs, (size_t)B * (num_steps + 1) * dm.ns);
+  st.out(a.cost, cost, (size_t)B);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_rollout(h, a)) return rc;
+  return st.finish();
 }
 
 // Sum of the per-trajectory gradient rows in a fixed order: block k owns entry k; thread t adds rows t, t + 256, ... in ascending order, then the
@@ -2025,38 +1946,25 @@ static __global__ __launch_bounds__(256) void fit_reduce_kernel(int B, int np, c
 }
 
 static bool fit_supported(int id) {
-  switch (id) {
-#define X(N) case MYR_SYS_##N: return SysDp<Sys##N>::SUPPORTED;
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-    case MYR_SYS_NODE_CARTPOLE: return true;
-  }
-  return false;
+  return for_system(id, true, [](auto t) { using S = SYS_OF(t); return std::is_same<S, SysNODE_CARTPOLE>::value || SysDp<S>::SUPPORTED; }, [] { return false; });
 }
 static bool sys_known(int id) { SysInfo si; return sys_info(id, &si); }
 
-// device pointers throughout; grad: [B][np] rows (grad_stride == np) or the [np] sum over the batch (grad_stride == 0, rows in sbuf)
-static int dispatch_fit(myr_handle h, int B, int num_steps, int u_rows, const double* xs_obs, const double* us, const double* wt,
-                        const double* params, int pstride, double* loss, double* grad, int grad_stride) {
+// device pointers throughout (a.Bp, a.xh are set here); a.grad: [B][np] rows (grad_stride == np) or the [np] sum over the batch (grad_stride == 0, rows in sbuf)
+static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
   const myr_dims& dm = h->dims;
-  long Bp = ((long)B + 63) / 64 * 64;
-  if (((Bp / 64) & 1) == 0) Bp += 64;                 // odd multiple of 64 lanes: rotate the state rows over the HBM channels
-  const size_t nxh = (size_t)(num_steps + 1) * dm.ns * (size_t)Bp, nrows = grad_stride ? 0 : (size_t)B * dm.np;
-  if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, (al(nxh) + al(nrows)) * 8)) return rc;
-  double* xh = (double*)h->sbuf;
-  double* rows = grad_stride ? grad : xh + al(nxh);
+  double* const sum = a.grad;
+  a.Bp = padded_lanes(a.B);
+  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
+  st.scratch(a.xh, (size_t)(a.num_steps + 1) * dm.ns * (size_t)a.Bp);
+  if (!grad_stride) st.scratch(a.grad, (size_t)a.B * dm.np);
+  if (int rc = st.commit()) return rc;
   if (!fit_supported(h->d.system_id))                  // refused before the timer starts: begin and end stay paired
     return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
                                      : no_such_path(h, "myr_fit_grad");
-  int rc = timed_begin(h, MYR_K_FIT);
-  if (rc) return rc;
-  switch (h->d.system_id) {
-#define X(N) case MYR_SYS_##N: rc = fit_for_system<Sys##N>(h, B, Bp, num_steps, u_rows, xs_obs, us, wt, params, pstride, xh, loss, rows); break;
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-    case MYR_SYS_NODE_CARTPOLE: rc = fit_for_system<SysNODE_CARTPOLE>(h, B, Bp, num_steps, u_rows, xs_obs, us, wt, params, pstride, xh, loss, rows); break;
-  }
-  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, B, (int)dm.np, rows, grad);
+  if (int rc = timed_begin(h, MYR_K_FIT)) return rc;
+  const int rc = for_system(h->d.system_id, true, [&](auto t) { return fit_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.grad, sum);
   const int rc_end = timed_end(h, MYR_K_FIT);          // on every path
   return rc ? rc : rc_end;
 }
@@ -2064,44 +1972,32 @@ static int dispatch_fit(myr_handle h, int B, int num_steps, int u_rows, const do
 extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                             const double* wt, const double* params, int32_t params_stride, double* loss, double* grad,
                             int32_t grad_stride, int32_t mem) {
+  const char* who = "myr_fit_grad";
   if (!h || !xs_obs || !us || !grad) return fail(MYR_E_ARG, "myr_fit_grad: null handle, xs_obs, us or grad");
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, "myr_fit_grad");
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
   if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
   if (B < 0 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_grad: bad sizes");
   if (grad_stride != 0 && grad_stride != h->dims.np)
     return fail(MYR_E_ARG, "myr_fit_grad: grad_stride must be 0 (one row: the sum over the batch) or np (a row per trajectory)");
-  if (params && params_stride != 0 && params_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_fit_grad: params_stride must be 0 (shared) or np");
-  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE) {
-    if (!params) return fail(MYR_E_ARG, "myr_fit_grad: a NODE system needs its weights in `params`");
-    if (params_stride != 0) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: a NODE system takes one shared set of weights (params_stride 0)");
-  }
-  if (mem != MYR_MEM_DEVICE && mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_fit_grad: bad mem kind");
+  if (int rc = check_stride(h, who, params, params_stride)) return rc;
+  if (int rc = check_node_weights(h, who, params)) return rc;
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE && params_stride != 0)
+    return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: a NODE system takes one shared set of weights (params_stride 0)");
+  if (int rc = check_mem(who, mem)) return rc;
   if (B == 0) return MYR_OK;                          // (nothing is written)
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
-  if (mem == MYR_MEM_DEVICE) return dispatch_fit(h, B, num_steps, u_rows, xs_obs, us, wt, params, params_stride, loss, grad, grad_stride);
-  const size_t nxs = (size_t)B * (num_steps + 1) * dm.ns, nus = (size_t)B * u_rows * dm.nu, nwt = wt ? (size_t)num_steps + 1 : 0;
-  const size_t npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  const size_t nl = loss ? (size_t)B : 0, ng = grad_stride ? (size_t)B * dm.np : (size_t)dm.np;
-  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nxs) + al(nus) + al(nwt) + al(npar) + al(nl) + al(ng)) * 8);
-  if (rc) return rc;
-  double* dxs = (double*)h->dbuf;
-  double* dus = dxs + al(nxs);
-  double* dwt = dus + al(nus);
-  double* dp = dwt + al(nwt);
-  double* dl = dp + al(npar);
-  double* dg = dl + al(nl);
-  HIPCHK(hipMemcpyAsync(dxs, xs_obs, nxs * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(dus, us, nus * 8, hipMemcpyHostToDevice, h->stream));
-  if (nwt) HIPCHK(hipMemcpyAsync(dwt, wt, nwt * 8, hipMemcpyHostToDevice, h->stream));
-  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  rc = dispatch_fit(h, B, num_steps, u_rows, dxs, dus, nwt ? dwt : nullptr, npar ? dp : nullptr, params_stride, nl ? dl : nullptr, dg, grad_stride);
-  if (rc) return rc;
-  if (nl) HIPCHK(hipMemcpyAsync(loss, dl, nl * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(grad, dg, ng * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return MYR_OK;
+  FitArgs a{B, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, params_stride, nullptr, nullptr, nullptr};
+  DevStage st = call_stage(h, mem);
+  st.in(a.xs_obs, xs_obs, (size_t)B * (num_steps + 1) * dm.ns);
+  st.in(a.us, us, (size_t)B * u_rows * dm.nu);
+  st.in(a.wt, wt, (size_t)num_steps + 1);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.out(a.loss, loss, (size_t)B);
+  st.out(a.grad, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_fit(h, a, grad_stride)) return rc;
+  return st.finish();
 }
 
 extern "C" int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, const double* adj_T, const double* params,
@@ -2109,61 +2005,52 @@ extern "C" int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, co
                         int32_t max_sweeps, double* xs, double* us, double* adjs, int32_t* sweeps, int32_t mem) {
   if (!h || !x0 || !xs || !us || !adjs || !clip_lo || !clip_hi) return fail(MYR_E_ARG, "myr_fbsm: null handle or array");
   if (h->dims.nu > 8) return fail(MYR_E_CAPACITY, "myr_fbsm: more than 8 controls");
-  VarScale vlo{}, vhi{};
-  for (int c = 0; c < h->dims.nu; ++c) { vlo.s[c] = clip_lo[c]; vhi.s[c] = clip_hi[c]; }
+  FbsmArgs a{};
+  for (int c = 0; c < h->dims.nu; ++c) { a.lo.s[c] = clip_lo[c]; a.hi.s[c] = clip_hi[c]; }
   if (B < 0 || N < 1 || max_sweeps < 1) return fail(MYR_E_ARG, "myr_fbsm: bad sizes");
   if (mem != MYR_MEM_HOST) return fail(MYR_E_ARG, "myr_fbsm: host arrays only");
-  if (params && params_stride != 0 && params_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_fbsm: params_stride must be 0 (shared) or np");
+  if (int rc = check_stride(h, "myr_fbsm", params, params_stride)) return rc;
   if (B == 0) return MYR_OK;
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
-  long Bp = ((long)B + 63) / 64 * 64;
-  if (((Bp / 64) & 1) == 0) Bp += 64;                 // odd multiple of 64 lanes: rotate points over HBM channels
+  const long Bp = padded_lanes(B);
   const bool discrete = h->d.system_id == MYR_SYS_INVASIVEPLANT;      // u has one row per step, not per point
   if (discrete && !params) return fail(MYR_E_ARG, "myr_fbsm: a discrete system needs `params`");
   const size_t rows_x = (size_t)(N + 1) * dm.ns, rows_u = (size_t)(N + (discrete ? 0 : 1)) * dm.nu;
-  const size_t nx0 = (size_t)B * dm.ns, npar = params ? (params_stride ? (size_t)B * dm.np : (size_t)dm.np) : 0;
-  // batch-minor working arrays + instance-major staging for the transposes + sweeps
-  const size_t work = (2 * rows_x + rows_u) * (size_t)Bp, stage = (size_t)B * (rows_x > rows_u ? rows_x : rows_u);
-  int rc = ensure_buf(&h->dbuf, &h->dbuf_bytes, (al(nx0) + al(npar) + al((size_t)dm.ns) + al(work) + al(stage) + al((size_t)B)) * 8);
-  if (rc) return rc;
-  double* dx0 = (double*)h->dbuf;
-  double* dp = dx0 + al(nx0);
-  double* dadj = dp + al(npar);
-  double* X = dadj + al((size_t)dm.ns);
-  double* A = X + rows_x * Bp;
-  double* U = A + rows_x * Bp;
-  double* st = X + al(work);
-  int32_t* dsw = reinterpret_cast<int32_t*>(st + al(stage));
-  HIPCHK(hipMemcpyAsync(dx0, x0, nx0 * 8, hipMemcpyHostToDevice, h->stream));
-  if (npar) HIPCHK(hipMemcpyAsync(dp, params, npar * 8, hipMemcpyHostToDevice, h->stream));
-  if (adj_T) HIPCHK(hipMemcpyAsync(dadj, adj_T, (size_t)dm.ns * 8, hipMemcpyHostToDevice, h->stream));
-#define MYR_FBSM(S) rc = launch_fbsm<S>(h, B, Bp, N, dx0, adj_T ? dadj : nullptr, npar ? dp : nullptr, params_stride, vlo, vhi, bang, delta, max_sweeps, X, U, A, dsw)
-  switch (h->d.system_id) {
-#define X(N) case MYR_SYS_##N: MYR_FBSM(Sys##N); break;
-    MYR_CLOSED_FORM_SYSTEMS(X)
-#undef X
-    case MYR_SYS_INVASIVEPLANT: {
-      if (int rc_begin = timed_begin(h, MYR_K_FBSM)) return rc_begin;
-      hipLaunchKernelGGL(fbsm_discrete_kernel<DiscINVASIVEPLANT>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, Bp, N, dx0,
-                         adj_T ? dadj : nullptr, dp, params_stride, vlo, vhi, delta, max_sweeps, X, U, A, dsw);
-      rc = timed_end(h, MYR_K_FBSM);
-      break;
-    }
-    default: rc = fail(MYR_E_UNSUPPORTED, "myr_fbsm: this system has no adjoint dynamics");
+  a.B = B; a.Bp = Bp; a.N = N; a.pstride = params_stride; a.bang = bang; a.delta = delta; a.max_sweeps = max_sweeps;
+  // the inputs; the batch-minor working arrays X | A | U; an instance-major array for the transposes back; the sweep counts
+  double* back = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.x0, x0, (size_t)B * dm.ns);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.in(a.adjT, adj_T, (size_t)dm.ns);
+  st.scratch(a.X, (2 * rows_x + rows_u) * (size_t)Bp);
+  st.scratch(back, (size_t)B * (rows_x > rows_u ? rows_x : rows_u));
+  st.scratch(a.sweeps, (size_t)B);
+  if (int rc = st.commit()) return rc;
+  a.A = a.X + rows_x * Bp;
+  a.U = a.A + rows_x * Bp;
+  int rc;
+  if (discrete) {
+    if (int rc_begin = timed_begin(h, MYR_K_FBSM)) return rc_begin;
+    hipLaunchKernelGGL(fbsm_discrete_kernel<DiscINVASIVEPLANT>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, Bp, N, a.x0,
+                       a.adjT, a.params, params_stride, a.lo, a.hi, delta, max_sweeps, a.X, a.U, a.A, a.sweeps);
+    rc = timed_end(h, MYR_K_FBSM);
+  } else {
+    rc = for_system(h->d.system_id, false, [&](auto t) { return launch_fbsm<SYS_OF(t)>(h, a); },
+                    [] { return fail(MYR_E_UNSUPPORTED, "myr_fbsm: this system has no adjoint dynamics"); });
   }
-#undef MYR_FBSM
   if (rc) return rc;
-  struct { double* src; double* dst; size_t cols; } outs[3] = {{X, xs, rows_x}, {U, us, rows_u}, {A, adjs, rows_x}};
+  // one result at a time through `back`: transpose, download, synchronise (no st.finish(): nothing is registered as an output)
+  struct { double* src; double* dst; size_t cols; } outs[3] = {{a.X, xs, rows_x}, {a.U, us, rows_u}, {a.A, adjs, rows_x}};
   for (auto& o : outs) {
     dim3 grid((unsigned)((o.cols + 31) / 32), (unsigned)((B + 31) / 32));
-    hipLaunchKernelGGL(transpose_back_kernel, grid, dim3(256), 0, h->stream, o.src, st, B, (int)o.cols, Bp);
+    hipLaunchKernelGGL(transpose_back_kernel, grid, dim3(256), 0, h->stream, o.src, back, B, (int)o.cols, Bp);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(o.dst, st, (size_t)B * o.cols * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(o.dst, back, (size_t)B * o.cols * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
-  if (sweeps) HIPCHK(hipMemcpy(sweeps, dsw, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (sweeps) HIPCHK(hipMemcpy(sweeps, a.sweeps, (size_t)B * 4, hipMemcpyDeviceToHost));
   return MYR_OK;
 }
 #endif  // !MYR_TU_SYSTEM
