@@ -230,6 +230,7 @@ MYR_HD inline void chol_solve(const double* a, double* b) {
 }  // namespace detail
 }  // namespace myriad
 #include "ip_policy.h"   // the interior-point loop's scalar state and rules (uses HsSolveOpts and detail:: above)
+#include "bound_rules.h" // the rules of one bounded variable (uses detail::rcp_ / dmax / dmin above)
 namespace myriad {
 
 // One collocation point's linearisation.
@@ -268,26 +269,6 @@ struct HsSolver {
 #pragma unroll
     for (int c = 0; c < NU; ++c) P.u[c] = V.z[NS + c];
     Sys::lin_d2(P.x, P.u, p, P.f, P.A, P.B, &P.g, P.gw, P.D2);
-  }
-
-  // bound data of one variable (branch-free): barrier Hessian sigma, (-zL + zU) for the adjoint,
-  // mu-coefficient g1 = -1/(z-l) + 1/(u-z); complementarity extremes; pinned flag
-  struct BV { double sigma, g1, zlu; bool pinned; };
-  MYR_HD static inline BV bound_terms(double zv, double l, double u, double zl, double zu, double& compl_max, double& compl_min) {
-    BV r;
-    const bool fr = l < u;
-    const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-    const double sl = hl ? zv - l : 1.0, su = hu ? u - zv : 1.0;
-    const double zlv = hl ? zl : 0.0, zuv = hu ? zu : 0.0;
-    const double il = hl ? detail::rcp_(sl) : 0.0, iu = hu ? detail::rcp_(su) : 0.0;
-    r.pinned = !fr;
-    r.sigma = zlv * il + zuv * iu;
-    r.g1 = iu - il;
-    r.zlu = zuv - zlv;
-    const double cl = sl * zlv, cu = su * zuv;
-    compl_max = detail::dmax(compl_max, detail::dmax(hl ? cl : compl_max, hu ? cu : compl_max));
-    compl_min = detail::dmin(compl_min, detail::dmin(hl ? cl : compl_min, hu ? cu : compl_min));
-    return r;
   }
 
   // ------------------------------------------------------------------------------------------------
@@ -373,9 +354,9 @@ struct HsSolver {
       bool pin_e[NW];
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
-        BV b = bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
+        BoundTerms b = bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
         sig_e[c] = b.sigma; g1_e[c] = b.g1; zlu_e[c] = b.zlu; pin_e[c] = b.pinned;
-        BV bm = bound_terms(Vm.z[c], Vm.l[c], Vm.u[c], Vm.zl[c], Vm.zu[c], so.compl_max, so.compl_min);
+        BoundTerms bm = bound_terms(Vm.z[c], Vm.l[c], Vm.u[c], Vm.zl[c], Vm.zu[c], so.compl_max, so.compl_min);
         sig_m[c] = bm.sigma; g1_m[c] = bm.g1; zlu_m[c] = bm.zlu;
       }
 
@@ -672,7 +653,7 @@ struct HsSolver {
       double sig0[NW], g10[NW], zlu0[NW], W0[NW * NW];
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
-        BV b = bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
+        BoundTerms b = bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
         sig0[c] = b.sigma; g10[c] = b.g1; zlu0[c] = b.zlu;
       }
 #pragma unroll
@@ -743,31 +724,6 @@ struct HsSolver {
   // Forward sweep: step dz for theta = (1, mu, nu); also step-length limits and merit slope.
   // ------------------------------------------------------------------------------------------------
   struct FwdOut { double alpha_p, alpha_d, gphi; };
-
-  // accumulates gphi = grad(phi_mu)^T dz and the fraction-to-the-boundary limits for z (primal) and zL, zU (dual);
-  // branch-free, operands already in registers
-  MYR_HD static inline void step_limits(double zv, double l, double u, double zl, double zu, double d, double mu,
-                                        double wg_grad, double tau, FwdOut& fo) {
-    const bool fr = l < u;
-    const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-    const double sl = hl ? zv - l : 1.0, su = hu ? u - zv : 1.0;
-    const double zlv = hl ? zl : 1.0, zuv = hu ? zu : 1.0;
-    // five fp64 divisions instead of eight (each is a ~35-instruction sequence): one reciprocal per slack, one for the
-    // step component (only the bound the step moves towards can limit it)
-    const double rsl = detail::rcp_(sl), rsu = detail::rcp_(su);
-    double gb = wg_grad;
-    gb -= hl ? mu * rsl : 0.0;
-    gb += hu ? mu * rsu : 0.0;
-    const double dzl = -zlv + (mu - zlv * d) * rsl;
-    const double dzu = -zuv + (mu + zuv * d) * rsu;
-    const bool tol_ = hl && d < 0.0, tou_ = hu && d > 0.0;
-    const double ap_ = (tol_ || tou_) ? tau * (tol_ ? sl : su) * detail::rcp_(fabs(d)) : 1.0;
-    const double ad_l = (hl && dzl < 0.0) ? -tau * zlv * detail::rcp_(dzl) : 1.0;
-    const double ad_u = (hu && dzu < 0.0) ? -tau * zuv * detail::rcp_(dzu) : 1.0;
-    fo.alpha_p = detail::dmin(fo.alpha_p, ap_);
-    fo.alpha_d = detail::dmin(fo.alpha_d, detail::dmin(ad_l, ad_u));
-    fo.gphi += fr ? gb * d : 0.0;
-  }
 
   MYR_HD static void forward(const HsWork& w, const HsSolveOpts& o, const double* p, double mu, const double* nu,
                              const bool* term_pinned, FwdOut& fo) {
@@ -866,6 +822,8 @@ struct HsSolver {
         const long i = zi(K, j, c);
         zv[c] = w.z[i]; dv[c] = w.dz[i]; lv[c] = w.lb[i]; uv[c] = w.ub[i];
       }
+      // SlackLog of bound_rules.h, literal here: through the shared record some systems' lane kernels need a larger private segment
+      // (profiles/r14_bound_rules/README.md)
       double slk = 1.0; int sexp = 0;
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
@@ -877,7 +835,6 @@ struct HsSolver {
         { int e_; slk *= frexp((sl > 0.0 ? sl : 1.0) * (su > 0.0 ? su : 1.0), &e_); sexp += e_; }
         if (c < NS) x[c] = v; else u[c - NS] = v;
       }
-      // one log per point instead of 2 NW: slack pairs multiplied as mantissas, binary exponents summed (no under/overflow)
       bar -= log(slk) + sexp * 0.6931471805599453;
       Sys::f(x, u, p, ff);
       set_time<Sys>(p, 0.5 * h * j);
@@ -906,39 +863,18 @@ struct HsSolver {
     const double iks = 1.0 / ksig;
     for (int i = 0; i < n; ++i) {
       const double l = w.lb[i], u = w.ub[i], zv = w.z[i], d = w.dz[i], zl = w.zL[i], zu = w.zU[i];
-      const bool fr = l < u;
-      const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-      const double zn = fr ? zv + ap * d : zv;
-      const double sl = hl ? zv - l : 1.0, su = hu ? u - zv : 1.0;
-      const double snl = hl ? zn - l : 1.0, snu = hu ? u - zn : 1.0;
-      double vl = zl + ad * (-zl + (mu - zl * d) / sl);
-      double vu = zu + ad * (-zu + (mu + zu * d) / su);
-      const double ml = mu / snl, mu_ = mu / snu;        // one division per new slack; the safeguard band is [m / ksig, m ksig]
-      vl = detail::dmax(detail::dmin(vl, ksig * ml), ml * iks);
-      vu = detail::dmax(detail::dmin(vu, ksig * mu_), mu_ * iks);
-      w.z[i] = zn;
-      w.zL[i] = hl ? vl : 0.0;
-      w.zU[i] = hu ? vu : 0.0;
+      const BoundKind k = bound_kind(l, u);
+      const double zn = k.fr ? zv + ap * d : zv;
+      const BoundMult m = bound_accept<false>(k, l, u, zv, zn, d, zl, zu, ad, mu, ksig, iks);      // this core divides
+      w.z[i] = zn; w.zL[i] = m.zL; w.zU[i] = m.zU;
     }
   }
 
   // starting point: pinned variables on their value, the others pushed strictly inside their bounds
   MYR_HD static void init(const HsWork& w, int n) {
-    const double k1 = 1e-2, k2 = 1e-2;
     for (int i = 0; i < n; ++i) {
-      const double l = w.lb[i], u = w.ub[i], v0 = w.z[i];
-      const bool fr = l < u;
-      const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-      const double width = (hl && hu) ? (u - l) : INFINITY;
-      const double pl = detail::dmin(k1 * detail::dmax(1.0, fabs(l)), k2 * width);
-      const double pu = detail::dmin(k1 * detail::dmax(1.0, fabs(u)), k2 * width);
-      double v = v0;
-      v = hl ? detail::dmax(v, l + pl) : v;
-      v = hu ? detail::dmin(v, u - pu) : v;
-      v = fr ? v : l;
-      w.z[i] = v;
-      w.zL[i] = hl ? 1.0 : 0.0;
-      w.zU[i] = hu ? 1.0 : 0.0;
+      const BoundStart b = bound_start(w.z[i], w.lb[i], w.ub[i]);
+      w.z[i] = b.z; w.zL[i] = b.zL; w.zU[i] = b.zU;
     }
   }
 
@@ -980,6 +916,7 @@ struct IpLoop {
       // the bound multipliers join the sweep's sums here; the wavefront kernels get them from their linearisation pass
       double sm = so.sum_mult; int nm = so.n_mult;
       for (int i = 0; i < n; ++i) {
+        // mult_sum of bound_rules.h, literal here: through the function some systems' lane and shooting kernels need a larger private segment
         const double l = w.lb[i], u = w.ub[i], zl = w.zL[i], zu = w.zU[i];
         const bool fr = l < u;
         const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);

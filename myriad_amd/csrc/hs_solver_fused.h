@@ -512,7 +512,7 @@ struct HsFused {
   struct PRec { double x[NS], f[NS], A[NS * NS], B[NS * NU], own[NS]; };   // own = w_j dg/dx + (zU - zL)_x of the point
 
   // the accepted step applied to the NW variables of point j (network systems: a pass of its own in front of the matrix-core
-  // linearisation; same formulas as in lin_at)
+  // linearisation; the same bound_accept<true> as in lin_at)
   __device__ static inline void step_at(Ctx& c, const Step& st, int j, PRec&) {
     double bl[NW], bu[NW];
     load_bounds(c, j, bl, bu);
@@ -521,22 +521,15 @@ struct HsFused {
     for (int q = 0; q < NW; ++q) {
       const long i = zi(c, j, q);
       const double l = bl[q], u = bu[q], zv = c.z[i], d = c.dz[i], zl = c.zL[i], zu = c.zU[i];
-      const bool fr = l < u;
-      const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-      const double zn = fr ? fma(st.ap, d, zv) : zv;      // (an explicit fma: the network passes evaluate the trial point as fma(alpha, dz, z), and the stored activations must belong to THIS point)
-      const double sl = hl ? zv - l : 1.0, su = hu ? u - zv : 1.0;
-      const double snl = hl ? zn - l : 1.0, snu = hu ? u - zn : 1.0;
-      double vl = zl + st.ad * (-zl + (st.mu - zl * d) * detail::rcp_(sl));
-      double vu = zu + st.ad * (-zu + (st.mu + zu * d) * detail::rcp_(su));
-      const double ml = st.mu * detail::rcp_(snl), mu_ = st.mu * detail::rcp_(snu);
-      vl = detail::dmax(detail::dmin(vl, st.ksig * ml), ml * iks);
-      vu = detail::dmax(detail::dmin(vu, st.ksig * mu_), mu_ * iks);
-      c.z[i] = zn; c.zL[i] = hl ? vl : 0.0; c.zU[i] = hu ? vu : 0.0;
+      const BoundKind k = bound_kind(l, u);
+      const double zn = k.fr ? fma(st.ap, d, zv) : zv;    // (an explicit fma: the network passes evaluate the trial point as fma(alpha, dz, z), and the stored activations must belong to THIS point)
+      const BoundMult m = bound_accept<true>(k, l, u, zv, zn, d, zl, zu, st.ad, st.mu, st.ksig, iks);      // this kernel multiplies by rcp_
+      c.z[i] = zn; c.zL[i] = m.zL; c.zU[i] = m.zU;
     }
   }
 
   // One point of the backward phase: the accepted step of the previous iteration is applied on the values loaded anyway
-  // (same formulas, same order of operations as HsWave::points_lin), then dynamics + first derivatives, bound sums.
+  // (the same bound_accept<true> as HsWave::points_lin), then dynamics + first derivatives, bound sums.
   // Every lane runs it (uniform control flow: the callers use cross-lane moves); `live` gates stores and sums.
   __device__ static inline void lin_at(Ctx& c, const Step& st, int j, bool live, PRec& R, Acc& a) {
     typename S::VarBlk V;
@@ -554,17 +547,10 @@ struct HsFused {
       for (int q = 0; q < NW; ++q) {
         const long i = zi(c, j, q);
         const double l = V.l[q], u = V.u[q], zv = V.z[q], d = dv[q], zl = V.zl[q], zu = V.zu[q];
-        const bool fr = l < u;
-        const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-        const double zn = fr ? fma(st.ap, d, zv) : zv;      // (an explicit fma: the network passes evaluate the trial point as fma(alpha, dz, z), and the stored activations must belong to THIS point)
-        const double sl = hl ? zv - l : 1.0, su = hu ? u - zv : 1.0;
-        const double snl = hl ? zn - l : 1.0, snu = hu ? u - zn : 1.0;
-        double vl = zl + st.ad * (-zl + (st.mu - zl * d) * detail::rcp_(sl));
-        double vu = zu + st.ad * (-zu + (st.mu + zu * d) * detail::rcp_(su));
-        const double ml = st.mu * detail::rcp_(snl), mu_ = st.mu * detail::rcp_(snu);
-        vl = detail::dmax(detail::dmin(vl, st.ksig * ml), ml * iks);
-        vu = detail::dmax(detail::dmin(vu, st.ksig * mu_), mu_ * iks);
-        V.z[q] = zn; V.zl[q] = hl ? vl : 0.0; V.zu[q] = hu ? vu : 0.0;
+        const BoundKind k = bound_kind(l, u);
+        const double zn = k.fr ? fma(st.ap, d, zv) : zv;  // (the explicit fma of step_at)
+        const BoundMult m = bound_accept<true>(k, l, u, zv, zn, d, zl, zu, st.ad, st.mu, st.ksig, iks);
+        V.z[q] = zn; V.zl[q] = m.zL; V.zu[q] = m.zU;
         if (live) { c.z[i] = V.z[q]; c.zL[i] = V.zl[q]; c.zU[i] = V.zu[q]; }
       }
     }
@@ -588,21 +574,19 @@ struct HsFused {
       Sys::lin(R.x, u_, c.pp.get(), R.f, R.A, R.B, &g, gw);
     const double wj = wq(c.K, j, c.h);
     if (TRAP && j == c.K - 1) fold_terminal<Sys>(R.x, u_, c.pp.get(), wj, g, gw);   // trapezoidal.py:126-127
-    double cmax = a.cmax, cmin = a.cmin, sm = 0.0, slk = 1.0; int nm = 0, sexp = 0;
+    double cmax = a.cmax, cmin = a.cmin, sm = 0.0; int nm = 0;
+    SlackLog sl;       // one log per point (no violation count here)
 #pragma unroll
     for (int q = 0; q < NW; ++q) {
-      typename S::BV b = S::bound_terms(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], cmax, cmin);
+      BoundTerms b = bound_terms(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], cmax, cmin);
       if (q < NS) R.own[q < NS ? q : 0] = wj * gw[q] + b.zlu;
-      const bool fr = V.l[q] < V.u[q];
-      const bool hl = fr && (V.l[q] > -INFINITY), hu = fr && (V.u[q] < INFINITY);
-      sm += (hl ? V.zl[q] : 0.0) + (hu ? V.zu[q] : 0.0);
-      nm += (hl ? 1 : 0) + (hu ? 1 : 0);
-      const double sl = hl ? V.z[q] - V.l[q] : 1.0, su = hu ? V.u[q] - V.z[q] : 1.0;
-      { int e_; slk *= frexp((sl > 0.0 ? sl : 1.0) * (su > 0.0 ? su : 1.0), &e_); sexp += e_; }
+      const BoundKind k = bound_kind(V.l[q], V.u[q]);
+      mult_sum(k, V.zl[q], V.zu[q], sm, nm);
+      sl.add(k, V.z[q], V.l[q], V.u[q]);
     }
     if (live) {
       a.cmax = cmax; a.cmin = cmin; a.sm += sm; a.nm += nm;
-      a.lg -= log(slk) + sexp * 0.6931471805599453;
+      a.lg -= sl.value();
       a.f += wj * g;
     }
   }
@@ -1006,7 +990,7 @@ struct HsFused {
       double sig[NW], g1v[NW], zlu[NW], cmx = 0.0, cmn = INFINITY;
 #pragma unroll
       for (int q = 0; q < NW; ++q) {
-        typename S::BV b = S::bound_terms(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], cmx, cmn);
+        BoundTerms b = bound_terms(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], cmx, cmn);
         sig[q] = b.sigma; g1v[q] = b.g1; zlu[q] = b.zlu;
       }
 #pragma unroll
@@ -2013,7 +1997,7 @@ struct HsFused {
 #pragma unroll
       for (int q = 0; q < NW; ++q) {
         if (live) c.dz[zi(c, j, q)] = d[q];
-        S::step_limits(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], d[q], mu, wj * gw[q], tau, t);
+        step_limits(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], d[q], mu, wj * gw[q], tau, t);
       }
       if (live) l = t;
     };
@@ -2184,6 +2168,8 @@ struct HsFused {
   __device__ static inline void trial_point(Ctx& c, int j, double alpha, bool live, TPt& P, double& fa, double& ba, int& bad) {
     double u[NU], bl[NW], bu[NW];
     load_bounds(c, j, bl, bu);
+    // SlackLog of bound_rules.h, literal here: through the shared record this kernel's trial pass is compiled differently
+    // (profiles/r14_bound_rules/README.md)
     double slk = 1.0; int sexp = 0, bd = 0;
 #pragma unroll
     for (int q = 0; q < NW; ++q) {
@@ -2290,8 +2276,8 @@ struct HsFused {
 
   // ---- start: the caller's point pushed inside its bounds (HsWave::init), into LDS; bound table ---------------------------------
   __device__ static void init(Ctx& c, const double* zg) {
-    const double k1 = 1e-2, k2 = 1e-2;
-    const int K = c.K;
+    const double k1 = 1e-2, k2 = 1e-2;     // bound_start of bound_rules.h, literal here: through the function the stores of this loop are
+    const int K = c.K;                     // issued in another order (profiles/r14_bound_rules/README.md)
     int same = 1;
     for (int i = c.tid; i < c.n; i += NT) {
       const double l = c.lb[i], u = c.ub[i], v0 = zg[i];

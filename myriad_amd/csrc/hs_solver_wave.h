@@ -162,7 +162,7 @@ struct HsWave {
   struct P1 { double f, cmax, cmin, sm, lg; int nm; };   // lg = -sum log(slack): barrier term of the merit function / mu
   // The accepted step of the previous iteration is applied HERE, on the values this phase loads anyway (update() as a
   // phase of its own re-read six arrays and paid their latency sixteen rounds in a row): z += a_p dz, zL/zU += a_d d..,
-  // same formulas, same order of operations as update().
+  // by the same bound_accept<true> as update().
   struct Step { bool on; double ap, ad, mu, ksig; };
   __device__ static void points_lin(Ctx& c, P1& o, const Step& st) {
     if constexpr (MLP) {       // the network pass reads z from memory: apply the step first
@@ -173,7 +173,7 @@ struct HsWave {
     const double iks = 1.0 / st.ksig;
     for (int j = c.lane; j < c.K; j += 64) {
       typename S::VarBlk V;
-      double slk = 1.0; int sexp = 0;       // as in trial(): one log per point
+      SlackLog sl;                          // as in trial(): one log per point (no violation count here)
       if (!MLP && st.on) {
         double dv[NW];                        // all loads of the point before its first store (see points_hess)
 #pragma unroll
@@ -185,17 +185,10 @@ struct HsWave {
         for (int q = 0; q < NW; ++q) {
           const long i = zi(c, j, q);
           const double l = V.l[q], u = V.u[q], zv = V.z[q], d = dv[q], zl = V.zl[q], zu = V.zu[q];
-          const bool fr = l < u;
-          const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-          const double zn = fr ? zv + st.ap * d : zv;
-          const double sl = hl ? zv - l : 1.0, su = hu ? u - zv : 1.0;
-          const double snl = hl ? zn - l : 1.0, snu = hu ? u - zn : 1.0;
-          double vl = zl + st.ad * (-zl + (st.mu - zl * d) * detail::rcp_(sl));
-          double vu = zu + st.ad * (-zu + (st.mu + zu * d) * detail::rcp_(su));
-          const double ml = st.mu * detail::rcp_(snl), mu_ = st.mu * detail::rcp_(snu);
-          vl = detail::dmax(detail::dmin(vl, st.ksig * ml), ml * iks);
-          vu = detail::dmax(detail::dmin(vu, st.ksig * mu_), mu_ * iks);
-          V.z[q] = zn; V.l[q] = l; V.u[q] = u; V.zl[q] = hl ? vl : 0.0; V.zu[q] = hu ? vu : 0.0;
+          const BoundKind k = bound_kind(l, u);
+          const double zn = k.fr ? zv + st.ap * d : zv;
+          const BoundMult m = bound_accept<true>(k, l, u, zv, zn, d, zl, zu, st.ad, st.mu, st.ksig, iks);      // this kernel multiplies by rcp_
+          V.z[q] = zn; V.l[q] = l; V.u[q] = u; V.zl[q] = m.zL; V.zu[q] = m.zU;
           c.z[i] = V.z[q]; c.zL[i] = V.zl[q]; c.zU[i] = V.zu[q];
         }
       } else {
@@ -231,16 +224,13 @@ struct HsWave {
       for (int q = 0; q < NW; ++q) pt[(PF_GW + q) * K] = P.gw[q];
 #pragma unroll
       for (int q = 0; q < NW; ++q) {
-        typename S::BV b = S::bound_terms(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], cmax, cmin);
+        BoundTerms b = bound_terms(V.z[q], V.l[q], V.u[q], V.zl[q], V.zu[q], cmax, cmin);
         pt[(PF_SIG + q) * K] = b.sigma; pt[(PF_G1 + q) * K] = b.g1; pt[(PF_ZLU + q) * K] = b.zlu;
-        const bool fr = V.l[q] < V.u[q];
-        const bool hl = fr && (V.l[q] > -INFINITY), hu = fr && (V.u[q] < INFINITY);
-        sm += (hl ? V.zl[q] : 0.0) + (hu ? V.zu[q] : 0.0);
-        nm += (hl ? 1 : 0) + (hu ? 1 : 0);
-        const double sl = hl ? V.z[q] - V.l[q] : 1.0, su = hu ? V.u[q] - V.z[q] : 1.0;
-        { int e_; slk *= frexp((sl > 0.0 ? sl : 1.0) * (su > 0.0 ? su : 1.0), &e_); sexp += e_; }
+        const BoundKind k = bound_kind(V.l[q], V.u[q]);
+        mult_sum(k, V.zl[q], V.zu[q], sm, nm);
+        sl.add(k, V.z[q], V.l[q], V.u[q]);
       }
-      lg -= log(slk) + sexp * 0.6931471805599453;
+      lg -= sl.value();
       f += wq(K, j, c.h) * P.g;
     }
     o.f = wv_sum(f); o.cmax = wv_max(cmax); o.cmin = wv_min(cmin); o.sm = wv_sum(sm); o.nm = wv_isum(nm); o.lg = wv_sum(lg);
@@ -1247,7 +1237,7 @@ struct HsWave {
 #pragma unroll
       for (int q = 0; q < NW; ++q) {
         const long i = zi(c, j, q);
-        S::step_limits(c.z[i], c.lb[i], c.ub[i], c.zL[i], c.zU[i], c.dz[i], mu, wj * c.pt[(PF_GW + q) * c.K + j], tau, l);
+        step_limits(c.z[i], c.lb[i], c.ub[i], c.zL[i], c.zU[i], c.dz[i], mu, wj * c.pt[(PF_GW + q) * c.K + j], tau, l);
       }
     }
     fo.alpha_p = wv_min(l.alpha_p); fo.alpha_d = wv_min(l.alpha_d); fo.gphi = wv_sum(l.gphi);
@@ -1261,8 +1251,8 @@ struct HsWave {
     double fa = 0, ba = 0; int bad = 0;
     for (int j = c.lane; j < K; j += 64) {
       double x[NS], u[NU], ff[NS];
-      // one log per point instead of 2 NW (fp64 log is a long software sequence and dominated the trial): the slack
-      // pairs (z-l)(u-z) are multiplied as mantissas, their binary exponents summed, so no product can under- or overflow
+      // SlackLog of bound_rules.h (one log per point instead of 2 NW: the logs dominated the trial), literal here: through the shared record
+      // two systems' kernels need a larger private segment (profiles/r14_bound_rules/README.md)
       double slk = 1.0; int sexp = 0;
 #pragma unroll
       for (int q = 0; q < NW; ++q) {
@@ -1315,34 +1305,17 @@ struct HsWave {
     const double iks = 1.0 / ksig;
     for (int i = c.lane; i < c.n; i += 64) {
       const double l = c.lb[i], u = c.ub[i], zv = c.z[i], d = c.dz[i], zl = c.zL[i], zu = c.zU[i];
-      const bool fr = l < u;
-      const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-      const double zn = fr ? zv + ap * d : zv;
-      const double sl = hl ? zv - l : 1.0, su = hu ? u - zv : 1.0;
-      const double snl = hl ? zn - l : 1.0, snu = hu ? u - zn : 1.0;
-      double vl = zl + ad * (-zl + (mu - zl * d) * detail::rcp_(sl));
-      double vu = zu + ad * (-zu + (mu + zu * d) * detail::rcp_(su));
-      const double ml = mu * detail::rcp_(snl), mu_ = mu * detail::rcp_(snu);  // the safeguard band is [m / ksig, m ksig]
-      vl = detail::dmax(detail::dmin(vl, ksig * ml), ml * iks);
-      vu = detail::dmax(detail::dmin(vu, ksig * mu_), mu_ * iks);
-      c.z[i] = zn; c.zL[i] = hl ? vl : 0.0; c.zU[i] = hu ? vu : 0.0;
+      const BoundKind k = bound_kind(l, u);
+      const double zn = k.fr ? zv + ap * d : zv;
+      const BoundMult m = bound_accept<true>(k, l, u, zv, zn, d, zl, zu, ad, mu, ksig, iks);      // this kernel multiplies by rcp_
+      c.z[i] = zn; c.zL[i] = m.zL; c.zU[i] = m.zU;
     }
   }
 
   __device__ static void init(Ctx& c) {
-    const double k1 = 1e-2, k2 = 1e-2;
     for (int i = c.lane; i < c.n; i += 64) {
-      const double l = c.lb[i], u = c.ub[i], v0 = c.z[i];
-      const bool fr = l < u;
-      const bool hl = fr && (l > -INFINITY), hu = fr && (u < INFINITY);
-      const double width = (hl && hu) ? (u - l) : INFINITY;
-      const double pl = detail::dmin(k1 * detail::dmax(1.0, fabs(l)), k2 * width);
-      const double pu = detail::dmin(k1 * detail::dmax(1.0, fabs(u)), k2 * width);
-      double v = v0;
-      v = hl ? detail::dmax(v, l + pl) : v;
-      v = hu ? detail::dmin(v, u - pu) : v;
-      v = fr ? v : l;
-      c.z[i] = v; c.zL[i] = hl ? 1.0 : 0.0; c.zU[i] = hu ? 1.0 : 0.0;
+      const BoundStart b = bound_start(c.z[i], c.lb[i], c.ub[i]);
+      c.z[i] = b.z; c.zL[i] = b.zL; c.zU[i] = b.zU;
     }
     if (c.lane < ZR) c.zr[c.lane] = 0.0;
   }

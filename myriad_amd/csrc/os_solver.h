@@ -248,7 +248,7 @@ struct TrapCore {
       double sig_e[NW], g1_e[NW], zlu_e[NW];
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
-        typename H::BV b = H::bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
+        BoundTerms b = bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
         sig_e[c] = b.sigma; g1_e[c] = b.g1; zlu_e[c] = b.zlu;
       }
       // E = I - h/2 A_e   (= -dc_j/dx_{j+1})
@@ -338,7 +338,7 @@ struct TrapCore {
       double sig0[NW], g10[NW], zlu0[NW], W0[NW * NW];
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
-        typename H::BV b = H::bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
+        BoundTerms b = bound_terms(Ve.z[c], Ve.l[c], Ve.u[c], Ve.zl[c], Ve.zu[c], so.compl_max, so.compl_min);
         sig0[c] = b.sigma; g10[c] = b.g1; zlu0[c] = b.zlu;
       }
 #pragma unroll
@@ -388,7 +388,7 @@ struct TrapCore {
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
         w.dz[zi(Kp, j, c)] = d[c];
-        H::step_limits(V.z[c], V.l[c], V.u[c], V.zl[c], V.zu[c], d[c], mu, wj * gw[c], tau, fo);
+        step_limits(V.z[c], V.l[c], V.u[c], V.zl[c], V.zu[c], d[c], mu, wj * gw[c], tau, fo);
       }
     };
     apply(0, s);
@@ -430,19 +430,15 @@ struct TrapCore {
       double zv[NW], dv[NW], lv[NW], uv[NW];
 #pragma unroll
       for (int c = 0; c < NW; ++c) { const long i = zi(Kp, j, c); zv[c] = w.z[i]; dv[c] = w.dz[i]; lv[c] = w.lb[i]; uv[c] = w.ub[i]; }
-      double slk = 1.0; int sexp = 0;
+      SlackLog sl;       // one log per point
 #pragma unroll
       for (int c = 0; c < NW; ++c) {
         const double v = zv[c] + alpha * dv[c];
-        const bool fr = lv[c] < uv[c];
-        const bool hl = fr && (lv[c] > -INFINITY), hu = fr && (uv[c] < INFINITY);
-        const double sl = hl ? v - lv[c] : 1.0, su = hu ? uv[c] - v : 1.0;
-        bad += (sl > 0.0 ? 0 : 1) + (su > 0.0 ? 0 : 1);
-        { int e_; slk *= frexp((sl > 0.0 ? sl : 1.0) * (su > 0.0 ? su : 1.0), &e_); sexp += e_; }
+        sl.add(bound_kind(lv[c], uv[c]), v, lv[c], uv[c]);
         if (c < NS) x[c] = v; else u[c - NS] = v;
       }
-      // one log per point instead of 2 NW: slack pairs multiplied as mantissas, binary exponents summed (no under/overflow)
-      bar -= log(slk) + sexp * 0.6931471805599453;
+      bad += sl.bad;
+      bar -= sl.value();
       Sys::f(x, u, p, ff);
       set_time<Sys>(p, h * j);
       double gj = Sys::g(x, u, p);
@@ -844,7 +840,7 @@ struct ShootCore {
   // own (bound) terms of one decision variable
   struct Own { double sigma, g1, zlu; bool pinned; };
   MYR_HD static inline Own own_of(const HsWork& w, long i, SweepOut& so) {
-    typename H::BV b = H::bound_terms(w.z[i], w.lb[i], w.ub[i], w.zL[i], w.zU[i], so.compl_max, so.compl_min);
+    BoundTerms b = bound_terms(w.z[i], w.lb[i], w.ub[i], w.zL[i], w.zU[i], so.compl_max, so.compl_min);
     Own r; r.sigma = b.sigma; r.g1 = b.g1; r.zlu = b.zlu; r.pinned = b.pinned;
     return r;
   }
@@ -1005,7 +1001,7 @@ struct ShootCore {
       for (int a = 0; a < NU; ++a) {
         so.stat = dmax(so.stat, fabs(ru_c[a]));
         double cm = 0, cn = INFINITY;
-        typename H::BV b = H::bound_terms(w.z[ui(o, 0, a)], w.lb[ui(o, 0, a)], w.ub[ui(o, 0, a)], w.zL[ui(o, 0, a)], w.zU[ui(o, 0, a)], cm, cn);
+        BoundTerms b = bound_terms(w.z[ui(o, 0, a)], w.lb[ui(o, 0, a)], w.ub[ui(o, 0, a)], w.zL[ui(o, 0, a)], w.zU[ui(o, 0, a)], cm, cn);
 #pragma unroll
         for (int b2 = 0; b2 < NU; ++b2) Huu[a * NU + b2] = (a == b2) ? b.sigma + delta : 0.0;
         g0u[a] = 0.0; g1u[a] = b.g1;
@@ -1031,7 +1027,7 @@ struct ShootCore {
     for (int c = 0; c < NS; ++c) { s[c] = 0.0; w.dz[xi(0, c)] = 0.0; }
     auto setvar = [&](long i, double d) {
       w.dz[i] = d;
-      H::step_limits(w.z[i], w.lb[i], w.ub[i], w.zL[i], w.zU[i], d, mu, 0.0, tau, fo);
+      step_limits(w.z[i], w.lb[i], w.ub[i], w.zL[i], w.zU[i], d, mu, 0.0, tau, fo);
     };
 #pragma unroll
     for (int a = 0; a < NU; ++a) {
@@ -1088,11 +1084,7 @@ struct ShootCore {
     auto val = [&](long i) -> double {
       const double v = w.z[i] + alpha * w.dz[i];
       const double l = w.lb[i], ub = w.ub[i];
-      const bool fr = l < ub;
-      const bool hl = fr && (l > -INFINITY), hu = fr && (ub < INFINITY);
-      const double sl = hl ? v - l : 1.0, su = hu ? ub - v : 1.0;
-      bad += (sl > 0.0 ? 0 : 1) + (su > 0.0 ? 0 : 1);
-      bar -= log((sl > 0.0 ? sl : 1.0) * (su > 0.0 ? su : 1.0));     // one log per variable (sl + su = u - l: the pair cannot underflow)
+      bar -= log(slack_pair(bound_kind(l, ub), v, l, ub, bad));     // one log per variable (sl + su = u - l: the pair cannot underflow)
       return v;
     };
     double uc[(M + 1) * NU];

@@ -142,7 +142,7 @@ struct ShootWave {
 
   // ---- lanes over variables: starting point and accepted step (HsSolver::init / update, one variable per lane) ----
   __device__ static void init(const HsWork& w, int n) {
-    const double k1 = 1e-2, k2 = 1e-2;
+    const double k1 = 1e-2, k2 = 1e-2;      // bound_start of bound_rules.h, literal here: through the function two systems' kernels need a larger private segment
     sw_lds* z = (sw_lds*)w.z.p; sw_lds* lb = (sw_lds*)w.lb.p; sw_lds* ub = (sw_lds*)w.ub.p; sw_lds* zL = (sw_lds*)w.zL.p; sw_lds* zU = (sw_lds*)w.zU.p;
     for (int i = threadIdx.x; i < n; i += 64) {
       const double l = lb[i], u = ub[i], v0 = z[i];
@@ -172,19 +172,10 @@ struct ShootWave {
     const bool reuse = ex[X_TA] == ap && ap > 0.0;
     for (int i = threadIdx.x; i < n; i += 64) {
       const double lo = l.lb[i], u = l.ub[i], zv = l.z[i], d = l.dz[i], zl = l.zL[i], zu = l.zU[i];
-      const bool fr = lo < u;
-      const bool hl = fr && (lo > -INFINITY), hu = fr && (u < INFINITY);
-      const double zn = fr ? (reuse ? l.zt[i] : zv + ap * d) : zv;
-      const double sl = hl ? zv - lo : 1.0, su = hu ? u - zv : 1.0;
-      const double snl = hl ? zn - lo : 1.0, snu = hu ? u - zn : 1.0;
-      double vl = zl + ad * (-zl + (mu - zl * d) / sl);
-      double vu = zu + ad * (-zu + (mu + zu * d) / su);
-      const double ml = mu / snl, mu_ = mu / snu;
-      vl = detail::dmax(detail::dmin(vl, ksig * ml), ml * iks);
-      vu = detail::dmax(detail::dmin(vu, ksig * mu_), mu_ * iks);
-      l.z[i] = zn;
-      l.zL[i] = hl ? vl : 0.0;
-      l.zU[i] = hu ? vu : 0.0;
+      const BoundKind k = bound_kind(lo, u);
+      const double zn = k.fr ? (reuse ? l.zt[i] : zv + ap * d) : zv;      // the stored trial point where the step was the last trial
+      const BoundMult m = bound_accept<false>(k, lo, u, zv, zn, d, zl, zu, ad, mu, ksig, iks);      // divides, as the lane core
+      l.z[i] = zn; l.zL[i] = m.zL; l.zU[i] = m.zU;
     }
     if (reuse) {
       const int S = steps(od);
@@ -561,7 +552,7 @@ struct ShootWave {
       // own (bound) terms of every variable
       double cmax = 0, cmin = INFINITY;
       for (int v = lane; v < n; v += 64) {
-        typename H::BV b = H::bound_terms(l.z[v], l.lb[v], l.ub[v], l.zL[v], l.zU[v], cmax, cmin);
+        BoundTerms b = bound_terms(l.z[v], l.lb[v], l.ub[v], l.zL[v], l.zU[v], cmax, cmin);
         l.sig[v] = b.sigma; l.g1[v] = b.g1; l.zlu[v] = b.zlu;
         // terminal state pinned?  Decided HERE, lane-divergently: as a wave-uniform select in the one-lane phase below,
         // ROCm 7.2's hipcc lowered `pinned ? 1.0 : 0.0` to v_cmp_nlt_f64 vcc ; s_cselect_b32 -- a select on SCC, which the
@@ -989,7 +980,7 @@ struct ShootWave {
     __syncthreads();
     FwdOut fl; fl.alpha_p = 1.0; fl.alpha_d = 1.0; fl.gphi = 0.0;
     for (int v = NS + lane; v < n; v += 64)       // every variable but x_0 (ShootCore::forward sets dz = 0 there, no limits)
-      H::step_limits(l.z[v], l.lb[v], l.ub[v], l.zL[v], l.zU[v], l.dz[v], mu, 0.0, tau, fl);
+      step_limits(l.z[v], l.lb[v], l.ub[v], l.zL[v], l.zU[v], l.dz[v], mu, 0.0, tau, fl);
     fo.alpha_p = wv_min(fl.alpha_p); fo.alpha_d = wv_min(fl.alpha_d); fo.gphi = wv_sum(gphi + fl.gphi);
     __syncthreads();
     MYR_SWTF(5)
@@ -1008,11 +999,7 @@ struct ShootWave {
     for (int i = lane; i < n; i += 64) {
       const double v = l.z[i] + alpha * l.dz[i];
       const double lo = l.lb[i], ub = l.ub[i];
-      const bool fr = lo < ub;
-      const bool hl = fr && (lo > -INFINITY), hu = fr && (ub < INFINITY);
-      const double sl = hl ? v - lo : 1.0, su = hu ? ub - v : 1.0;
-      bad += (sl > 0.0 ? 0 : 1) + (su > 0.0 ? 0 : 1);
-      bl -= log((sl > 0.0 ? sl : 1.0) * (su > 0.0 ? su : 1.0));
+      bl -= log(slack_pair(bound_kind(lo, ub), v, lo, ub, bad));      // one log per variable
       if (!at_z) l.zt[i] = v;
     }
     if (at_z) {

@@ -244,3 +244,60 @@ extern "C" int hostsim_policy_record(const double* in, double* sv, double* back)
   for (int i = 0; i < NMMAX; ++i) back[21 + i] = rhist[i];
   return IpState<4>::RECORD;
 }
+
+// ---- the bound rules (myriad_amd/csrc/bound_rules.h) on plain arrays of cases: tests/test_hostsim.py restates each rule ----
+// out[3 i ..] = z, zL, zU of the starting point of case i
+extern "C" void hostsim_bound_start(int n, const double* v0, const double* l, const double* u, double* out) {
+  for (int i = 0; i < n; ++i) {
+    const BoundStart b = bound_start(v0[i], l[i], u[i]);
+    out[3 * i] = b.z; out[3 * i + 1] = b.zL; out[3 * i + 2] = b.zU;
+  }
+}
+
+// the accepted step of case i with zn = zv + ap d formed here, as HsSolver::update forms it; rcp selects bound_accept<true>;
+// out[3 i ..] = zn, zL, zU
+extern "C" void hostsim_bound_accept(int n, int rcp, const double* l, const double* u, const double* zv, const double* d, const double* zl,
+                                     const double* zu, const double* ap, const double* ad, const double* mu, const double* ksig, double* out) {
+  for (int i = 0; i < n; ++i) {
+    const BoundKind k = bound_kind(l[i], u[i]);
+    const double zn = k.fr ? zv[i] + ap[i] * d[i] : zv[i], iks = 1.0 / ksig[i];
+    const BoundMult m = rcp ? bound_accept<true>(k, l[i], u[i], zv[i], zn, d[i], zl[i], zu[i], ad[i], mu[i], ksig[i], iks)
+                            : bound_accept<false>(k, l[i], u[i], zv[i], zn, d[i], zl[i], zu[i], ad[i], mu[i], ksig[i], iks);
+    out[3 * i] = zn; out[3 * i + 1] = m.zL; out[3 * i + 2] = m.zU;
+  }
+}
+
+// out[6 i ..] = sigma, g1, zlu, pinned, and the complementarity extremes as case i leaves them when they arrive as cmax[i], cmin[i]
+extern "C" void hostsim_bound_terms(int n, const double* zv, const double* l, const double* u, const double* zl, const double* zu,
+                                    const double* cmax, const double* cmin, double* out) {
+  for (int i = 0; i < n; ++i) {
+    double cx = cmax[i], cn = cmin[i];
+    const BoundTerms b = bound_terms(zv[i], l[i], u[i], zl[i], zu[i], cx, cn);
+    out[6 * i] = b.sigma; out[6 * i + 1] = b.g1; out[6 * i + 2] = b.zlu; out[6 * i + 3] = b.pinned ? 1.0 : 0.0; out[6 * i + 4] = cx; out[6 * i + 5] = cn;
+  }
+}
+
+// out[3 i ..] = alpha_p, alpha_d, gphi of case i alone (from 1, 1, 0)
+extern "C" void hostsim_step_limits(int n, const double* zv, const double* l, const double* u, const double* zl, const double* zu, const double* d,
+                                    const double* mu, const double* wg, const double* tau, double* out) {
+  struct { double alpha_p, alpha_d, gphi; } fo;
+  for (int i = 0; i < n; ++i) {
+    fo.alpha_p = 1.0; fo.alpha_d = 1.0; fo.gphi = 0.0;
+    step_limits(zv[i], l[i], u[i], zl[i], zu[i], d[i], mu[i], wg[i], tau[i], fo);
+    out[3 * i] = fo.alpha_p; out[3 * i + 1] = fo.alpha_d; out[3 * i + 2] = fo.gphi;
+  }
+}
+
+// n points of k variables each: out[4 p ..] = value(), slk, sexp, bad of point p; pairs[p k + i] = slack_pair of its variable i
+extern "C" void hostsim_slack_log(int n, int k, const double* v, const double* l, const double* u, double* out, double* pairs) {
+  for (int p = 0; p < n; ++p) {
+    SlackLog s;
+    int bad = 0;
+    for (int i = p * k; i < (p + 1) * k; ++i) {
+      const BoundKind kd = bound_kind(l[i], u[i]);
+      s.add(kd, v[i], l[i], u[i]);
+      pairs[i] = slack_pair(kd, v[i], l[i], u[i], bad);
+    }
+    out[4 * p] = s.value(); out[4 * p + 1] = s.slk; out[4 * p + 2] = s.sexp; out[4 * p + 3] = s.bad == bad ? s.bad : -1;
+  }
+}

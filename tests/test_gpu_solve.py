@@ -369,3 +369,83 @@ def test_solve_x0_rejects_bad_arguments():
     eng.solve_x0(np.zeros((2, eng.ns)), g[:-1], g, g, g)
   rc = eng.lib.myr_solve_x0(eng._h, 2, None, None, None, None, None, None, 0, None, None, None, None, None, None, None, _lib.MEM_HOST)
   assert rc != 0 and b"myr_solve_x0" in eng.lib.myr_last_error()
+
+
+_BOUND_FORMS = {"lane": {"MYRIAD_SOLVE_MODE": "lane"}, "wave1": {"MYRIAD_SOLVE_MODE": "wave1"}, "fused1": {"MYRIAD_FUSED_WAVES": "1"}, "fused2": {"MYRIAD_FUSED_WAVES": "2"}}
+_bound_ref = {}      # per rule: the inputs of the transcription and the lane form's solution under its own bounds, computed once
+
+
+def _bound_solve(monkeypatch, form, rule, z0, lb, ub, max_iter=300):
+  from myriad_amd.config import Config, HParams, NLPSolverType, OptimizerType, QuadratureRule
+  from myriad_amd.systems import SystemType
+  from myriad_amd.trajectory_optimizers import get_optimizer
+  for k in ("MYRIAD_FUSED_WAVES", "MYRIAD_SOLVE_MODE", "MYRIAD_POISON", "MYRIAD_PARK_ITER", "MYRIAD_NODE_COOP", "MYRIAD_NODE_WPB", "MYRIAD_NODE_HELPERS"):
+    monkeypatch.delenv(k, raising=False)
+  monkeypatch.setenv("MYRIAD_SECOND_STARTS", "0"); monkeypatch.setenv("MYRIAD_ELASTIC", "0")
+  for k, v in _BOUND_FORMS[form].items():
+    monkeypatch.setenv(k, v)
+  hp = HParams(system=SystemType.VANDERPOL, optimizer=OptimizerType.COLLOCATION, quadrature_rule=QuadratureRule[rule], intervals=6, nlpsolver=NLPSolverType.SQP)
+  opt = get_optimizer(hp, Config(verbose=False, plot=False), hp.system())
+  p = opt.system.device_params()
+  if z0 is None:
+    x0 = np.tile(opt.system.x_0, (3, 1)) * (1.0 + 0.01 * np.arange(3)[:, None])
+    z0, lb, ub = opt.batch_inputs(x0, p)
+  o = opt.engine.default_opts()
+  o.max_iter = max_iter
+  res = opt.engine.solve(z0, lb, ub, params=p, opts=o)
+  out = {k: np.array(res[k]) for k in ("z", "cost", "status", "iters")}
+  opt.engine.close()
+  return out, (z0, lb, ub)
+
+
+@pytest.mark.parametrize("bounds", ["A", "B"])
+@pytest.mark.parametrize("rule", ["HERMITE_SIMPSON", "TRAPEZOIDAL"])
+def test_every_bound_class_in_every_solver_form(monkeypatch, rule, bounds):
+  """The problems of the suite never hand the solver a one-sided or an absent bound through the caller's arrays; the bound rules (csrc/bound_rules.h)
+  treat each class on its own.  VANDERPOL, N = 6, B = 3 (start states x_0 (1 + 0.01 b), pinned at knot 0), both collocation rules, from x*, u* of the lane
+  form under the transcription's own bounds:
+    A: at every knot >= 1 state 0 upper-only at 0.9 max x*_0 and state 1 lower-only at 0.9 min x*_1 (both become active), both states of knot 2 free on both
+       sides, the controls two-sided as they are;
+    B: the transcription's bounds with control knot 3 pinned at u*_3
+  -- together pinned, lower only, upper only, two-sided and free.  The lane form converges on every instance (on the host twin, the lane kernel's source:
+  A in 16 iterations with Hermite-Simpson and 11 trapezoidal, one active knot on each one-sided bound; B in 9 and 6).  Round 2's wavefront kernel and the
+  fused kernel with one and two wavefronts against it, with the assertions of test_tile_sweeps_at_ring_edge_horizons: after two iterations the same
+  finiteness pattern and iterates within 1e-7 relative; whole solves: equal status, cost to 1e-8 relative.  (A and B are not combined: with a pinned control
+  knot AND one-sided state bounds the lane solver ends at its iteration limit, on the host twin as well -- profiles/r14_bound_rules/README.md.)"""
+  if rule not in _bound_ref:
+    _bound_ref[rule] = _bound_solve(monkeypatch, "lane", rule, None, None, None)
+  ref, (z0, lb0, ub0) = _bound_ref[rule]
+  assert (ref["status"] == 0).all(), (rule, ref["status"])
+  K, ns = (13 if rule == "HERMITE_SIMPSON" else 7), 2
+  xs, us = ref["z"][:, :K * ns].reshape(3, K, ns), ref["z"][:, K * ns:]
+  lb, ub = lb0.copy(), ub0.copy()
+  if bounds == "A":
+    l, u = lb[:, :K * ns].reshape(3, K, ns), ub[:, :K * ns].reshape(3, K, ns)      # (views: the edits below land in lb, ub)
+    l[:, 1:, 0] = -np.inf; u[:, 1:, 0] = 0.9 * xs[:, 1:, 0].max(axis=1)[:, None]
+    l[:, 1:, 1] = 0.9 * xs[:, 1:, 1].min(axis=1)[:, None]; u[:, 1:, 1] = np.inf
+    l[:, 2, :] = -np.inf; u[:, 2, :] = np.inf
+    assert (u[:, 1, 0] < xs[:, 1:, 0].max(axis=1)).all() and (l[:, 1, 1] > xs[:, 1:, 1].min(axis=1)).all()      # both cut the unconstrained optimum off
+  else:
+    lb[:, K * ns + 3] = us[:, 3]; ub[:, K * ns + 3] = us[:, 3]
+  free = lb < ub
+  print(rule, bounds, "classes: pinned", int((~free).sum()), "lower only", int((free & np.isfinite(lb) & ~np.isfinite(ub)).sum()), "upper only",
+        int((free & ~np.isfinite(lb) & np.isfinite(ub)).sum()), "two-sided", int((free & np.isfinite(lb) & np.isfinite(ub)).sum()), "free",
+        int((free & ~np.isfinite(lb) & ~np.isfinite(ub)).sum()))
+  lane2 = _bound_solve(monkeypatch, "lane", rule, z0, lb, ub, max_iter=2)[0]
+  lane = _bound_solve(monkeypatch, "lane", rule, z0, lb, ub)[0]
+  print(rule, bounds, "lane: status", lane["status"], "iters", lane["iters"], "cost", lane["cost"])
+  assert (lane["status"] == 0).all(), (rule, bounds, lane["status"], lane["iters"])
+  if bounds == "A":
+    up, lo = free & ~np.isfinite(lb) & np.isfinite(ub), free & np.isfinite(lb) & ~np.isfinite(ub)
+    assert ((np.abs(lane["z"] - ub) < 1e-4) & up).any(axis=1).all() and ((np.abs(lane["z"] - lb) < 1e-4) & lo).any(axis=1).all()      # a one-sided bound of each kind is active
+  for form in ("wave1", "fused1", "fused2"):
+    w = _bound_solve(monkeypatch, form, rule, z0, lb, ub, max_iter=2)[0]
+    fin = np.isfinite(w["z"]) & np.isfinite(lane2["z"])
+    d = np.abs(w["z"] - lane2["z"])[fin] / np.maximum(1.0, np.abs(lane2["z"])[fin])
+    print(rule, bounds, form, "iterates after 2 iterations: max relative difference", d.max(initial=0.0))
+    assert d.max(initial=0.0) <= 1e-7, (rule, bounds, form, d.max())
+    assert np.array_equal(np.isfinite(w["z"]), np.isfinite(lane2["z"]))
+    w = _bound_solve(monkeypatch, form, rule, z0, lb, ub)[0]
+    print(rule, bounds, form, "status", w["status"], lane["status"], "iters", w["iters"], lane["iters"], "cost", w["cost"], lane["cost"])
+    assert np.array_equal(w["status"], lane["status"]), (rule, bounds, form, w["status"], lane["status"], w["iters"], lane["iters"])
+    np.testing.assert_allclose(w["cost"], lane["cost"], rtol=1e-8, atol=0.0)

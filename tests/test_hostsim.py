@@ -351,3 +351,225 @@ def test_policy_park_record_round_trip(sim):
   fields[12] = 0.0
   sim.hostsim_policy_record(A(fields), A(sv), A(back))
   assert sv[12] == 0.0 and back[12] == 0.0
+
+
+# ---- the bound rules (myriad_amd/csrc/bound_rules.h): the treatment of one bounded variable that every solver form shares, restated here in
+# the same operation order on IEEE doubles (numpy scalars: a division by zero gives inf as in C).  The twin is built without -march, so
+# nothing is contracted into an fma, and on the host rcp_(x) is 1.0 / x: the exact rules must agree bit for bit (NaN where the twin has NaN).
+F = np.float64
+INF, NAN = F(np.inf), F(np.nan)
+dmax = lambda a, b: a if a > b else b
+dmin = lambda a, b: a if a < b else b
+
+
+def _kind(l, u):
+  fr = bool(l < u)
+  return fr, fr and bool(l > -INF), fr and bool(u < INF)
+
+
+def _bound_cases():
+  """(l, u, zv) of every bound class -- pinned, lower only, upper only, two-sided, free, a NaN bound -- with slacks from 1e-300 to 1e300"""
+  rng = np.random.default_rng(14)
+  slacks = [1e-300, 1e-200, 3e-17, 1e-8, 0.25, 1.0, 7.0, 1e8, 1e150, 1e300]
+  c = [(1.5, 1.5, 1.5), (0.0, 0.0, 0.3), (2.0, 1.0, 1.5), (-INF, INF, 0.7), (-INF, INF, -1e300), (-INF, -INF, 0.0), (INF, INF, 0.0),
+       (NAN, 1.0, 0.5), (0.0, NAN, 0.5), (NAN, NAN, 0.5)]
+  for s in slacks:
+    c += [(0.0, INF, s), (-INF, 0.0, -s), (0.0, 1e300, s), (-1e300, 0.0, -s), (0.0, 2.0 * s, s)]
+    c += [(1.0, INF, 1.0 + s), (-INF, -1.0, -1.0 - s)]      # (the slack is rounded at the small sizes: still the twin's operands)
+  c += [(0.0, INF, -1e-3), (-INF, 0.0, 1e-3), (0.0, 1.0, 1.0), (0.0, 1.0, 0.0), (0.0, 1.0, 2.0)]      # on and beyond a bound
+  for _ in range(60):
+    l, w = rng.normal() * 10.0 ** rng.integers(-3, 4), 10.0 ** rng.uniform(-6, 3)
+    t = rng.uniform(0.0, 1.0)
+    kind = rng.integers(0, 4)
+    c.append((l if kind & 1 else -INF, l + w if kind & 2 else INF, l + t * w))
+  return [tuple(F(x) for x in t) for t in c]
+
+
+BOUND_CASES = _bound_cases()
+
+
+def _cols(rows):
+  return [np.ascontiguousarray(np.array(r, dtype=np.float64)) for r in zip(*rows)]
+
+
+def _start_rule(v0, l, u):
+  k1 = k2 = F(1e-2)
+  fr, hl, hu = _kind(l, u)
+  width = (u - l) if (hl and hu) else INF
+  pl = dmin(k1 * dmax(F(1.0), abs(l)), k2 * width)
+  pu = dmin(k1 * dmax(F(1.0), abs(u)), k2 * width)
+  v = v0
+  v = dmax(v, l + pl) if hl else v
+  v = dmin(v, u - pu) if hu else v
+  v = v if fr else l
+  return v, F(1.0 if hl else 0.0), F(1.0 if hu else 0.0)
+
+
+def test_bound_start_rule(sim):
+  """every bound class, the caller's value inside, on and outside the bounds: z, zL, zU bit for bit"""
+  rows = [(v0, l, u) for (l, u, zv) in BOUND_CASES for v0 in (zv, l, u, F(-3.0), F(1e5), zv + F(1e-3))]
+  v0, l, u = _cols(rows)
+  out = np.zeros(3 * len(rows))
+  sim.hostsim_bound_start.argtypes = [C.c_int] + [C.c_void_p] * 4
+  sim.hostsim_bound_start(len(rows), A(v0), A(l), A(u), A(out))
+  with np.errstate(all="ignore"):
+    want = np.array([_start_rule(*r) for r in rows]).ravel()
+  np.testing.assert_array_equal(out, want)
+  assert {_kind(l, u) for (_, l, u) in rows} == {(False, False, False), (True, True, False), (True, False, True), (True, True, True), (True, False, False)}
+  assert np.isnan(out).any()      # (a NaN bound pins the variable on it)
+
+
+def _accept_rule(rcp, l, u, zv, d, zl, zu, ap, ad, mu, ksig):
+  div = (lambda x, s: x * (F(1.0) / s)) if rcp else (lambda x, s: x / s)
+  iks = F(1.0) / ksig
+  fr, hl, hu = _kind(l, u)
+  zn = zv + ap * d if fr else zv
+  sl, su = (zv - l if hl else F(1.0)), (u - zv if hu else F(1.0))
+  snl, snu = (zn - l if hl else F(1.0)), (u - zn if hu else F(1.0))
+  vl = zl + ad * (-zl + div(mu - zl * d, sl))
+  vu = zu + ad * (-zu + div(mu + zu * d, su))
+  ml, mu_ = div(mu, snl), div(mu, snu)
+  vl = dmax(dmin(vl, ksig * ml), ml * iks)
+  vu = dmax(dmin(vu, ksig * mu_), mu_ * iks)
+  return zn, (vl if hl else F(0.0)), (vu if hu else F(0.0))
+
+
+def _step_rows():
+  """the bound cases x steps towards and away from each bound x ad in {0, 1} x ksig = 1e10 and 1 (both ends of the band bind) x two mu"""
+  rng = np.random.default_rng(15)
+  rows = []
+  for (l, u, zv) in BOUND_CASES:
+    for d in (F(-0.5), F(0.5), F(0.0), F(-1e-3) * abs(zv), F(2.0) * abs(zv)):
+      for ad in (F(0.0), F(1.0)):
+        for ksig in (F(1e10), F(1.0)):
+          rows.append((l, u, zv, d, F(rng.uniform(0.1, 3.0)), F(10.0 ** rng.uniform(-9, 2)), F(rng.uniform(0.0, 1.0)), ad, F(10.0 ** rng.integers(-9, 0)), ksig))
+  for (l, u, zv) in BOUND_CASES[-60:]:
+    rows.append((l, u, zv, F(rng.normal()), F(10.0 ** rng.uniform(-6, 2)), F(10.0 ** rng.uniform(-6, 2)), F(rng.uniform(0.0, 1.0)), F(rng.uniform(0.0, 1.0)),
+                 F(10.0 ** rng.uniform(-9, 0)), F(10.0 ** rng.uniform(0.0, 10.0))))
+  return rows
+
+
+STEP_ROWS = _step_rows()      # (l, u, zv, d, zl, zu, ap, ad, mu, ksig)
+
+
+@pytest.fixture(scope="module")
+def accepted(sim):
+  cols = _cols(STEP_ROWS)
+  sim.hostsim_bound_accept.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 11
+  got = {}
+  for rcp in (0, 1):
+    out = np.zeros(3 * len(STEP_ROWS))
+    sim.hostsim_bound_accept(len(STEP_ROWS), rcp, *[A(c) for c in cols], A(out))
+    got[rcp] = out
+  return got
+
+
+@pytest.mark.parametrize("rcp", [0, 1])
+def test_bound_accept_rule(accepted, rcp):
+  """new multipliers and their kappa_sigma band, dividing (rcp = 0) and multiplying by the reciprocal (rcp = 1): bit for bit"""
+  with np.errstate(all="ignore"):
+    want = np.array([_accept_rule(rcp, *r) for r in STEP_ROWS]).ravel()
+  np.testing.assert_array_equal(accepted[rcp], want)
+  # the flag is wired: some case has other bits with the reciprocal; and the band binds at both ends where ksig = 1
+  assert (accepted[0].view(np.int64) != accepted[1].view(np.int64)).sum() > 0      # (bit patterns: a NaN does not count as a difference)
+  one = np.array([r[9] == 1.0 and _kind(r[0], r[1])[1] and r[7] == 1.0 for r in STEP_ROWS])
+  zl = accepted[rcp].reshape(-1, 3)[:, 1]
+  with np.errstate(all="ignore"):
+    m = np.array([(r[8] * (F(1.0) / (r[2] + r[6] * r[3] - r[0])) if rcp else r[8] / (r[2] + r[6] * r[3] - r[0])) for r in STEP_ROWS])
+  assert one.sum() > 50 and (zl[one] == m[one]).all()
+
+
+def _terms_rule(zv, l, u, zl, zu, cmax, cmin):
+  fr, hl, hu = _kind(l, u)
+  sl, su = (zv - l if hl else F(1.0)), (u - zv if hu else F(1.0))
+  zlv, zuv = (zl if hl else F(0.0)), (zu if hu else F(0.0))
+  il, iu = (F(1.0) / sl if hl else F(0.0)), (F(1.0) / su if hu else F(0.0))
+  cl, cu = sl * zlv, su * zuv
+  cmax = dmax(cmax, dmax(cl if hl else cmax, cu if hu else cmax))
+  cmin = dmin(cmin, dmin(cl if hl else cmin, cu if hu else cmin))
+  return zlv * il + zuv * iu, iu - il, zuv - zlv, F(0.0 if fr else 1.0), cmax, cmin
+
+
+def test_bound_terms_rule(sim):
+  """barrier Hessian, mu-coefficient, multiplier difference, pinned flag and the complementarity extremes: bit for bit"""
+  rows = [(r[2], r[0], r[1], r[4], r[5], cx, cn) for r in STEP_ROWS[::3] for (cx, cn) in ((F(0.0), INF), (F(0.5), F(1e-4)))]
+  cols = _cols(rows)
+  out = np.zeros(6 * len(rows))
+  sim.hostsim_bound_terms.argtypes = [C.c_int] + [C.c_void_p] * 8
+  sim.hostsim_bound_terms(len(rows), *[A(c) for c in cols], A(out))
+  with np.errstate(all="ignore"):
+    want = np.array([_terms_rule(*r) for r in rows]).ravel()
+  np.testing.assert_array_equal(out, want)
+
+
+def _limits_rule(zv, l, u, zl, zu, d, mu, wg, tau):
+  rcp = lambda x: F(1.0) / x
+  fr, hl, hu = _kind(l, u)
+  sl, su = (zv - l if hl else F(1.0)), (u - zv if hu else F(1.0))
+  zlv, zuv = (zl if hl else F(1.0)), (zu if hu else F(1.0))
+  rsl, rsu = rcp(sl), rcp(su)
+  gb = wg
+  gb = gb - (mu * rsl if hl else F(0.0))
+  gb = gb + (mu * rsu if hu else F(0.0))
+  dzl = -zlv + (mu - zlv * d) * rsl
+  dzu = -zuv + (mu + zuv * d) * rsu
+  tol_, tou_ = hl and bool(d < 0.0), hu and bool(d > 0.0)
+  ap_ = tau * (sl if tol_ else su) * rcp(abs(d)) if (tol_ or tou_) else F(1.0)
+  ad_l = -tau * zlv * rcp(dzl) if (hl and dzl < 0.0) else F(1.0)
+  ad_u = -tau * zuv * rcp(dzu) if (hu and dzu < 0.0) else F(1.0)
+  return dmin(F(1.0), ap_), dmin(F(1.0), dmin(ad_l, ad_u)), F(0.0) + (gb * d if fr else F(0.0))
+
+
+def test_step_limits_rule(sim):
+  """fraction-to-the-boundary limits of the point and of both multipliers, and the merit slope's term: bit for bit"""
+  rows = [(r[2], r[0], r[1], r[4], r[5], r[3], r[8], F(0.37) * r[6], dmax(F(0.99), F(1.0) - r[8])) for r in STEP_ROWS[::2]]
+  cols = _cols(rows)
+  out = np.zeros(3 * len(rows))
+  sim.hostsim_step_limits.argtypes = [C.c_int] + [C.c_void_p] * 10
+  sim.hostsim_step_limits(len(rows), *[A(c) for c in cols], A(out))
+  with np.errstate(all="ignore"):
+    want = np.array([_limits_rule(*r) for r in rows]).ravel()
+  np.testing.assert_array_equal(out, want)
+  assert (out.reshape(-1, 3)[:, 0] < 1.0).sum() > 20 and (out.reshape(-1, 3)[:, 1] < 1.0).sum() > 20
+
+
+@pytest.mark.parametrize("k", [2, 10, 28])
+def test_slack_log_value(sim, k):
+  """SlackLog::value() of points of k variables against R = fsum(log s_i) over the same clamped slacks, within
+  2^-52 (k + |log slk| + 2 |sexp| ln 2 + |R| + sum |log s_i|): k roundings of the mantissa product (and of the pairs), one of the log, the
+  product with the rounded ln 2, the final sum, the reference's own logs.  slack_pair and the violation count are exact."""
+  import math
+  rng = np.random.default_rng(16 + k)
+  one_sided = [c for c in BOUND_CASES if _kind(c[0], c[1]) in ((True, True, False), (True, False, True), (True, False, False))]
+  # (the product of a two-sided pair must be a normal double: 1e-200 on both sides or 1e150 x 1e300 are left to the one-sided cases)
+  with np.errstate(all="ignore"):
+    two_sided = [c for c in BOUND_CASES if _kind(c[0], c[1]) == (True, True, True) and (c[2] - c[0] <= 0.0 or c[1] - c[2] <= 0.0 or 1e-290 < (c[2] - c[0]) * (c[1] - c[2]) < 1e290)]
+  other = [c for c in BOUND_CASES if not _kind(c[0], c[1])[0]]
+  pool = one_sided + two_sided + other
+  points = [[pool[i] for i in rng.integers(0, len(pool), k)] for _ in range(40)]
+  points.append([c for c in one_sided if c[2] in (1e300, -1e300)][:k] * k)      # all large, all small: the exponents add up, nothing overflows
+  points.append([c for c in one_sided if c[2] in (1e-300, -1e-300)][:k] * k)
+  points = [p[:k] for p in points]
+  flat = [c for p in points for c in p]
+  l, u, v = _cols(flat)
+  out, pairs = np.zeros(4 * len(points)), np.zeros(len(flat))
+  sim.hostsim_slack_log.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5
+  sim.hostsim_slack_log(len(points), k, A(v), A(l), A(u), A(out), A(pairs))
+  worst = 0.0
+  for p, pt in enumerate(points):
+    s, bad = [], 0
+    for i, (lo, up, x) in enumerate(pt):
+      fr, hl, hu = _kind(lo, up)
+      sl, su = (x - lo if hl else F(1.0)), (up - x if hu else F(1.0))
+      bad += (0 if sl > 0.0 else 1) + (0 if su > 0.0 else 1)
+      sl, su = (sl if sl > 0.0 else F(1.0)), (su if su > 0.0 else F(1.0))
+      assert pairs[p * k + i] == sl * su
+      s += [float(sl), float(su)]
+    got, slk, sexp, nbad = out[4 * p:4 * p + 4]
+    assert nbad == bad
+    R = math.fsum(math.log(x) for x in s)
+    bound = 2.0 ** -52 * (k + abs(math.log(slk)) + 2.0 * abs(sexp) * math.log(2.0) + abs(R) + sum(abs(math.log(x)) for x in s))
+    assert np.isfinite(got) and np.isfinite(bound) and abs(got - R) <= bound, (p, got, R, bound)
+    worst = max(worst, abs(got - R) / bound if bound > 0.0 else 0.0)
+  print(f"k = {k}: largest |value - R| / bound = {worst:.3f}")
+  assert sum(out[3::4] > 0) > 3      # (some points hold a violated bound)
