@@ -17,6 +17,7 @@
  *                                                experiments/e2e_sysid.py:113-125           myr_vjp (add_gradf=1), myr_jvp
  *   step(x, lmbda) (extragradient iteration)     nlp_solvers/extra_gradient.py:25-33        myr_exgd
  *   FBSM(hp,cfg,system).solve()                  trajectory_optimizers/forward_backward_sweep.py:88-116   myr_fbsm
+ *   many_steps_grad / lookahead_update           experiments/e2e_sysid.py:148-177, 209-218  myr_exgd_grad
  *
  * Conventions
  *   - all floating point is IEEE fp64 (the reference sets jax_enable_x64, run.py:15);
@@ -310,6 +311,27 @@ int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, const double*
 int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                  const double* wt, const double* params, int32_t params_stride,
                  double* loss, double* grad, int32_t grad_stride, int32_t mem);
+
+/*
+ * Derivative of `nsteps` extragradient steps (myr_exgd) in the model parameters, by one reverse sweep through the steps on the device
+ * (experiments/e2e_sysid.py:148-177 carries dz/dp, dlam/dp forward from a starting point held fixed; this is the same derivative, contracted
+ * with a seed, for any number of parameters; library version 0.3).  With (z_n, lam_n) the iterate after `nsteps` steps from (z, lam):
+ *   grad[b][k] = seed_z[b] . d z_n / d params[k] + seed_lam[b] . d lam_n / d params[k]
+ *   dz0[b] = (d z_n / d z)^T seed_z[b] + (d lam_n / d z)^T seed_lam[b],   dlam0[b] likewise in lam.
+ * A variable that a step leaves on a bound (and a pinned one, lb == ub) passes nothing on.
+ *   z [B][n], lam [B][m] (not modified); lb, ub [B][n]; params, eta_x, eta_v, nsteps as in myr_exgd; seed_z [B][n]; seed_lam [B][m] or NULL (= 0);
+ *   grad [B][np] if grad_stride == np, [np] = sum over the batch if grad_stride == 0 (fixed order, no atomics: the same bits on every
+ *   call, for MYR_MEM_HOST and MYR_MEM_DEVICE alike); dz0 [B][n] or NULL; dlam0 [B][m] or NULL.
+ * nsteps == 0 gives grad = 0, dz0 = seed_z, dlam0 = seed_lam.  The steps' history (nsteps (2 n + m) + n doubles per instance) lives in the
+ * handle's scratch; a batch whose history would pass 1 GiB runs in chunks of instances.
+ * MYR_E_UNSUPPORTED: SHOOTING, the network system, the elastic twins, INVASIVEPLANT; MYR_E_CAPACITY: the reverse sweep's
+ * (3 n + 2 m + x_rows ns) doubles pass the 160 KiB LDS; MYR_E_ARG: null z / lam / lb / ub / seed_z / grad, negative nsteps, a grad_stride
+ * or params_stride other than 0 and np.
+ */
+int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub,
+                  const double* params, int32_t params_stride, double eta_x, double eta_v, int32_t nsteps,
+                  const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
+                  double* dz0, double* dlam0, int32_t mem);
 
 /* Average device time (HIP events on the handle's stream) of the launches of one kernel since the last reset. */
 int myr_kernel_time(myr_handle h, int32_t kernel_id, double* avg_ms, int32_t* launches);

@@ -25,6 +25,7 @@
 #include "shoot_eval.h"
 #include "rollout.h"
 #include "fit.h"
+#include "exgd_grad.h"
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
@@ -315,6 +316,10 @@ struct SolveCall {
 struct RolloutArgs { int B, num_steps, u_rows; const double *x0, *us, *params; int pstride; double *xs, *cost; };      // xs, cost may be null
 struct FitArgs {      // xh: [num_steps+1][NS][Bp] state scratch; loss [B] or null; grad [B][NP] rows
   int B; long Bp; int num_steps, u_rows; const double *xs_obs, *us, *wt, *params; int pstride; double *xh, *loss, *grad;
+};
+struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of one chunk of `chunk` instances; seed_lam, dz0, dlam0 may be null
+  int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
+  double *rows, *dz0, *dlam0, *hist; int chunk;
 };
 struct FbsmArgs {      // X, A [N+1][NS][Bp], U [N+1 | N][NU][Bp]: batch-minor
   int B; long Bp; int N; const double *x0, *adjT, *params; int pstride; VarScale lo, hi; double bang, delta; int max_sweeps;
@@ -1037,6 +1042,39 @@ int fit_for_system(myr_handle h, const FitArgs& a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// derivative of the unrolled extragradient steps in the model parameters (exgd_grad.h: colloc_exgd_grad_kernel)
+// ------------------------------------------------------------------------------------------------
+template <class Sys, int SCHEME>
+static int launch_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
+  const int N = h->d.intervals;
+  const myr_dims& dm = h->dims;
+  const size_t lds = colloc_exgd_grad_lds_bytes<Sys, SCHEME>(N);
+  if (lds > 160 * 1024) return fail(MYR_E_CAPACITY, "myr_exgd_grad: intervals too large for the LDS-resident reverse sweep");
+  auto kern = colloc_exgd_grad_kernel<Sys, SCHEME>;
+  // (the limit is a property of the FUNCTION, shared by every handle of the process: the hardware's 160 KB, not this handle's size -- kernel_blocks_per_cu)
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  // the batch in chunks of instances that share one history buffer (launches on one stream: a chunk starts when the one before has ended)
+  for (long b0 = 0; b0 < a.B; b0 += a.chunk) {
+    const int nb = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64), lds, h->stream, nb, N, h->d.T / N, a.z + b0 * dm.n, a.lam + b0 * dm.m, a.lb + b0 * dm.n,
+                       a.ub + b0 * dm.n, a.params ? a.params + b0 * a.pstride : nullptr, a.pstride, a.eta_x, a.eta_v, a.nsteps, a.seed_z + b0 * dm.n,
+                       a.seed_lam ? a.seed_lam + b0 * dm.m : nullptr, a.hist, a.rows + b0 * dm.np, a.dz0 ? a.dz0 + b0 * dm.n : nullptr,
+                       a.dlam0 ? a.dlam0 + b0 * dm.m : nullptr);
+  }
+  return MYR_OK;
+}
+
+template <class Sys>
+int exgd_grad_for_system(myr_handle h, const ExgdGradArgs& a) {
+  // myr_exgd_grad has refused the twins, the network system and SHOOTING, each with its own message; the constexpr keeps their kernels out of the build
+  if constexpr (SysDpw<Sys>::SUPPORTED) {
+    if (h->d.transcription == MYR_TR_HERMITE_SIMPSON) return launch_exgd_grad<Sys, PROD_HS>(h, a);
+    if (h->d.transcription == MYR_TR_TRAPEZOIDAL) return launch_exgd_grad<Sys, PROD_TRAP>(h, a);
+  }
+  return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: not built for this system and transcription");
+}
+
 // ---- per-system entry points: explicit instantiation (system objects) / extern declaration (main object) -----------------
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
   LINK template int eval_for_system<S>(myr_handle, const EvalArgs&);          \
@@ -1044,6 +1082,7 @@ int fit_for_system(myr_handle h, const FitArgs& a) {
   LINK template int solve_for_system<S>(myr_handle, const SolveCall&);        \
   LINK template int rollout_for_system<S>(myr_handle, const RolloutArgs&);    \
   LINK template int fit_for_system<S>(myr_handle, const FitArgs&);            \
+  LINK template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
 // a system's object in parts (the build splits the slow ones): -DMYR_TU_PART=1 the Hermite-Simpson wavefront solvers and the dispatch, 3 the trapezoidal
@@ -1065,6 +1104,7 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, 
   template int products_for_system<S>(myr_handle, const ProdArgs&);           \
   template int rollout_for_system<S>(myr_handle, const RolloutArgs&);         \
   template int fit_for_system<S>(myr_handle, const FitArgs&);                 \
+  template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&);      \
   template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 MYR_SYSTEM_ENTRY_POINTS_REST(myriad::MYR_TU_SYSTEM)
 #endif
@@ -1079,7 +1119,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.2 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.3 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -1997,6 +2037,66 @@ extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t 
   st.out(a.grad, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_fit(h, a, grad_stride)) return rc;
+  return st.finish();
+}
+
+// device pointers throughout (a.hist, a.chunk and, for the batch sum, a.rows are set here); grad: [B][np] rows (grad_stride == np) or their sum
+static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride) {
+  const myr_dims& dm = h->dims;
+  // history of one instance: x_s, x_bar_s, lam_s of every step and the final x; the batch runs in chunks where the whole would pass the bound
+  const size_t per = ((size_t)a.nsteps * (2 * (size_t)dm.n + dm.m) + dm.n) * 8;
+  size_t bound = (size_t)1 << 30;
+  if (const char* e = getenv("MYRIAD_EXGD_GRAD_HIST_BYTES")) { const long long v = atoll(e); if (v > 0) bound = (size_t)v; }      // tests: force the chunked path
+  size_t chunk = bound / per;
+  a.chunk = (int)(chunk < 1 ? 1 : (chunk > (size_t)a.B ? (size_t)a.B : chunk));
+  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
+  st.scratch(a.hist, (size_t)a.chunk * (per / 8));
+  if (grad_stride) a.rows = grad;
+  else st.scratch(a.rows, (size_t)a.B * dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
+  const int rc = for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, grad);
+  const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
+  return rc ? rc : rc_end;
+}
+
+extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub, const double* params,
+                             int32_t params_stride, double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam,
+                             double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
+  const char* who = "myr_exgd_grad";
+  if (int rc = check_products_args(h, who, B, z, lam, lb, params, params_stride)) return rc;
+  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad: null ub");
+  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad: negative nsteps");
+  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad: null seed_z or grad");
+  if (grad_stride != 0 && grad_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_exgd_grad: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: an elastic twin has no model of its own to differentiate; use the handle of its system");
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: the network system is not built (second derivatives in 4 804 weights)");
+  if (h->d.transcription == MYR_TR_SHOOTING)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: SHOOTING is not built (it needs the second-order adjoint of the rollout); use a collocation transcription");
+  if (int rc = check_mem(who, mem)) return rc;
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
+  ExgdGradArgs a{};
+  a.B = B; a.pstride = params_stride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
+  double* g = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lb, lb, nz);
+  st.in(a.ub, ub, nz);
+  st.in(a.lam, lam, nl);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.in(a.seed_z, seed_z, nz);
+  st.in(a.seed_lam, seed_lam, nl);
+  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  st.out(a.dz0, dz0, nz);
+  st.out(a.dlam0, dlam0, nl);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride)) return rc;
   return st.finish();
 }
 

@@ -201,6 +201,27 @@ class TrajectoryOptimizer(object):
     z, lam = self.engine.exgd(variables, lmbdas, self.bounds[:, 0], self.bounds[:, 1], eta_x, eta_v, nsteps, params=p)
     return z[0], lam[0]
 
+  def step_sizes(self):
+    """(eta_x, eta_v) of the extragradient steps as experiments/e2e_sysid.py:104-109 picks them: defaults.learning_rates, else the hyperparameters"""
+    from myriad_amd.defaults import learning_rates
+    lr = learning_rates.get(self.hp.system, {})
+    return float(lr.get('eta_x', self.hp.eta_x)), float(lr.get('eta_v', self.hp.eta_lmbda))
+
+  def unrolled_grad(self, variables, lmbdas, params, seed, nsteps, eta_x=None, eta_v=None, lb=None, ub=None, reduce=False):
+    """seed . d x_nsteps / d params of `nsteps` extragradient steps from (variables, lmbdas) held fixed -- what the reference's
+    many_steps_grad + lookahead_update compute (experiments/e2e_sysid.py:148-177, 209-218) --, by one reverse sweep on the device
+    (myr_exgd_grad).  variables [n] or [B,n], seed likewise (dJ/dx); params: a parameter mapping (None: the system's own).  Returns the
+    gradient in the device order of system.param_names, [np] ([B,np] for a batch; its sum over the batch with reduce).  lb / ub: bounds per
+    instance (default: this optimizer's)."""
+    from myriad_amd.experiments.mle_sysid import split_params
+    p, sign = (self.system.device_params(), 1.0) if params is None else split_params(self.system, params)
+    ex, ev = self.step_sizes()
+    single = np.ndim(variables) == 1
+    out = self.engine.exgd_grad(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
+                                ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, seed, params=p, reduce=reduce,
+                                want_start=False)["grad"] * sign
+    return out[0] if single and not reduce else out
+
   # ---- what stands in for IPOPT's restoration phase ---------------------------------------------------------------------
   # The batched SQP has no feasibility-restoration phase of its own.  An instance that ends without a KKT point goes through
   # an ELASTIC PHASE (the system's elastic twin, where the library carries one) and then through SECOND STARTS from excitation

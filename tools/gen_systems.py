@@ -11,6 +11,9 @@ is added.  Run:  python tools/gen_systems.py
 
 `python tools/gen_systems.py --dp` writes myriad_amd/csrc/systems_dp_gen.h instead: the parameter derivatives of the
 dynamics (SysDp<Sys>::vjp_p, the reverse sweep of csrc/fit.h), from the same definitions.  systems_gen.h is left alone.
+
+`python tools/gen_systems.py --dpw` writes myriad_amd/csrc/systems_dpw_gen.h: the mixed derivatives of the point Lagrangian in the
+parameters and the variables (SysDpw<Sys>::vjp_p_dir, the reverse sweep of csrc/exgd_grad.h).  The other two headers are left alone.
 """
 import os
 import sympy as sp
@@ -18,6 +21,7 @@ from sympy.printing.c import C99CodePrinter
 
 OUT = os.path.join(os.path.dirname(__file__), "..", "myriad_amd", "csrc", "systems_gen.h")
 OUT_DP = os.path.join(os.path.dirname(__file__), "..", "myriad_amd", "csrc", "systems_dp_gen.h")
+OUT_DPW = os.path.join(os.path.dirname(__file__), "..", "myriad_amd", "csrc", "systems_dpw_gen.h")
 
 
 class inboxf(sp.Function):
@@ -480,6 +484,85 @@ def main_dp():
   print("wrote", os.path.abspath(OUT_DP))
 
 
+def gen_system_dpw(S):
+  """SysDpw<Sys>::vjp_p_dir: gp[k] = d/dp_k [ sum_i d[i] d/dw_i ( mu . f(w, p) + wg g(w, p, t) ) ], w = (x, u), of the field and the running cost
+  gen_system() emits (same substitution of the variable scales; t from the time slot).  Systems with a terminal cost also get
+  term_vjp_p_dir: gp[k] = d/dp_k ( term_grad . d )."""
+  name, x, u, p = S["name"], list(S["x"]), list(S["u"]), list(S["p"])
+  ns, nu, npar = len(x), len(u), len(p)
+  w = x + u
+  nw = ns + nu
+  sc = list(sp.symbols(f"sc0:{nw}", positive=True))
+  isc = list(sp.symbols(f"isc0:{ns}", positive=True))
+  smap = {v: sc[i] * v for i, v in enumerate(w)}
+  f = [sp.sympify(e).subs(smap, simultaneous=True) * isc[i] for i, e in enumerate(S["f"])]
+  g = sp.sympify(S["g"]).subs(smap, simultaneous=True)
+  gT = sp.sympify(S.get("gT", 0)).subs(smap, simultaneous=True)
+  tt = sp.Symbol("tt", nonnegative=True)
+  mu = list(sp.symbols(f"mu0:{ns}", real=True))
+  wg = sp.Symbol("wg", real=True)
+  d = list(sp.symbols(f"d0:{nw}", real=True))
+  lag = wg * g + sum(mu[i] * f[i] for i in range(ns))
+  phi = sum(d[i] * sp.diff(lag, w[i]) for i in range(nw))
+  gp = [sp.diff(phi, p[k]) for k in range(npar)]
+  phiT = sum(d[i] * sp.diff(gT, w[i]) for i in range(nw))
+  gpT = [sp.diff(phiT, p[k]) for k in range(npar)]
+  # csrc/exgd_grad.h gives the folded terminal cost no share in the Hessian block of the last point: it must be linear in (x, u)
+  assert all(sp.simplify(sp.diff(gT, a, b)) == 0 for a in w for b in w), "terminal cost must be linear (exgd_grad.h adds no Hessian term for it)"
+
+  def unpack(with_mu):
+    un = []
+    groups = [("x", x, 0), ("u", u, 0), ("p", p, 0), ("p", sc, npar), ("p", isc, npar + nw), ("d", d, 0)]
+    if with_mu:
+      groups.append(("mu", mu, 0))
+    for nm, syms, off in groups:
+      for i, sy in enumerate(syms):
+        un.append(f"    const double {sy} = {nm}[{off + i}];")
+    un.append(f"    const double tt = p[{npar + nw + ns}];")
+    allsy = x + u + p + sc + isc + d + (mu + [wg] if with_mu else []) + [tt]
+    return "\n".join(un) + "\n" + "\n".join(f"    (void){sy};" for sy in allsy)
+
+  o = []
+  o.append(f"// ===== {name} (id {S['id']}): np={npar} ({', '.join(S['pnames'])}) =====")
+  o.append(f"template <> struct SysDpw<Sys{name}> {{")
+  o.append("  static constexpr bool SUPPORTED = true;")
+  o.append("  MYR_HD static inline void vjp_p_dir(const double* x, const double* u, const double* p, const double* mu, double wg, const double* d,")
+  o.append("                                      double* gp) {")
+  o.append(unpack(True))
+  o.append(emit_block([(f"gp[{k}]", gp[k]) for k in range(npar)], "    "))
+  o.append("  }")
+  if gT != 0:
+    o.append("  MYR_HD static inline void term_vjp_p_dir(const double* x, const double* u, const double* p, const double* d, double* gp) {")
+    o.append(unpack(False))
+    o.append(emit_block([(f"gp[{k}]", gpT[k]) for k in range(npar)], "    "))
+    o.append("  }")
+  o.append("};")
+  return "\n".join(o)
+
+
+def main_dpw():
+  parts = ["// GENERATED by tools/gen_systems.py --dpw (sympy) -- do not edit by hand.",
+           "// Mixed derivatives of the point Lagrangian of systems_gen.h in the parameters and the variables:",
+           "// SysDpw<Sys>::vjp_p_dir(x, u, p, mu, wg, d, gp) writes gp[k] = d/dp_k [ sum_i d[i] d/dw_i ( mu . f(w, p) + wg g(w, p, t) ) ], k < NP, w = (x, u),",
+           "// d[NW] (p: the system's whole parameter buffer, variable scales and time slot included; the running cost is in, so a cost-only parameter",
+           "// has a real entry).  Systems with a terminal cost also have term_vjp_p_dir(x, u, p, d, gp): gp[k] = d/dp_k ( term_grad . d ).",
+           "// The elastic twins have no specialisation (SUPPORTED = false).",
+           "#pragma once",
+           '#include "systems_gen.h"',
+           "namespace myriad {",
+           "template <class Sys> struct SysDpw { static constexpr bool SUPPORTED = false; };",
+           ""]
+  for S in systems():
+    if S["name"].endswith("_ELASTIC"):
+      continue
+    parts.append(gen_system_dpw(S))
+    parts.append("")
+  parts.append("}  // namespace myriad")
+  with open(OUT_DPW, "w") as fh:
+    fh.write("\n".join(parts) + "\n")
+  print("wrote", os.path.abspath(OUT_DPW))
+
+
 def main():
   parts = ["// GENERATED by tools/gen_systems.py (sympy) -- do not edit by hand.",
            "// Closed-form dynamics / cost / derivative code for the control systems on the hot path.",
@@ -563,4 +646,4 @@ MYR_HD inline void fold_terminal(const double* x, const double* u, const double*
 
 if __name__ == "__main__":
   import sys
-  main_dp() if "--dp" in sys.argv[1:] else main()
+  main_dpw() if "--dpw" in sys.argv[1:] else (main_dp() if "--dp" in sys.argv[1:] else main())
