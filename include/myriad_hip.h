@@ -141,7 +141,8 @@ typedef struct {
                            are the same, bit for bit).  A batch much larger than the number of resident wavefronts runs as several
                            whole solves per wavefront and ends with the wavefronts that drew the long solves last; instead every
                            instance first gets `park_iter` iterations, the unfinished ones are parked (40 KB each) and resumed
-                           longest-first by their residuals at that point.  0 = the library decides (Hermite-Simpson, closed-form systems: 8 / 10 /
+                           longest-first by their residuals at that point (a wavefront that finds no fresh instance keeps iterating the one
+                           it holds until every instance has had its `park_iter` iterations, and parks it there).  0 = the library decides (Hermite-Simpson, closed-form systems: 8 / 10 /
                            12 iterations from 1.5 / 2 / 3 solves per resident wavefront on; whole solves otherwise; MYRIAD_PARK_ITER overrides), -1 = whole
                            solves, k > 0 = k iterations (an explicit k > 0 also selects the one-wavefront form for small batches, which the
                            library would otherwise give two wavefronts per trajectory: the two-wavefront form has no parking).  Needs the

@@ -38,15 +38,52 @@ namespace myriad {
 // a divisible load would take 77.5.  Phase 1 gives EVERY trajectory its first k1 iterations (equal work per slot) and parks the unfinished ones -- the
 // solver's LDS and the loop's scalars, 40 KB -- in global memory; the residuals at that point predict what is left (rank correlation 0.95), so phase 2
 // resumes them longest-first (`perm`) and the ragged end shrinks to a few iterations.  The arithmetic of a trajectory is the same, bit for bit.
+// Phase-1 fill (`fill`).  Launch 1 ends when its slowest slot does; a slot that finds no fresh ticket used to park its last trajectory at k1, leave, and
+// idle its SIMD until then.  With the fill it keeps iterating the trajectory it holds -- work phase 2 would do anyway -- and parks it at the first
+// iteration top at which every trajectory of the batch has had its k1 iterations.  Mode 1's park rule, at the top of every iteration it >= k1:
+//   the ticket counter is below B (fresh work remains)                         -> park (without the fill: always, i.e. at k1)
+//   `reached` == B (every trajectory has arrived at k1 or left its solve)      -> park
+//   otherwise                                                                 -> run this iteration.
+// A trajectory adds 1 to `reached` exactly once: the first time it stands at the top of iteration k1, or when it leaves `solve` before that (kernel).
+// The two counters are only READ, at iteration tops, between passes that do useful work: no slot ever waits for another workgroup.  A record carries
+// the iteration it was parked at (HsFused::PK_IT) and mode 2 resumes there; a trajectory that parks counts itself into its resume bucket (`cnt`).
 struct ParkArgs {
-  int mode;              // 0: whole solves; 1: stop at the top of iteration k1 and park; 2: ticket t resumes trajectory perm[t]
+  int mode;              // 0: whole solves; 1: park by the rule above; 2: ticket t resumes trajectory perm[t]
   int k1;
   const int* perm;       // mode 2: trajectories in resume order; count[0] of them
   const int* count;
   double* state;         // [B][stride]: the scalars of the loop, then the solver's LDS
   long stride;
+  int fill;              // mode 1: 1 = the phase-1 fill, 0 = park at k1 (MYRIAD_PARK_FILL=0)
+  int shift;             // mode 1: resume buckets per iteration parked after k1 (park_bucket_late; MYRIAD_PARK_SHIFT)
+  int* reached;          // mode 1: trajectories that have had their k1 iterations or finished earlier
+  int* cnt;              // mode 1: [PARK_BUCKETS] parked trajectories per resume bucket (park_bucket)
+#ifdef MYR_SLOT_STAMPS
+  long long* stamps;     // developer instrument: [slots][SLOT_STAMP_WORDS] wall clock at entry, at exit, tickets taken, after each ticket
+#endif
 };
 constexpr int MYR_STATUS_PARKED_ = 5;     // internal: never leaves myr_solve
+constexpr int SLOT_STAMP_WORDS = 64;
+
+// Resume order of a two-phase launch: parked trajectories by DESCENDING key (the geometric mean of the stationarity and the complementarity
+// residual at the parking point: rank correlation 0.9 with the iterations still to go), bucketed by half powers of two.  One function for the
+// trajectory that counts itself when it parks and for the kernel that places it (myriad_hip.hip: park_order_kernel).
+constexpr int PARK_BUCKETS = 256;
+__device__ inline int park_bucket(double st, double cp) {
+  const double key = (cp > 0.0 && st > 0.0) ? sqrt(st * cp) : (st > cp ? st : cp);
+  if (!(key > 0.0)) return 0;
+  if (!(key < 1e300)) return PARK_BUCKETS - 1;
+  int v = (int)floor(2.0 * log2(key)) + PARK_BUCKETS / 2 + 32;       // key 1 -> bucket 160; 1e-24 .. 1e14 spans the table
+  return v < 0 ? 0 : (v > PARK_BUCKETS - 1 ? PARK_BUCKETS - 1 : v);
+}
+// The key was calibrated on residuals that were all taken at k1.  A trajectory the fill parked `late` = it - k1 iterations further on has a smaller
+// residual for the same length of solve, and ranked by it the long solves among them start last: the headline batch's 43-iteration solve, parked at 15, sat
+// below the median bucket and launch 2 grew from 34 to 47 iterations' worth of time (profiles/r16_phase_fill/).  `shift` buckets per late iteration -- the
+// median residual falls by 2.6 ... 3 buckets an iteration -- put it back on the scale of k1.  Without the fill late = 0: the buckets of every round before.
+__device__ inline int park_bucket_late(double st, double cp, int late, int shift) {
+  const int v = park_bucket(st, cp) + shift * late;
+  return v > PARK_BUCKETS - 1 ? PARK_BUCKETS - 1 : v;
+}
 
 // Helper workgroups for the network passes (round 5).  Two thirds of an iteration of the network kernel are matrix-core passes over 13 independent tiles of
 // 16 points, and a workgroup owns a CU: a batch smaller than the device (config 5's share of an 8-GPU node is 128 trajectories) leaves CUs idle for the
@@ -213,6 +250,10 @@ struct HsFused {
   __host__ __device__ static int lds_doubles(int N) { return lds_solver_doubles(N) + (MLP ? npoints(N) * NS + NodeTraits<Sys>::lds_doubles : 0); }
   __host__ __device__ static size_t lds_bytes(int N) { return (size_t)lds_doubles(N) * 8; }
   static constexpr int NSCAL = 48;      // scalars of the solve loop in a parked trajectory's record
+  // the record of a parked trajectory: the policy's block (IpState::save / load), then this kernel's own: uni, the four results, and the iteration the
+  // trajectory was parked at (>= k1; -1 in the record of a trajectory that finished in launch 1: MYRIAD_PARK_DUMP shows which is which)
+  static constexpr int PK_UNI = IpState<NS>::RECORD, PK_RES = PK_UNI + 1, PK_IT = PK_RES + 4;
+  static_assert(PK_IT + 1 <= NSCAL, "record of a parked trajectory");
   __host__ __device__ static long park_doubles(int N) { return NSCAL + lds_solver_doubles(N) + (ZLU_GLOBAL ? 2L * npoints(N) * NW : 0); }      // (+ the bound multipliers of the forms that keep them in the slot's scratch)
 
   struct Ctx {
@@ -232,6 +273,7 @@ struct HsFused {
     bool h_valid;                         //   hb holds the activations of the iterate (the last trial point was accepted)
     const double *lb, *ub;                // the caller's bounds (global)
     bool uni;                             // interior points share one bound per component: served from sB
+    bool at_k1;                           // two-phase launch, mode 1: this trajectory has stood at the top of iteration k1 (and is counted in `reached`)
     SysParams<Sys> pp;
     bool term_pinned[NS];
     double *sLam, *sB, *sStash, *sTot, *sTr, *sRed, *sMisc, *sP, *sPc, *sTnu, *sKu;   // LDS
@@ -2316,12 +2358,10 @@ struct HsFused {
   }
 
   // ---- the solve: this kernel's passes around the one interior-point policy of ip_policy.h ---------------------------------------
-  __device__ static void solve(Ctx& c, const HsSolveOpts& o, const double* zg, HsSolveResult& res, int park_mode = 0, int park_k1 = 0,
-                               double* sv = nullptr) {
+  __device__ static void solve(Ctx& c, const HsSolveOpts& o, const double* zg, HsSolveResult& res, const ParkArgs pk = ParkArgs{}, double* sv = nullptr,
+                               const int* ticket = nullptr, int B = 0) {
     using namespace detail;
-    // the record of a parked trajectory: the policy's block (IpState::save / load), then this kernel's own five doubles
-    constexpr int PK_UNI = IpState<NS>::RECORD, PK_RES = PK_UNI + 1;
-    static_assert(PK_RES + 4 <= NSCAL, "record of a parked trajectory");
+    const int park_mode = pk.mode, park_k1 = pk.k1;
     IpState<NS> s;                     // the loop's scalars and every rule on them: ip_policy.h
     double hist[NMMAX];
     s.start(o);
@@ -2332,7 +2372,7 @@ struct HsFused {
     res.cost = 0.0; res.feas = 0.0; res.stat = 0.0; res.compl_ = 0.0;
     c.h_valid = false;                      // a new or resumed trajectory: the activation store belongs to the slot's previous one
     if (park_mode == 2) {
-      // resume a parked trajectory: the solver's LDS as it was at the top of iteration k1, the scalars of the loop, the slot's block of zeros
+      // resume a parked trajectory: the solver's LDS as it was at the top of the iteration it was parked at, the scalars of the loop, the slot's block of zeros
       const int nl = lds_solver_doubles(c.N);
       for (int i = c.tid; i < nl; i += NT) c.z[i] = __builtin_nontemporal_load(&sv[NSCAL + i]);     // (read once: keep it out of the caches the next kernels use)
       if constexpr (ZLU_GLOBAL) {
@@ -2342,7 +2382,7 @@ struct HsFused {
       s.load(sv, hist, pending);
       c.uni = sv[PK_UNI] != 0.0;
       res.cost = sv[PK_RES]; res.feas = sv[PK_RES + 1]; res.stat = sv[PK_RES + 2]; res.compl_ = sv[PK_RES + 3];
-      it0 = park_k1;
+      it0 = __builtin_amdgcn_readfirstlane((int)sv[PK_IT]);
     } else
       init(c, zg);
     wsync();
@@ -2350,7 +2390,28 @@ struct HsFused {
     for (int q = 0; q < NS; ++q) c.term_pinned[q] = !(c.sB[2 * NW + q] < c.sB[3 * NW + q]);
     res.status = 1; res.iters = o.max_iter;
     for (int it = it0; it <= o.max_iter; ++it) {
-      if (park_mode == 1 && it == park_k1) {
+      bool park_now = false;
+      if (park_mode == 1 && it >= park_k1) {      // the park rule (ParkArgs); wave-uniform: scalar branches only (matrix instructions ignore EXEC)
+        if (it == park_k1) {
+          c.at_k1 = true;
+          if (c.tid == 0) (void)__hip_atomic_fetch_add(pk.reached, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        park_now = true;
+        if (pk.fill) {
+          // two relaxed device-scope loads (executed at the L2), every lane the same address; nothing is read through them, so no acquire
+          const int tk = __hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const int rc = __hip_atomic_load(pk.reached, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          int pn = __builtin_amdgcn_readfirstlane((int)(tk < B || rc >= B));
+          if constexpr (NT > 64) {      // several wavefronts: all follow wavefront 0's reading
+            int* w = reinterpret_cast<int*>(c.sMisc) + 1;
+            if (c.wave == 0) *w = pn;        // (every lane: the value is wave-uniform)
+            __syncthreads();
+            pn = __builtin_amdgcn_readfirstlane(*w);
+          }
+          park_now = pn != 0;
+        }
+      }
+      if (park_now) {
         // park: everything the rest of the solve needs (the previous iteration ended with a workgroup barrier)
         const int nl = lds_solver_doubles(c.N);
         for (int i = c.tid; i < nl; i += NT) __builtin_nontemporal_store(c.z[i], &sv[NSCAL + i]);
@@ -2361,6 +2422,8 @@ struct HsFused {
           s.save(sv, hist, pending);
           sv[PK_UNI] = c.uni ? 1.0 : 0.0;
           sv[PK_RES] = res.cost; sv[PK_RES + 1] = res.feas; sv[PK_RES + 2] = res.stat; sv[PK_RES + 3] = res.compl_;
+          sv[PK_IT] = (double)it;
+          (void)__hip_atomic_fetch_add(&pk.cnt[park_bucket_late(res.stat, res.compl_, it - park_k1, pk.shift)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         res.status = MYR_STATUS_PARKED_; res.iters = it;
         return;
@@ -2571,6 +2634,9 @@ void hs_solve_fused_kernel(int B, int* ticket, HsSolveOpts o, VarScale vs, doubl
   c.N = o.N; c.K = W::npoints(o.N); c.n = c.K * W::NW; c.lane = threadIdx.x & 63; c.tid = threadIdx.x;
   c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform BY CONSTRUCTION: `if (c.wave == 0)` is a scalar branch (round 3 had it per lane)
   c.h = o.h; c.h6 = o.h / 6.0; c.h8 = o.h / 8.0;
+#ifdef MYR_SLOT_STAMPS
+  if (pk.stamps && c.tid == 0) pk.stamps[(long)blockIdx.x * SLOT_STAMP_WORDS] = wall_clock64();
+#endif
   // helper workgroups of the network kernel (NodeBoard): owners are workgroups 0..B-1, helper h of owner w is workgroup h B + w
   const bool coop = W::MLP && co.maxh > 0;
   const bool fixed = coop && B <= (int)gridDim.x;        // a batch that leaves workgroups without a trajectory: trajectory b belongs to workgroup b
@@ -2678,12 +2744,27 @@ void hs_solve_fused_kernel(int B, int* ticket, HsSolveOpts o, VarScale vs, doubl
         __hip_atomic_store(&c.board->att, MYR_COOP_RUNNING | (c.gen << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    if constexpr (NWAVES == 1 || W::MLP) W::solve(c, o, zg, r, pk.mode, pk.k1, pk.state + b * pk.stride);      // (W = 2 serves batches of one round only)
+    c.at_k1 = false;
+    if constexpr (NWAVES == 1 || W::MLP) W::solve(c, o, zg, r, pk, pk.state + b * pk.stride, ticket, B);      // (W = 2 serves batches of one round only)
     else W::solve(c, o, zg, r);
     if (r.status != MYR_STATUS_PARKED_) {
       for (int i = c.tid; i < c.n; i += W::NT) zg[i] = c.z[i];
       for (int i = c.tid; i < W::MLAM * c.N * W::NS; i += W::NT) lamg[i] = c.sLam[i];
+      if constexpr (NWAVES == 1 || W::MLP) {
+        if (pk.mode == 1 && c.tid == 0) {      // finished in launch 1: no record; counted here if it left before the top of iteration k1 (ParkArgs)
+          pk.state[b * pk.stride + W::PK_IT] = -1.0;
+          if (!c.at_k1) (void)__hip_atomic_fetch_add(pk.reached, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
     }
+#ifdef MYR_SLOT_STAMPS
+    if (pk.stamps && c.tid == 0) {
+      long long* st_ = pk.stamps + (long)blockIdx.x * SLOT_STAMP_WORDS;
+      const long long n_ = st_[2];
+      if (3 + n_ < SLOT_STAMP_WORDS) st_[3 + n_] = wall_clock64();
+      st_[2] = n_ + 1;
+    }
+#endif
 #ifdef MYR_PHASE_TIMING
     if (c.lane == 0 && b < 4) {
       printf("traj %ld wave %d it %d: backward %lld hess %lld fold %lld chunk %lld wait %lld join %lld first %lld ricc %lld nu %lld forward %lld ls %lld\n",
@@ -2734,6 +2815,9 @@ void hs_solve_fused_kernel(int B, int* ticket, HsSolveOpts o, VarScale vs, doubl
       W::coop_help(ha);
     }
   }
+#ifdef MYR_SLOT_STAMPS
+  if (pk.stamps && c.tid == 0) pk.stamps[(long)blockIdx.x * SLOT_STAMP_WORDS + 1] = wall_clock64();
+#endif
 }
 
 }  // namespace myriad

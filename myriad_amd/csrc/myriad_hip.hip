@@ -111,8 +111,10 @@ struct myr_handle_s {
   int fused_waves = 0;        // MYRIAD_FUSED_WAVES: wavefronts per trajectory (0 = by batch size)
   // two-phase launch of the one-wavefront fused kernel (hs_solver_fused.h: ParkArgs): records of the parked trajectories, resume order
   void* park_state = nullptr; size_t park_bytes = 0;
-  int* park_perm = nullptr; size_t park_n = 0;      // [park_n] resume order, then PARK_BUCKETS + 1 counters
+  int* park_perm = nullptr; size_t park_n = 0;      // [park_n] resume order, then PARK_BUCKETS + 2 counters: buckets, parked in all, `reached`
   int park_iter = -1;         // MYRIAD_PARK_ITER: iterations of phase 1 (-1 = by batch size, 0 = whole solves only)
+  int park_fill = 1;          // MYRIAD_PARK_FILL: 0 = every trajectory parks at k1 (phase 1 without the fill, hs_solver_fused.h: ParkArgs)
+  int park_shift = 3;         // MYRIAD_PARK_SHIFT: resume buckets per iteration a trajectory was parked after k1 (hs_solver_fused.h: park_bucket_late)
   // restoration inside myr_solve (myr_solve_opts.restoration): the twin handle, device scratch, and the account of the last call
   myr_handle_s* twin = nullptr;
   bool twin_unavailable = false;
@@ -582,31 +584,27 @@ extern template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_h
 #endif
 #endif
 
-// Resume order of a two-phase launch: parked trajectories by DESCENDING key (the geometric mean of the stationarity and the complementarity
-// residual at the parking point: rank correlation 0.9 with the iterations still to go), bucketed by half powers of two.  Three small launches.
-constexpr int PARK_BUCKETS = 256;
-static __device__ inline int park_bucket(const double* kkt, int b) {
-  const double st = kkt[3 * b + 1], cp = kkt[3 * b + 2];
-  const double key = (cp > 0.0 && st > 0.0) ? sqrt(st * cp) : (st > cp ? st : cp);
-  if (!(key > 0.0)) return 0;
-  if (!(key < 1e300)) return PARK_BUCKETS - 1;
-  int v = (int)floor(2.0 * log2(key)) + PARK_BUCKETS / 2 + 32;       // key 1 -> bucket 160; 1e-24 .. 1e14 spans the table
-  return v < 0 ? 0 : (v > PARK_BUCKETS - 1 ? PARK_BUCKETS - 1 : v);
-}
-static __global__ void park_hist_kernel(int B, const int32_t* __restrict__ status, const double* __restrict__ kkt, int* __restrict__ cnt) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B && status[b] == myriad::MYR_STATUS_PARKED_) atomicAdd(&cnt[park_bucket(kkt, b)], 1);
-}
-static __global__ void park_scan_kernel(int* __restrict__ cnt) {        // one thread: 256 counters -> start offsets, largest bucket first
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
+// Resume order of a two-phase launch (hs_solver_fused.h: park_bucket): the trajectories counted themselves into `cnt` when they parked; ONE workgroup
+// turns the 256 counts into start offsets, largest bucket first, and places every parked trajectory (the order inside a bucket is whatever the atomics give).
+using myriad::PARK_BUCKETS;
+// `late`: the iterations a trajectory was parked after k1, from its record (`state` + pk_it, HsFused::PK_IT).
+static __global__ __launch_bounds__(1024) void park_order_kernel(int B, const int32_t* __restrict__ status, const double* __restrict__ kkt, int* __restrict__ cnt, int* __restrict__ perm,
+                                                                 const double* __restrict__ state, long stride, int pk_it, int k1, int shift) {
+  __shared__ int off[PARK_BUCKETS];
+  if (threadIdx.x < PARK_BUCKETS) off[threadIdx.x] = cnt[threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x == 0) {
     int run = 0;
-    for (int k = PARK_BUCKETS - 1; k >= 0; --k) { const int c = cnt[k]; cnt[k] = run; run += c; }
+    for (int k = PARK_BUCKETS - 1; k >= 0; --k) { const int c = off[k]; off[k] = run; run += c; }
     cnt[PARK_BUCKETS] = run;
   }
-}
-static __global__ void park_scatter_kernel(int B, const int32_t* __restrict__ status, const double* __restrict__ kkt, int* __restrict__ cnt, int* __restrict__ perm) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B && status[b] == myriad::MYR_STATUS_PARKED_) perm[atomicAdd(&cnt[park_bucket(kkt, b)], 1)] = b;
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += blockDim.x)
+    if (status[b] == myriad::MYR_STATUS_PARKED_) {
+      const int late = (int)state[(long)b * stride + pk_it] - k1;
+      const int p = atomicAdd(&off[myriad::park_bucket_late(kkt[3 * b + 1], kkt[3 * b + 2], late, shift)], 1);
+      if (p < B) perm[p] = b;
+    }
 }
 
 // fused-phase wavefront kernel (hs_solver_fused.h): Hermite-Simpson, closed-form systems with one control and <= 4 states.
@@ -693,21 +691,31 @@ static int launch_hs_fused_w(myr_handle h, const SolveCall& a) {
     if ((size_t)B > h->park_n) {
       if (h->park_perm) HIPCHK(hipFree(h->park_perm));
       h->park_perm = nullptr; h->park_n = 0;
-      HIPCHK(hipMalloc(&h->park_perm, ((size_t)B + PARK_BUCKETS + 1) * sizeof(int)));
+      HIPCHK(hipMalloc(&h->park_perm, ((size_t)B + PARK_BUCKETS + 2) * sizeof(int)));
       h->park_n = (size_t)B;
     }
-    int* cnt = h->park_perm + h->park_n;
-    pk = myriad::ParkArgs{1, k1, h->park_perm, cnt + PARK_BUCKETS, (double*)h->park_state, pstr};
+    int* cnt = h->park_perm + h->park_n;        // [PARK_BUCKETS] per bucket, then the number parked, then `reached`
+    pk = myriad::ParkArgs{1, k1, h->park_perm, cnt + PARK_BUCKETS, (double*)h->park_state, pstr, h->park_fill, h->park_shift, cnt + PARK_BUCKETS + 1, cnt};
+    HIPCHK(hipMemsetAsync(cnt, 0, (PARK_BUCKETS + 2) * sizeof(int), h->stream));       // (launch 1 counts into them)
+#ifdef MYR_SLOT_STAMPS
+    // developer instrument (-DMYR_SLOT_STAMPS, tools/dev/slot_stamps.py): wall clock of every slot at entry, after each ticket and at exit, both launches;
+    // one buffer per process (the handle's layout is shared with objects built without the flag)
+    static void* stamp_buf = nullptr; static size_t stamp_bytes = 0;
+    const size_t stamp_need = 2 * (size_t)slots * myriad::SLOT_STAMP_WORDS * sizeof(long long);
+    if (int rc = ensure_buf(&stamp_buf, &stamp_bytes, stamp_need)) return rc;
+    HIPCHK(hipMemsetAsync(stamp_buf, 0, stamp_need, h->stream));
+    pk.stamps = (long long*)stamp_buf;
+#endif
     hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64 * NWAVES), lds, h->stream, B, h->ticket, o, h->vscale, a.z, a.lb, a.ub, a.lam, (double*)h->sbuf, stride,
                        a.params, a.pstride, a.cost, a.status, a.iters, a.kkt, h->poison, pk, co);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(cnt, 0, (PARK_BUCKETS + 1) * sizeof(int), h->stream));
     if (int rc = reset_ticket(h)) return rc;
-    const unsigned gb = (unsigned)((B + 255) / 256);
-    hipLaunchKernelGGL(park_hist_kernel, dim3(gb), dim3(256), 0, h->stream, B, a.status, a.kkt, cnt);
-    hipLaunchKernelGGL(park_scan_kernel, dim3(1), dim3(64), 0, h->stream, cnt);
-    hipLaunchKernelGGL(park_scatter_kernel, dim3(gb), dim3(256), 0, h->stream, B, a.status, a.kkt, cnt, h->park_perm);
+    hipLaunchKernelGGL(park_order_kernel, dim3(1), dim3(1024), 0, h->stream, B, a.status, a.kkt, cnt, h->park_perm,
+                       (const double*)h->park_state, pstr, (int)W::PK_IT, k1, h->park_shift);
     pk.mode = 2;
+#ifdef MYR_SLOT_STAMPS
+    pk.stamps += (size_t)slots * myriad::SLOT_STAMP_WORDS;
+#endif
   }
 #ifdef MYR_COOP_TRACE
   static int* trace_host = nullptr;
@@ -738,11 +746,23 @@ static int launch_hs_fused_w(myr_handle h, const SolveCall& a) {
     if (ab) return fail(MYR_E_HIP, "network kernel: a wait between a trajectory's workgroups ran into its bound (MYRIAD_NODE_HELPERS=0 runs without helper workgroups)");
   }
   if (k1 > 0) {
-    if (const char* path = getenv("MYRIAD_PARK_DUMP")) {      // developer knob: the loop scalars of every record as parked ([B][NSCAL] doubles), for the study of resume orders
-      std::vector<double> sc((size_t)B * W::NSCAL);
+    if (const char* path = getenv("MYRIAD_PARK_DUMP")) {      // developer knob: the loop scalars of every record as parked ([B][NSCAL] doubles), for the study of resume orders;
+      std::vector<double> sc((size_t)B * W::NSCAL + 4);       // then four doubles: NSCAL, the index of the parking iteration (PK_IT), trajectories parked, `reached`
       HIPCHK(hipMemcpy2D(sc.data(), W::NSCAL * sizeof(double), h->park_state, (size_t)pk.stride * sizeof(double), W::NSCAL * sizeof(double), (size_t)B, hipMemcpyDeviceToHost));
+      int tail[2] = {0, 0};
+      HIPCHK(hipMemcpy(tail, pk.count, sizeof(tail), hipMemcpyDeviceToHost));
+      double* t = sc.data() + (size_t)B * W::NSCAL;
+      t[0] = (double)W::NSCAL; t[1] = (double)W::PK_IT; t[2] = (double)tail[0]; t[3] = (double)tail[1];
       if (FILE* f = fopen(path, "wb")) { fwrite(sc.data(), sizeof(double), sc.size(), f); fclose(f); }
     }
+#ifdef MYR_SLOT_STAMPS
+    if (const char* path = getenv("MYRIAD_SLOT_STAMPS")) {      // [2 launches][slots][SLOT_STAMP_WORDS] int64 behind a header {slots, SLOT_STAMP_WORDS}
+      const long long head[2] = {(long long)slots, (long long)myriad::SLOT_STAMP_WORDS};
+      std::vector<long long> st(2 * (size_t)slots * myriad::SLOT_STAMP_WORDS);
+      HIPCHK(hipMemcpy(st.data(), pk.stamps - (size_t)slots * myriad::SLOT_STAMP_WORDS, st.size() * sizeof(long long), hipMemcpyDeviceToHost));
+      if (FILE* f = fopen(path, "wb")) { fwrite(head, sizeof(long long), 2, f); fwrite(st.data(), sizeof(long long), st.size(), f); fclose(f); }
+    }
+#endif
   }
   return timed_account(h, MYR_K_SOLVE);      // (a launch the helper protocol aborted is not counted)
 }
@@ -1210,6 +1230,8 @@ extern "C" int myr_create(const myr_problem_desc* desc, myr_handle* out) {
   if (const char* e = getenv("MYRIAD_STACK_FILL")) h->stack_fill = !strcmp(e, "nan") ? 1 : (!strcmp(e, "random") ? 2 : (!strcmp(e, "big") ? 3 : (!strcmp(e, "zero") ? 4 : 0)));
   if (const char* e = getenv("MYRIAD_NODE_HELPERS")) h->node_helpers = atoi(e);   // developer knob: helper workgroups per trajectory of the network kernel (0 = none)
   if (const char* e = getenv("MYRIAD_PARK_ITER")) h->park_iter = atoi(e);         // developer knob: iterations of phase 1 of the two-phase launch (0 = off)
+  if (const char* e = getenv("MYRIAD_PARK_FILL")) h->park_fill = atoi(e) != 0;    // developer knob: 0 = phase 1 without the fill (every trajectory parks at k1)
+  if (const char* e = getenv("MYRIAD_PARK_SHIFT")) { const int v = atoi(e); h->park_shift = v < 0 ? 0 : (v > 64 ? 64 : v); }      // developer knob: see park_shift
   if (const char* e = getenv("MYRIAD_FUSED_WAVES")) h->fused_waves = atoi(e);     // developer knob: wavefronts per trajectory of the fused kernel
   if (const char* e = getenv("MYRIAD_SOLVE_SLOTS")) h->solve_slots = atoi(e);   // developer knob: resident wavefronts of the solve kernel
   if (const char* e = getenv("MYRIAD_POISON")) {      // test knob: "nan" (signalling NaN), "big", "random", or a 64-bit pattern in hex
