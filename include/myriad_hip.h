@@ -18,6 +18,8 @@
  *   step(x, lmbda) (extragradient iteration)     nlp_solvers/extra_gradient.py:25-33        myr_exgd
  *   FBSM(hp,cfg,system).solve()                  trajectory_optimizers/forward_backward_sweep.py:88-116   myr_fbsm
  *   many_steps_grad / lookahead_update           experiments/e2e_sysid.py:148-177, 209-218  myr_exgd_grad
+ *   jax.hessian / jax.jvp(jax.grad(lagrangian))  (no call site in the reference: the exact second derivative
+ *                                                an external second-order method asks for)  myr_hvp
  *
  * Conventions
  *   - all floating point is IEEE fp64 (the reference sets jax_enable_x64, run.py:15);
@@ -333,6 +335,25 @@ int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const double* lam, c
                   const double* params, int32_t params_stride, double eta_x, double eta_v, int32_t nsteps,
                   const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
                   double* dz0, double* dlam0, int32_t mem);
+
+/*
+ * Lagrangian Hessian-vector product, matrix-free and exact, for all three transcriptions (library version 0.4).  With
+ * L(z, lam, p) = f(z, p) + lam^T c(z, p), a direction v and psi(z, lam, p) = <grad_z L(z, lam, p), v>:
+ *   out_z[b] = grad_z psi = (d^2 L / dz dz) v[b],      out_p[b] = grad_p psi = (d^2 L / dp dz) v[b].
+ * (grad_lam psi = J v is myr_jvp.)  with_cost == 0 drops f from L in both outputs and leaves sum_i lam_i (d^2 c_i / dz dz) v -- the
+ * constraint-Hessian callback of SciPy's trust-constr.
+ *   z [B][n]; lam [B][m] or NULL (= 0); v [B][n]; params as in myr_vjp; out_z [B][n] or NULL;
+ *   out_p [B][np] if p_stride == np, [np] = the sum over the batch if p_stride == 0 (fixed order, no atomics: the same bits on every
+ *   call, for MYR_MEM_HOST and MYR_MEM_DEVICE alike), or NULL.  Inputs are not modified; B == 0 does nothing.
+ * Collocation: the Hessian is block-diagonal over the points.  SHOOTING: per (instance, interval) a forward tangent rollout and a
+ * second-order reverse sweep through the integrator's stages (EULER, HEUN, MIDPOINT, RK4); the terminal cost of BACTERIA, TUMOUR and
+ * PREDATORPREY sits on the integrated end state of the last interval (shooting.py:206-208) and takes part through that interval's costate.
+ * MYR_E_ARG: null z / v, both outputs null, a p_stride or params_stride other than 0 and np, a bad mem;
+ * MYR_E_UNSUPPORTED: the network system, the elastic twins, INVASIVEPLANT; MYR_E_CAPACITY: SHOOTING with more than 2^30 (instance, interval)
+ * pairs in one call (the collocation kernel reads its inputs where they lie: no horizon is too long for it).
+ */
+int myr_hvp(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params,
+            int32_t params_stride, int32_t with_cost, double* out_z, double* out_p, int32_t p_stride, int32_t mem);
 
 /* Average device time (HIP events on the handle's stream) of the launches of one kernel since the last reset. */
 int myr_kernel_time(myr_handle h, int32_t kernel_id, double* avg_ms, int32_t* launches);

@@ -30,7 +30,7 @@ STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr
 
 EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
            "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
-           "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad"]
+           "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp"]
 
 
 class ProblemDesc(C.Structure):
@@ -110,6 +110,8 @@ def load() -> C.CDLL:
   lib.myr_exgd.restype = C.c_int
   lib.myr_exgd_grad.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
   lib.myr_exgd_grad.restype = C.c_int
+  lib.myr_hvp.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, C.c_int32, C.c_int32]
+  lib.myr_hvp.restype = C.c_int
   lib.myr_fbsm.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_double, C.c_double, C.c_int32,
                            dp, dp, dp, ip, C.c_int32]
   lib.myr_fbsm.restype = C.c_int
@@ -425,6 +427,32 @@ class Engine:
     _chk(self.lib.myr_exgd_grad(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), int(params_stride), float(eta_x),
                                 float(eta_v), int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
                                 MEM_DEVICE), "myr_exgd_grad")
+
+  def hvp(self, z, lam, v, params=None, with_cost=True, want_z=True, want_p=False, reduce=False):
+    """myr_hvp: Lagrangian Hessian-vector product.  With L = f + lam^T c (f dropped when with_cost is false) and psi = <grad_z L, v>:
+    {"hz" [B,n] = grad_z psi = (d2L/dz dz) v (with want_z), "hp" [B,np] = grad_p psi = (d2L/dp dz) v, or [np] = the sum over the batch with
+    reduce=True (with want_p)}.  lam None: zero multipliers."""
+    z = self._batch2(z, self.n, "z"); v = self._batch2(v, self.n, "v")
+    B = z.shape[0]
+    lam = None if lam is None else self._batch2(lam, self.m, "lam")
+    if v.shape[0] != B or (lam is not None and lam.shape[0] != B):
+      raise ValueError("z, lam and v must have the same batch size")
+    p, ps = self._params(params, B)
+    hz = np.empty((B, self.n)) if want_z else None
+    hp = (np.empty(self.np) if reduce else np.empty((B, self.np))) if want_p else None
+    _chk(self.lib.myr_hvp(self._h, B, _addr(z), _addr(lam), _addr(v), _addr(p), ps, int(bool(with_cost)), _addr(hz), _addr(hp),
+                          0 if reduce else self.np, MEM_HOST), "myr_hvp")
+    out = {}
+    if want_z:
+      out["hz"] = hz
+    if want_p:
+      out["hp"] = hp
+    return out
+
+  def hvp_device(self, B, z, lam, v, out_z=None, out_p=None, p_stride=0, params=None, params_stride=0, with_cost=True):
+    """Zero-copy variant of hvp: every array is a device tensor on this handle's device (lam, out_z, out_p may be None); nothing is copied."""
+    _chk(self.lib.myr_hvp(self._h, int(B), _addr(z), _addr(lam), _addr(v), _addr(params), int(params_stride), int(bool(with_cost)), _addr(out_z),
+                          _addr(out_p), int(p_stride), MEM_DEVICE), "myr_hvp")
 
   def products_device(self, op, B, z, w, out, params=None, params_stride=0, add_gradf=0):
     """Zero-copy vjp ('vjp') / jvp ('jvp') on device tensors."""

@@ -26,6 +26,8 @@
 #include "rollout.h"
 #include "fit.h"
 #include "exgd_grad.h"
+#include "colloc_hvp.h"
+#include "shoot_hvp.h"
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
@@ -322,6 +324,9 @@ struct FitArgs {      // xh: [num_steps+1][NS][Bp] state scratch; loss [B] or nu
 struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of one chunk of `chunk` instances; seed_lam, dz0, dlam0 may be null
   int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
   double *rows, *dz0, *dlam0, *hist; int chunk;
+};
+struct HvpArgs {      // lam, out_z, rows ([B][NP] parameter rows) may be null; hist, side: shooting scratch, batch-minor with Pp columns (one per pair)
+  int B; const double *z, *lam, *v, *params; int pstride, with_cost; double *out_z, *rows, *hist, *side; long Pp;
 };
 struct FbsmArgs {      // X, A [N+1][NS][Bp], U [N+1 | N][NU][Bp]: batch-minor
   int B; long Bp; int N; const double *x0, *adjT, *params; int pstride; VarScale lo, hi; double bang, delta; int max_sweeps;
@@ -1095,6 +1100,43 @@ int exgd_grad_for_system(myr_handle h, const ExgdGradArgs& a) {
   return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: not built for this system and transcription");
 }
 
+// ------------------------------------------------------------------------------------------------
+// Lagrangian Hessian-vector product (colloc_hvp.h: colloc_hvp_kernel; shoot_hvp.h: shoot_hvp_kernel, shoot_hvp_gather_kernel)
+// ------------------------------------------------------------------------------------------------
+// myr_hvp has refused the twins and the network system, each with its own message; the constexpr keeps their kernels out of the build
+template <class Sys>
+int hvp_colloc_for_system(myr_handle h, const HvpArgs& a) {
+  if constexpr (SysDpw<Sys>::SUPPORTED) {
+    const int N = h->d.intervals;
+    if (h->d.transcription == MYR_TR_HERMITE_SIMPSON)
+      hipLaunchKernelGGL((colloc_hvp_kernel<Sys, PROD_HS>), dim3((unsigned)a.B), dim3(64), 0, h->stream, a.B, N, h->d.T / N, a.z, a.lam, a.v, a.params,
+                         a.pstride, a.with_cost, a.out_z, a.rows);
+    else
+      hipLaunchKernelGGL((colloc_hvp_kernel<Sys, PROD_TRAP>), dim3((unsigned)a.B), dim3(64), 0, h->stream, a.B, N, h->d.T / N, a.z, a.lam, a.v, a.params,
+                         a.pstride, a.with_cost, a.out_z, a.rows);
+    return MYR_OK;
+  }
+  return fail(MYR_E_UNSUPPORTED, "myr_hvp: not built for this system");
+}
+
+template <class Sys, int M>
+static int launch_shoot_hvp(myr_handle h, const HvpArgs& a) {
+  const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+  const long P = (long)a.B * I;
+  hipLaunchKernelGGL((shoot_hvp_kernel<Sys, M>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, a.B, a.Pp, I, cpi, (int)h->d.integration_method,
+                     h->d.T, a.z, a.lam, a.v, a.params, a.pstride, a.with_cost, a.hist, a.side);
+  hipLaunchKernelGGL((shoot_hvp_gather_kernel<Sys, M>), dim3(grid_for((long)a.B * (h->dims.n + h->dims.np))), dim3(256), 0, h->stream, a.B, a.Pp, I, cpi,
+                     (const double*)a.side, a.out_z, a.rows);
+  return MYR_OK;
+}
+
+template <class Sys>
+int hvp_shoot_for_system(myr_handle h, const HvpArgs& a) {
+  if constexpr (SysDpw<Sys>::SUPPORTED)
+    return h->d.integration_method == MYR_INT_RK4 ? launch_shoot_hvp<Sys, 2>(h, a) : launch_shoot_hvp<Sys, 1>(h, a);
+  return fail(MYR_E_UNSUPPORTED, "myr_hvp: not built for this system");
+}
+
 // ---- per-system entry points: explicit instantiation (system objects) / extern declaration (main object) -----------------
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
   LINK template int eval_for_system<S>(myr_handle, const EvalArgs&);          \
@@ -1103,10 +1145,12 @@ int exgd_grad_for_system(myr_handle h, const ExgdGradArgs& a) {
   LINK template int rollout_for_system<S>(myr_handle, const RolloutArgs&);    \
   LINK template int fit_for_system<S>(myr_handle, const FitArgs&);            \
   LINK template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&); \
+  LINK template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
+  LINK template int hvp_shoot_for_system<S>(myr_handle, const HvpArgs&);      \
   LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
 // a system's object in parts (the build splits the slow ones): -DMYR_TU_PART=1 the Hermite-Simpson wavefront solvers and the dispatch, 3 the trapezoidal
-// wavefront solvers, 4 the shooting solvers, 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
+// wavefront solvers, 4 the shooting solvers and the shooting Hessian-vector product, 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
 #if MYR_TU_PART == 1
 template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 template int solve_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
@@ -1114,6 +1158,7 @@ template int solve_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall
 template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 4
 template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
+template int hvp_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const HvpArgs&);
 #elif MYR_TU_PART == 5
 template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 6
@@ -1125,6 +1170,7 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, 
   template int rollout_for_system<S>(myr_handle, const RolloutArgs&);         \
   template int fit_for_system<S>(myr_handle, const FitArgs&);                 \
   template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&);      \
+  template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);          \
   template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 MYR_SYSTEM_ENTRY_POINTS_REST(myriad::MYR_TU_SYSTEM)
 #endif
@@ -1139,7 +1185,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.3 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.4 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -2119,6 +2165,64 @@ extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const dou
   st.out(a.dlam0, dlam0, nl);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_exgd_grad(h, a, g, grad_stride)) return rc;
+  return st.finish();
+}
+
+// device pointers throughout (a.hist, a.side, a.Pp and, for the batch sum, a.rows are set here); out_p: [B][np] rows (p_stride == np), their sum, or null
+static int dispatch_hvp(myr_handle h, HvpArgs a, double* out_p, int p_stride) {
+  const myr_dims& dm = h->dims;
+  const bool shoot = h->d.transcription == MYR_TR_SHOOTING;
+  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
+  if (shoot) {      // per (instance, interval) pair: the history of its steps and its side record (ShootHvp::hist_doubles, side_doubles), a column per lane
+    const long I = h->d.intervals, cpi = h->d.controls_per_interval, M = h->d.integration_method == MYR_INT_RK4 ? 2 : 1;
+    const long P = (long)a.B * I;
+    if (P > (1L << 30)) return fail(MYR_E_CAPACITY, "myr_hvp: more than 2^30 (instance, interval) pairs in one call");
+    a.Pp = (P + 63) / 64 * 64;
+    if (((a.Pp / 64) & 1) == 0) a.Pp += 64;      // an odd number of wavefronts, as padded_lanes
+    st.scratch(a.hist, (size_t)(cpi * 2 * dm.ns) * (size_t)a.Pp);
+    st.scratch(a.side, (size_t)(dm.ns + (M * cpi + 1) * dm.nu + dm.np) * (size_t)a.Pp);
+  }
+  if (out_p && p_stride) a.rows = out_p;
+  else if (out_p) st.scratch(a.rows, (size_t)a.B * dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
+  const int rc = shoot ? for_system(h->d.system_id, true, [&](auto t) { return hvp_shoot_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; })
+                       : for_system(h->d.system_id, true, [&](auto t) { return hvp_colloc_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+  if (!rc && out_p && !p_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, out_p);
+  const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
+  return rc ? rc : rc_end;
+}
+
+extern "C" int myr_hvp(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params, int32_t params_stride,
+                       int32_t with_cost, double* out_z, double* out_p, int32_t p_stride, int32_t mem) {
+  const char* who = "myr_hvp";
+  if (!h || !z || !v) return fail(MYR_E_ARG, "myr_hvp: null handle, z or v");
+  if (!out_z && !out_p) return fail(MYR_E_ARG, "myr_hvp: both outputs are null");
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
+  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_hvp: an elastic twin has no model of its own to differentiate; use the handle of its system");
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_hvp: the network system is not built (second derivatives in 4 804 weights)");
+  if (int rc = check_batch(who, B)) return rc;
+  if (p_stride != 0 && p_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_hvp: p_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_stride(h, who, params, params_stride)) return rc;
+  if (int rc = check_mem(who, mem)) return rc;
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n;
+  HvpArgs a{};
+  a.B = B; a.pstride = params_stride; a.with_cost = with_cost != 0;
+  double* gp = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lam, lam, (size_t)B * dm.m);
+  st.in(a.v, v, nz);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.out(a.out_z, out_z, nz);
+  st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_hvp(h, a, gp, p_stride)) return rc;
   return st.finish();
 }
 

@@ -195,6 +195,12 @@ class TrajectoryOptimizer(object):
     p = self.system.device_params() if params is None else self.system.params_from_mapping(params)
     return self.engine.jvp(variables, v, params=p)[0]
 
+  def lagrangian_hessp(self, xs_and_us, lmbdas, v, params=None, with_cost=True):
+    """(d2 lagrangian / dx dx) v, matrix-free and exact on the device (myr_hvp), for every transcription.  with_cost=False drops the objective:
+    sum_i lmbda_i (d2 c_i / dx dx) v, the `hess(x, v)` a SciPy NonlinearConstraint takes; lmbdas None with with_cost=True: the objective's Hessian."""
+    p = self.system.device_params() if params is None else self.system.params_from_mapping(params)
+    return self.engine.hvp(xs_and_us, lmbdas, v, params=p, with_cost=with_cost)["hz"][0]
+
   def extragradient_step(self, variables, lmbdas, eta_x, eta_v, nsteps=1, params=None):
     """`nsteps` iterations of the reference's `step(x, lmbda)` (extra_gradient.py:25-33)."""
     p = self.system.device_params() if params is None else self.system.params_from_mapping(params)
