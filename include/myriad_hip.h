@@ -18,6 +18,8 @@
  *   step(x, lmbda) (extragradient iteration)     nlp_solvers/extra_gradient.py:25-33        myr_exgd
  *   FBSM(hp,cfg,system).solve()                  trajectory_optimizers/forward_backward_sweep.py:88-116   myr_fbsm
  *   many_steps_grad / lookahead_update           experiments/e2e_sysid.py:148-177, 209-218  myr_exgd_grad
+ *   many_steps_grad / lookahead_update in the network weights
+ *                                                experiments/node_e2e_sysid.py:139-166, 187-196  myr_exgd_grad_node
  *   jax.hessian / jax.jvp(jax.grad(lagrangian))  (no call site in the reference: the exact second derivative
  *                                                an external second-order method asks for)  myr_hvp
  *
@@ -335,6 +337,24 @@ int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const double* lam, c
                   const double* params, int32_t params_stride, double eta_x, double eta_v, int32_t nsteps,
                   const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
                   double* dz0, double* dlam0, int32_t mem);
+
+/*
+ * myr_exgd_grad in the np = 4804 weights of the network system (experiments/node_e2e_sysid.py:139-166, 187-196; library version 0.5): the same
+ * step, the same seeds and outputs, the same history in the handle's scratch (chunks under the same 1 GiB bound), the same bits for
+ * MYR_MEM_HOST and MYR_MEM_DEVICE and on every call.  A variable on a bound or pinned passes nothing on; nsteps == 0 gives grad = 0,
+ * dz0 = seed_z, dlam0 = seed_lam; inputs are not modified; B == 0 writes nothing.
+ *   params [np]: ONE weight set shared by the batch, in the order of csrc/node_system.h, required (there is no params_stride);
+ *   grad [B][np] if grad_stride == np, [np] = their fixed-order sum if grad_stride == 0; seed_lam, dz0, dlam0 may be NULL.
+ * One workgroup of four wavefronts per instance, lane j = hidden unit j of both layers (csrc/node_exgd_grad.h).
+ * MYR_E_UNSUPPORTED: a handle whose system is not MYR_SYS_NODE_CARTPOLE (use myr_exgd_grad), a transcription other than
+ * MYR_TR_HERMITE_SIMPSON (the one myr_vjp / myr_exgd build for the network system); MYR_E_ARG: null z / lam / lb / ub / seed_z / grad /
+ * params, negative nsteps or B, a grad_stride other than 0 and np, a bad mem; MYR_E_CAPACITY: the weight copy (5 064 doubles) and the
+ * sweep's (3 n + 2 m + x_rows ns) doubles pass the 160 KiB LDS (N = 400 does).  myr_exgd_grad and myr_hvp keep refusing the network system.
+ */
+int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub,
+                       const double* params, double eta_x, double eta_v, int32_t nsteps,
+                       const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
+                       double* dz0, double* dlam0, int32_t mem);
 
 /*
  * Lagrangian Hessian-vector product, matrix-free and exact, for all three transcriptions (library version 0.4).  With

@@ -30,7 +30,8 @@ STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr
 
 EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
            "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
-           "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp"]
+           "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp",
+           "myr_exgd_grad_node"]
 
 
 class ProblemDesc(C.Structure):
@@ -110,6 +111,8 @@ def load() -> C.CDLL:
   lib.myr_exgd.restype = C.c_int
   lib.myr_exgd_grad.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
   lib.myr_exgd_grad.restype = C.c_int
+  lib.myr_exgd_grad_node.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
+  lib.myr_exgd_grad_node.restype = C.c_int
   lib.myr_hvp.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, C.c_int32, C.c_int32]
   lib.myr_hvp.restype = C.c_int
   lib.myr_fbsm.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_double, C.c_double, C.c_int32,
@@ -427,6 +430,37 @@ class Engine:
     _chk(self.lib.myr_exgd_grad(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), int(params_stride), float(eta_x),
                                 float(eta_v), int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
                                 MEM_DEVICE), "myr_exgd_grad")
+
+  def exgd_grad_node(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
+    """myr_exgd_grad_node: exgd_grad in the 4 804 shared weights of the network system (`params`: the flat vector of csrc/node_system.h's order;
+    Hermite-Simpson).  Returns {"grad" [B,np], or [np] = the sum over the batch with reduce=True, "dz0" [B,n], "dlam0" [B,m]}."""
+    z = self._batch2(z, self.n, "z"); lam = self._batch2(lam, self.m, "lam")
+    B = z.shape[0]
+    if lam.shape[0] != B:
+      raise ValueError("z and lam must have the same batch size")
+    lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), z.shape))
+    ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), z.shape))
+    sz = np.ascontiguousarray(np.broadcast_to(_f64(seed_z), z.shape))
+    sl = None if seed_lam is None else np.ascontiguousarray(np.broadcast_to(_f64(seed_lam), lam.shape))
+    p = None if params is None else np.ascontiguousarray(_f64(params))
+    if p is not None and p.shape != (self.np,):
+      raise ValueError(f"params must be the {self.np} shared weights")
+    grad = np.empty(self.np) if reduce else np.empty((B, self.np))
+    dz0 = np.empty((B, self.n)) if want_start else None
+    dlam0 = np.empty((B, self.m)) if want_start else None
+    _chk(self.lib.myr_exgd_grad_node(self._h, B, _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(p), float(eta_x), float(eta_v), int(nsteps),
+                                     _addr(sz), _addr(sl), _addr(grad), 0 if reduce else self.np, _addr(dz0), _addr(dlam0), MEM_HOST),
+         "myr_exgd_grad_node")
+    out = {"grad": grad}
+    if want_start:
+      out["dz0"] = dz0; out["dlam0"] = dlam0
+    return out
+
+  def exgd_grad_node_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None, dlam0=None):
+    """Zero-copy variant of exgd_grad_node: every array is a device tensor on this handle's device."""
+    _chk(self.lib.myr_exgd_grad_node(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), float(eta_x), float(eta_v),
+                                     int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
+                                     MEM_DEVICE), "myr_exgd_grad_node")
 
   def hvp(self, z, lam, v, params=None, with_cost=True, want_z=True, want_p=False, reduce=False):
     """myr_hvp: Lagrangian Hessian-vector product.  With L = f + lam^T c (f dropped when with_cost is false) and psi = <grad_z L, v>:

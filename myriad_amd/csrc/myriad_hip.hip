@@ -26,6 +26,7 @@
 #include "rollout.h"
 #include "fit.h"
 #include "exgd_grad.h"
+#include "node_exgd_grad.h"
 #include "colloc_hvp.h"
 #include "shoot_hvp.h"
 #include "fbsm.h"
@@ -135,6 +136,7 @@ struct myr_handle_s {
   size_t vbuf_bytes = 0;
   // helper workgroups of the network kernel (hs_solver_fused.h: NodeBoard): boards | abort word | published vectors
   void* coop_buf = nullptr; size_t coop_bytes = 0;
+  int node_exgd_wpi = 4;      // MYRIAD_NODE_EXGD_WPI: wavefronts per instance of node_exgd_grad_kernel (1, 2 or 4: 8 spills; profiles/r18_node_exgd_grad)
   int node_helpers = -1;      // MYRIAD_NODE_HELPERS: helper workgroups per trajectory (-1 = by batch size)
   int32_t plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // myr_solve_plan: how the last first-attempt solve was launched
   bool plan_frozen = false;                     //   (second starts re-launch on this handle: they leave the first attempt's record alone)
@@ -1100,6 +1102,35 @@ int exgd_grad_for_system(myr_handle h, const ExgdGradArgs& a) {
   return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: not built for this system and transcription");
 }
 
+// the same derivative in the weights of the network system (node_exgd_grad.h: node_exgd_grad_kernel; myr_exgd_grad_node has checked system and transcription)
+template <int WPI>
+static int launch_node_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
+  const int N = h->d.intervals;
+  const myr_dims& dm = h->dims;
+  const size_t lds = node_exgd_grad_lds_bytes(N);
+  auto kern = node_exgd_grad_kernel<WPI>;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  for (long b0 = 0; b0 < a.B; b0 += a.chunk) {      // (chunks that share one history buffer, as launch_exgd_grad)
+    const int nb = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64 * WPI), lds, h->stream, nb, N, h->d.T / N, a.z + b0 * dm.n, a.lam + b0 * dm.m, a.lb + b0 * dm.n,
+                       a.ub + b0 * dm.n, a.params, a.eta_x, a.eta_v, a.nsteps, a.seed_z + b0 * dm.n, a.seed_lam ? a.seed_lam + b0 * dm.m : nullptr, a.hist,
+                       a.rows + b0 * dm.np, a.dz0 ? a.dz0 + b0 * dm.n : nullptr, a.dlam0 ? a.dlam0 + b0 * dm.m : nullptr);
+  }
+  return MYR_OK;
+}
+
+template <class Sys>
+int exgd_grad_node_for_system(myr_handle h, const ExgdGradArgs& a) {
+  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // the kernel lives in the network system's object only
+    switch (h->node_exgd_wpi) {      // (myr_exgd_grad_node has checked that the LDS record fits)
+      case 1: return launch_node_exgd_grad<1>(h, a);
+      case 2: return launch_node_exgd_grad<2>(h, a);
+      default: return launch_node_exgd_grad<4>(h, a);
+    }
+  }
+  return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node: the network system only; use myr_exgd_grad");
+}
+
 // ------------------------------------------------------------------------------------------------
 // Lagrangian Hessian-vector product (colloc_hvp.h: colloc_hvp_kernel; shoot_hvp.h: shoot_hvp_kernel, shoot_hvp_gather_kernel)
 // ------------------------------------------------------------------------------------------------
@@ -1145,6 +1176,7 @@ int hvp_shoot_for_system(myr_handle h, const HvpArgs& a) {
   LINK template int rollout_for_system<S>(myr_handle, const RolloutArgs&);    \
   LINK template int fit_for_system<S>(myr_handle, const FitArgs&);            \
   LINK template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&); \
+  LINK template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
   LINK template int hvp_shoot_for_system<S>(myr_handle, const HvpArgs&);      \
   LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
@@ -1170,6 +1202,7 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, 
   template int rollout_for_system<S>(myr_handle, const RolloutArgs&);         \
   template int fit_for_system<S>(myr_handle, const FitArgs&);                 \
   template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&);      \
+  template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
   template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);          \
   template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 MYR_SYSTEM_ENTRY_POINTS_REST(myriad::MYR_TU_SYSTEM)
@@ -1185,7 +1218,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.4 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.5 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -1274,6 +1307,7 @@ extern "C" int myr_create(const myr_problem_desc* desc, myr_handle* out) {
   if (l) { int v = atoi(l); if (v >= 1 && v <= 64) h->solve_lpw = v; }
   if (const char* e = getenv("MYRIAD_REG_FILL")) h->reg_fill = !strcmp(e, "nan") ? 1 : (!strcmp(e, "random") ? 2 : (!strcmp(e, "big") ? 3 : (!strcmp(e, "zero") ? 4 : 0)));
   if (const char* e = getenv("MYRIAD_STACK_FILL")) h->stack_fill = !strcmp(e, "nan") ? 1 : (!strcmp(e, "random") ? 2 : (!strcmp(e, "big") ? 3 : (!strcmp(e, "zero") ? 4 : 0)));
+  if (const char* e = getenv("MYRIAD_NODE_EXGD_WPI")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->node_exgd_wpi = v; }      // developer knob
   if (const char* e = getenv("MYRIAD_NODE_HELPERS")) h->node_helpers = atoi(e);   // developer knob: helper workgroups per trajectory of the network kernel (0 = none)
   if (const char* e = getenv("MYRIAD_PARK_ITER")) h->park_iter = atoi(e);         // developer knob: iterations of phase 1 of the two-phase launch (0 = off)
   if (const char* e = getenv("MYRIAD_PARK_FILL")) h->park_fill = atoi(e) != 0;    // developer knob: 0 = phase 1 without the fill (every trajectory parks at k1)
@@ -2109,7 +2143,7 @@ extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t 
 }
 
 // device pointers throughout (a.hist, a.chunk and, for the batch sum, a.rows are set here); grad: [B][np] rows (grad_stride == np) or their sum
-static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride) {
+static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, bool node = false) {
   const myr_dims& dm = h->dims;
   // history of one instance: x_s, x_bar_s, lam_s of every step and the final x; the batch runs in chunks where the whole would pass the bound
   const size_t per = ((size_t)a.nsteps * (2 * (size_t)dm.n + dm.m) + dm.n) * 8;
@@ -2123,7 +2157,8 @@ static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int gr
   else st.scratch(a.rows, (size_t)a.B * dm.np);
   if (int rc = st.commit()) return rc;
   if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
-  const int rc = for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+  const int rc = node ? exgd_grad_node_for_system<SysNODE_CARTPOLE>(h, a)
+                      : for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
   if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, grad);
   const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
   return rc ? rc : rc_end;
@@ -2165,6 +2200,49 @@ extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const dou
   st.out(a.dlam0, dlam0, nl);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_exgd_grad(h, a, g, grad_stride)) return rc;
+  return st.finish();
+}
+
+// the same call for the weights of the network system: one shared weight set (no params_stride), Hermite-Simpson
+extern "C" int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub, const double* params,
+                                  double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam, double* grad,
+                                  int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
+  const char* who = "myr_exgd_grad_node";
+  if (!h || !z || !lam || !lb) return fail(MYR_E_ARG, "myr_exgd_grad_node: null handle or array");
+  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_node: null ub");
+  if (int rc = check_batch(who, B)) return rc;
+  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_node: negative nsteps");
+  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_node: null seed_z or grad");
+  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node: this handle's system is not the network system; use myr_exgd_grad");
+  if (h->d.transcription != MYR_TR_HERMITE_SIMPSON)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node: HERMITE_SIMPSON only, the one transcription myr_vjp / myr_exgd build for the network system");
+  if (int rc = check_node_weights(h, who, params)) return rc;
+  if (grad_stride != 0 && grad_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_exgd_grad_node: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_mem(who, mem)) return rc;
+  if (node_exgd_grad_lds_bytes(h->d.intervals) > 160 * 1024)
+    return fail(MYR_E_CAPACITY, "myr_exgd_grad_node: intervals too large for the LDS-resident reverse sweep beside the weight copy");
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
+  ExgdGradArgs a{};
+  a.B = B; a.pstride = 0; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
+  double* g = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lb, lb, nz);
+  st.in(a.ub, ub, nz);
+  st.in(a.lam, lam, nl);
+  st.in(a.params, params, (size_t)dm.np);
+  st.in(a.seed_z, seed_z, nz);
+  st.in(a.seed_lam, seed_lam, nl);
+  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  st.out(a.dz0, dz0, nz);
+  st.out(a.dlam0, dlam0, nl);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, true)) return rc;
   return st.finish();
 }
 
