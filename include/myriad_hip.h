@@ -66,7 +66,11 @@ enum { MYR_SYS_CARTPOLE = 0, MYR_SYS_VANDERPOL = 1, MYR_SYS_CANCERTREATMENT = 2,
           "Elastic mode"): x' = f(x,u) + s with NS slack controls s appended to u and the running cost g + rho/2 |s|^2, rho the
           LAST model parameter.  All entry points work on them like on any system (NU = nu + ns controls), except myr_solve under
           MYR_TR_SHOOTING (every twin): MYR_E_UNSUPPORTED, "... built for the collocation transcriptions".  (Up to round 4 ROCKETLANDING's
-          twin had no trapezoidal solver either.)  Every system with pinned terminal states has one (round 4). */
+          twin had no trapezoidal solver either.)  Every system with pinned terminal states has one (round 4).
+          Under myr_set_var_scale a twin does NOT solve the same problem in other variables: its penalty is rho/2 sum_i (s_i / sc_i)^2,
+          sc_i the scale entry of slack i (entry ns + nu + i of the twin's vector) -- every slack is weighed against the magnitude the
+          caller states for it.  The library's own elastic phase (myr_solve_opts.restoration) gives each slack the scale of its state.
+          With unit scales, and in every entry point but the scaled solve, the penalty is rho/2 |s|^2. */
        MYR_SYS_CARTPOLE_ELASTIC = 100, MYR_SYS_VANDERPOL_ELASTIC = 101, MYR_SYS_PENDULUM_ELASTIC = 113, MYR_SYS_MOUNTAINCAR_ELASTIC = 114,
        MYR_SYS_ROCKETLANDING_ELASTIC = 115,
        /* lenhart/invasive_plant.py: DISCRETE-time (five foci, five controls).  Only myr_fbsm (its discrete recurrences)
@@ -247,6 +251,10 @@ int myr_solve_x0(myr_handle h, int32_t B, const double* x0s, const double* g0, c
  * user scaling, which the reference reaches through `nlp_scaling_method`); inputs and outputs of myr_solve stay in the
  * ORIGINAL variables (z, lam) except kkt[][0], the constraint violation, which is measured in scaled states.
  * Not available for NODE systems.  Power-of-two scales make the change of variables exact in floating point.
+ * The *_ELASTIC twins are the exception to "the same problem": their slack penalty is written in the scaled variables,
+ * rho/2 sum_i (s_i / sc_i)^2 with sc_i the scale entry of slack i, so on a twin handle the scale changes the problem that is
+ * solved (the cost returned is that weighted cost).  The elastic phase of the restoration sets each slack's entry to the scale of
+ * its state.  A refused vector (MYR_E_ARG) changes nothing: the scales set before stay in force.
  */
 int myr_set_var_scale(myr_handle h, const double* scale);
 

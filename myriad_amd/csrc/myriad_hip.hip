@@ -1918,12 +1918,17 @@ extern "C" int myr_set_var_scale(myr_handle h, const double* scale) {
   if (h->d.system_id == MYR_SYS_NODE_CARTPOLE && scale) return fail(MYR_E_UNSUPPORTED, "myr_set_var_scale: not available for NODE systems");
   const int nw = h->dims.ns + h->dims.nu;
   if (nw > 16) return fail(MYR_E_CAPACITY, "myr_set_var_scale: more than 16 variables per point");
+  // every entry is checked before anything changes: a refused vector leaves the previous scales (and the twin made under them) in force
+  if (scale) {
+    for (int i = 0; i < nw; ++i) {
+      if (!(scale[i] > 0.0) || !(scale[i] < 1e300)) return fail(MYR_E_ARG, "myr_set_var_scale: scales must be positive and finite");
+    }
+  }
   if (h->twin) { (void)myr_destroy(h->twin); h->twin = nullptr; }      // (the twin of the restoration phase takes its scales from here: made again on demand)
   bool on = false;
   for (int i = 0; i < 16; ++i) h->vscale.s[i] = 1.0;
   if (scale) {
     for (int i = 0; i < nw; ++i) {
-      if (!(scale[i] > 0.0) || !(scale[i] < 1e300)) return fail(MYR_E_ARG, "myr_set_var_scale: scales must be positive and finite");
       h->vscale.s[i] = scale[i];
       on = on || scale[i] != 1.0;
     }

@@ -773,10 +773,13 @@ class NodeCartPole(CartPole):
 
 class Elastic(System):
   """The ELASTIC TWIN of a system (no counterpart in the reference; include/myriad_hip.h MYR_SYS_*_ELASTIC): x' = f(x,u) + s with
-  ns free slack controls s appended to u, running cost g + rho/2 |s|^2.  The checker of the twins' device code."""
+  ns free slack controls s appended to u, running cost g + rho/2 |s|^2.  The checker of the twins' device code.
+  slack_scale [ns]: the penalty becomes rho/2 sum_i (s_i / slack_scale_i)^2 -- what a twin handle solves under myr_set_var_scale, whose
+  penalty is written in the scaled slacks (slack_scale_i = the scale entry of slack i); None: the unweighted penalty."""
 
-  def __init__(self, base: System, rho: float = 1.0):
+  def __init__(self, base: System, rho: float = 1.0, slack_scale=None):
     self.base, self.rho = base, float(rho)
+    self.slack_scale = None if slack_scale is None else _t(np.asarray(slack_scale, dtype=np.float64).reshape(base.ns))
     self.name = base.name + "_ELASTIC"
     self.param_names = tuple(base.param_names) + ("rho",)
     self.x_0, self.x_T, self.T = base.x_0, base.x_T, base.T
@@ -790,7 +793,8 @@ class Elastic(System):
     return self.base.dynamics(x, u[..., :self._nu]) + u[..., self._nu:]
 
   def cost(self, x, u, t=None):
-    return self.base.cost(x, u[..., :self._nu], t) + 0.5 * self.rho * (u[..., self._nu:] ** 2).sum(-1)
+    s = u[..., self._nu:] if self.slack_scale is None else u[..., self._nu:] / self.slack_scale
+    return self.base.cost(x, u[..., :self._nu], t) + 0.5 * self.rho * (s ** 2).sum(-1)
 
 
 SYSTEMS = {c.name: c for c in (CartPole, VanDerPol, CancerTreatment, SimpleCase, Bioreactor, Glucose, MouldFungicide,
