@@ -20,6 +20,8 @@
  *   many_steps_grad / lookahead_update           experiments/e2e_sysid.py:148-177, 209-218  myr_exgd_grad
  *   many_steps_grad / lookahead_update in the network weights
  *                                                experiments/node_e2e_sysid.py:139-166, 187-196  myr_exgd_grad_node
+ *   many_steps_grad / lookahead_update under SHOOTING (the default hyperparameters)
+ *                                                experiments/e2e_sysid.py:148-177, 209-218  myr_exgd_grad_shoot
  *   jax.hessian / jax.jvp(jax.grad(lagrangian))  (no call site in the reference: the exact second derivative
  *                                                an external second-order method asks for)  myr_hvp
  *
@@ -363,6 +365,22 @@ int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, const double* l
                        const double* params, double eta_x, double eta_v, int32_t nsteps,
                        const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
                        double* dz0, double* dlam0, int32_t mem);
+
+/*
+ * myr_exgd_grad under MYR_TR_SHOOTING (the transcription the reference's experiments/e2e_sysid.py runs with its default hyperparameters;
+ * library version 0.6): the same step, seeds, outputs and null rules, the same history in the handle's scratch (chunks of instances under the
+ * same 1 GiB bound), the same bits for MYR_MEM_HOST and MYR_MEM_DEVICE and on every call; nsteps == 0 gives grad = 0, dz0 = seed_z,
+ * dlam0 = seed_lam; inputs are not modified; B == 0 writes nothing.  All four integrators, every closed-form system.
+ * The reverse sweep is 2 nsteps + 1 passes of one lane per (instance, interval) pair -- a forward tangent rollout and myr_hvp's second-order
+ * reverse, started from the multiplier cotangent, so that one pass gives H v + J^T alpha, its parameter part and the pair's rows of J v --,
+ * each followed by an elementwise mask pass (csrc/shoot_exgd_grad.h).
+ * MYR_E_UNSUPPORTED: a transcription other than MYR_TR_SHOOTING (use myr_exgd_grad), the network system, the elastic twins, INVASIVEPLANT;
+ * MYR_E_CAPACITY: more than 2^30 (instance, interval) pairs in one call; MYR_E_ARG: as myr_exgd_grad.  myr_exgd_grad keeps refusing SHOOTING.
+ */
+int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub,
+                        const double* params, int32_t params_stride, double eta_x, double eta_v, int32_t nsteps,
+                        const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
+                        double* dz0, double* dlam0, int32_t mem);
 
 /*
  * Lagrangian Hessian-vector product, matrix-free and exact, for all three transcriptions (library version 0.4).  With

@@ -29,6 +29,7 @@
 #include "node_exgd_grad.h"
 #include "colloc_hvp.h"
 #include "shoot_hvp.h"
+#include "shoot_exgd_grad.h"
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
@@ -330,6 +331,10 @@ struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of 
 struct HvpArgs {      // lam, out_z, rows ([B][NP] parameter rows) may be null; hist, side: shooting scratch, batch-minor with Pp columns (one per pair)
   int B; const double *z, *lam, *v, *params; int pstride, with_cost; double *out_z, *rows, *hist, *side; long Pp;
 };
+struct ShootExgdGradArgs {      // as ExgdGradArgs; hist, work: the scratch of one chunk of `chunk` instances (launch_shoot_exgd_grad carves work); Pp: its pair columns
+  int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
+  double *rows, *dz0, *dlam0, *hist, *work; int chunk; long Pp;
+};
 struct FbsmArgs {      // X, A [N+1][NS][Bp], U [N+1 | N][NU][Bp]: batch-minor
   int B; long Bp; int N; const double *x0, *adjT, *params; int pstride; VarScale lo, hi; double bang, delta; int max_sweeps;
   double *X, *U, *A; int32_t* sweeps;
@@ -432,8 +437,46 @@ static int launch_products(myr_handle h, const ProdArgs& a) {
   return timed_end(h, MYR_K_PROD);
 }
 
+// count doubles from one device array of the handle's stream to another
+static int copy_doubles(myr_handle h, double* dst, const double* src, long count) {
+  HIPCHK(hipMemcpyAsync(dst, src, (size_t)count * 8, hipMemcpyDeviceToDevice, h->stream));
+  return MYR_OK;
+}
+
+// `nsteps` extragradient steps of a shooting problem as a launch sequence (the iterate of a shooting problem is small: no LDS-resident variant), in place
+// in (zio, lamio).  scr: B (cpi + 1) NS doubles of sweep scratch; g, zbar [B][n]; cbuf [B][m].  hist (or null; ShootExgdGrad's layout for a chunk of
+// B instances): x_s, x_bar_s, lam_s of every step and the final x are copied out as the steps go.  myr_exgd and myr_exgd_grad_shoot both run this.
+template <class Sys, int M>
+static int shoot_exgd_steps(myr_handle h, int B, double* zio, double* lamio, const double* lb, const double* ub, const double* params, int pstride,
+                             double eta_x, double eta_v, int nsteps, double* scr, double* g, double* zbar, double* cbuf, double* hist) {
+  const int I = h->d.intervals, cpi = h->d.controls_per_interval, method = h->d.integration_method;
+  const myr_dims& dm = h->dims;
+  const dim3 grid((unsigned)((B + 63) / 64)), blk(64);
+  const long tz = (long)B * dm.n, tl = (long)B * dm.m;
+  const unsigned ub_ = grid_for(tz);
+  for (int s = 0; s < nsteps; ++s) {
+    double* hs = hist ? hist + (size_t)s * (size_t)(2 * tz + tl) : nullptr;
+    if (hs) {
+      if (int rc = copy_doubles(h, hs, zio, tz)) return rc;
+      if (int rc = copy_doubles(h, hs + 2 * tz, lamio, tl)) return rc;
+    }
+    hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, B, I, cpi, method, h->d.T, (const double*)zio, params, pstride,
+                       (double*)nullptr, g, (double*)nullptr, (double*)nullptr, scr, (const double*)lamio, 1);
+    hipLaunchKernelGGL(exgd_update_kernel, dim3(ub_), dim3(256), 0, h->stream, tz, (const double*)zio, (const double*)g, lb, ub, eta_x, zbar);
+    if (hs)
+      if (int rc = copy_doubles(h, hs + tz, zbar, tz)) return rc;
+    hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, B, I, cpi, method, h->d.T, (const double*)zbar, params, pstride,
+                       (double*)nullptr, g, (double*)nullptr, (double*)nullptr, scr, (const double*)lamio, 1);
+    hipLaunchKernelGGL(exgd_update_kernel, dim3(ub_), dim3(256), 0, h->stream, tz, (const double*)zio, (const double*)g, lb, ub, eta_x, zio);
+    hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, B, I, cpi, method, h->d.T, (const double*)zio, params, pstride,
+                       (double*)nullptr, (double*)nullptr, cbuf, (double*)nullptr, scr, (const double*)nullptr, 1);
+    hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, h->stream, tl, eta_v, (const double*)cbuf, lamio);
+  }
+  return hist ? copy_doubles(h, hist + (size_t)nsteps * (size_t)(2 * tz + tl), zio, tz) : (int)MYR_OK;
+}
+
 // shooting: J^T lam / grad L by the reverse sweep of shoot_eval_kernel seeded with lam, J v by forward tangents, and the
-// extragradient step as a launch sequence (the iterate of a shooting problem is small: no LDS-resident variant)
+// extragradient step (shoot_exgd_steps)
 template <class Sys, int M>
 static int launch_shoot_products_m(myr_handle h, const ProdArgs& a) {
   const int I = h->d.intervals, cpi = h->d.controls_per_interval, method = h->d.integration_method;
@@ -444,6 +487,7 @@ static int launch_shoot_products_m(myr_handle h, const ProdArgs& a) {
   double* scr = (double*)h->sbuf;
   const dim3 grid((unsigned)((a.B + 63) / 64)), blk(64);
   if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
+  int rc = MYR_OK;
   if (a.op == PRODOP_VJP) {
     hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, a.z, a.params, a.pstride,
                        (double*)nullptr, a.out, (double*)nullptr, (double*)nullptr, scr, a.w, a.add_gradf);
@@ -451,21 +495,10 @@ static int launch_shoot_products_m(myr_handle h, const ProdArgs& a) {
     hipLaunchKernelGGL((shoot_jvp_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, a.z, a.w, a.params, a.pstride, a.out);
   } else {
     double* g = scr + sweep / 8; double* zbar = g + (size_t)a.B * dm.n; double* cbuf = zbar + (size_t)a.B * dm.n;
-    const long tz = (long)a.B * dm.n, tl = (long)a.B * dm.m;
-    const unsigned ub_ = grid_for(tz);
-    for (int s = 0; s < a.nsteps; ++s) {
-      hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, (const double*)a.zio, a.params, a.pstride,
-                         (double*)nullptr, g, (double*)nullptr, (double*)nullptr, scr, (const double*)a.lamio, 1);
-      hipLaunchKernelGGL(exgd_update_kernel, dim3(ub_), dim3(256), 0, h->stream, tz, (const double*)a.zio, (const double*)g, a.lb, a.ub, a.eta_x, zbar);
-      hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, (const double*)zbar, a.params, a.pstride,
-                         (double*)nullptr, g, (double*)nullptr, (double*)nullptr, scr, (const double*)a.lamio, 1);
-      hipLaunchKernelGGL(exgd_update_kernel, dim3(ub_), dim3(256), 0, h->stream, tz, (const double*)a.zio, (const double*)g, a.lb, a.ub, a.eta_x, a.zio);
-      hipLaunchKernelGGL((shoot_eval_kernel<Sys, M>), grid, blk, 0, h->stream, a.B, I, cpi, method, h->d.T, (const double*)a.zio, a.params, a.pstride,
-                         (double*)nullptr, (double*)nullptr, cbuf, (double*)nullptr, scr, (const double*)nullptr, 1);
-      hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((tl + 255) / 256)), dim3(256), 0, h->stream, tl, a.eta_v, (const double*)cbuf, a.lamio);
-    }
+    rc = shoot_exgd_steps<Sys, M>(h, a.B, a.zio, a.lamio, a.lb, a.ub, a.params, a.pstride, a.eta_x, a.eta_v, a.nsteps, scr, g, zbar, cbuf, nullptr);
   }
-  return timed_end(h, MYR_K_PROD);
+  const int rc_end = timed_end(h, MYR_K_PROD);
+  return rc ? rc : rc_end;
 }
 
 template <class Sys>
@@ -1168,6 +1201,67 @@ int hvp_shoot_for_system(myr_handle h, const HvpArgs& a) {
   return fail(MYR_E_UNSUPPORTED, "myr_hvp: not built for this system");
 }
 
+// ------------------------------------------------------------------------------------------------
+// derivative of the unrolled extragradient steps under SHOOTING (shoot_exgd_grad.h: the seeded pair pass and the mask pass behind it)
+// ------------------------------------------------------------------------------------------------
+template <class Sys, int M>
+static int launch_shoot_exgd_grad(myr_handle h, const ShootExgdGradArgs& a) {
+  using HV = ShootHvp<Sys, M>;
+  const int I = h->d.intervals, cpi = h->d.controls_per_interval, method = h->d.integration_method;
+  const long n = h->dims.n, m = h->dims.m, np = h->dims.np, C = a.chunk, Pp = a.Pp;
+  // the chunk's scratch: the iterate of the forward steps and what they need, a_x, the direction, and a column per pair of a_lam, history and side record
+  double* zio = a.work;            double* lamio = zio + C * n;     double* g = lamio + C * m;      double* zbar = g + C * n;
+  double* cbuf = zbar + C * n;     double* scr = cbuf + C * m;      double* ax = scr + C * (long)(cpi + 1) * Sys::NS;
+  double* dir = ax + C * n;        double* al = dir + C * n;        double* phist = al + Pp * Sys::NS;
+  double* side = phist + Pp * HV::hist_doubles(cpi);
+  for (long b0 = 0; b0 < a.B; b0 += C) {      // chunks that share one history buffer, as launch_exgd_grad
+    const int nb = (int)(a.B - b0 < C ? a.B - b0 : C);
+    const long P = (long)nb * I, tz = (long)nb * n, tl = (long)nb * m, hs = 2 * tz + tl;
+    const double* lb = a.lb + b0 * n; const double* ub = a.ub + b0 * n;
+    const double* params = a.params ? a.params + b0 * a.pstride : nullptr;
+    double* rows = a.rows + b0 * np;
+    if (int rc = copy_doubles(h, zio, a.z + b0 * n, tz)) return rc;
+    if (int rc = copy_doubles(h, lamio, a.lam + b0 * m, tl)) return rc;
+    if (int rc = shoot_exgd_steps<Sys, M>(h, nb, zio, lamio, lb, ub, params, a.pstride, a.eta_x, a.eta_v, a.nsteps, scr, g, zbar, cbuf, a.hist)) return rc;
+    if (int rc = copy_doubles(h, ax, a.seed_z + b0 * n, tz)) return rc;
+    hipLaunchKernelGGL(shoot_exgd_grad_lam_kernel, dim3(grid_for(Pp * Sys::NS + tz + nb * np)), dim3(256), 0, h->stream, 1, nb, Pp, I, (int)Sys::NS, n, (int)np,
+                       a.seed_lam ? a.seed_lam + b0 * m : nullptr, al, dir, rows, (double*)nullptr);
+    auto pass = [&](const double* pt, const double* lam, double scale, int mode) {
+      hipLaunchKernelGGL((shoot_exgd_grad_pair_kernel<Sys, M>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, nb, Pp, I, cpi, method, h->d.T, pt,
+                         lam, (const double*)dir, params, a.pstride, scale, al, phist, side);
+      hipLaunchKernelGGL((shoot_exgd_grad_mask_kernel<Sys, M>), dim3(grid_for(tz + nb * np)), dim3(256), 0, h->stream, nb, Pp, I, cpi, mode, scale, a.eta_x,
+                         (const double*)side, (const double*)al, pt, lb, ub, ax, dir, rows);
+    };
+    if (a.nsteps > 0) pass(a.hist + a.nsteps * hs, nullptr, a.eta_v, SHOOT_MASK_STEP);      // at x_n, on the zero direction
+    for (int s = a.nsteps - 1; s >= 0; --s) {
+      const double* H = a.hist + s * hs;
+      pass(H + tz, H + 2 * tz, 0.0, SHOOT_MASK_BAR);
+      pass(H, H + 2 * tz, s > 0 ? a.eta_v : 0.0, s > 0 ? SHOOT_MASK_STEP : SHOOT_MASK_LAST);
+    }
+    if (a.dz0)
+      if (int rc = copy_doubles(h, a.dz0 + b0 * n, ax, tz)) return rc;
+    if (a.dlam0)
+      hipLaunchKernelGGL(shoot_exgd_grad_lam_kernel, dim3(grid_for(P * Sys::NS)), dim3(256), 0, h->stream, 0, nb, Pp, I, (int)Sys::NS, n, (int)np,
+                         (const double*)nullptr, al, (double*)nullptr, (double*)nullptr, a.dlam0 + b0 * m);
+  }
+  return MYR_OK;
+}
+
+// doubles of `work` for a chunk of C instances with Pp pair columns (the carve of launch_shoot_exgd_grad)
+static size_t shoot_exgd_grad_work_doubles(myr_handle h, size_t C, size_t Pp) {
+  const myr_dims& dm = h->dims;
+  const size_t cpi = h->d.controls_per_interval, Mr = h->d.integration_method == MYR_INT_RK4 ? 2 : 1;
+  return C * (5 * (size_t)dm.n + 2 * (size_t)dm.m + (cpi + 1) * dm.ns) + Pp * (dm.ns + cpi * 2 * dm.ns + dm.ns + (Mr * cpi + 1) * dm.nu + dm.np);
+}
+
+// myr_exgd_grad_shoot has refused the twins, the network system and the collocation transcriptions, each with its own message
+template <class Sys>
+int exgd_grad_shoot_for_system(myr_handle h, const ShootExgdGradArgs& a) {
+  if constexpr (SysDpw<Sys>::SUPPORTED)
+    return h->d.integration_method == MYR_INT_RK4 ? launch_shoot_exgd_grad<Sys, 2>(h, a) : launch_shoot_exgd_grad<Sys, 1>(h, a);
+  return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: not built for this system");
+}
+
 // ---- per-system entry points: explicit instantiation (system objects) / extern declaration (main object) -----------------
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
   LINK template int eval_for_system<S>(myr_handle, const EvalArgs&);          \
@@ -1179,10 +1273,11 @@ int hvp_shoot_for_system(myr_handle h, const HvpArgs& a) {
   LINK template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
   LINK template int hvp_shoot_for_system<S>(myr_handle, const HvpArgs&);      \
+  LINK template int exgd_grad_shoot_for_system<S>(myr_handle, const ShootExgdGradArgs&); \
   LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
 // a system's object in parts (the build splits the slow ones): -DMYR_TU_PART=1 the Hermite-Simpson wavefront solvers and the dispatch, 3 the trapezoidal
-// wavefront solvers, 4 the shooting solvers and the shooting Hessian-vector product, 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
+// wavefront solvers, 4 the shooting solvers, the shooting Hessian-vector product and the shooting derivative of the extragradient steps, 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
 #if MYR_TU_PART == 1
 template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 template int solve_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
@@ -1191,6 +1286,7 @@ template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const Solv
 #elif MYR_TU_PART == 4
 template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 template int hvp_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const HvpArgs&);
+template int exgd_grad_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ShootExgdGradArgs&);
 #elif MYR_TU_PART == 5
 template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 6
@@ -1218,7 +1314,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.5 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.6 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -2147,17 +2243,24 @@ extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t 
   return st.finish();
 }
 
+// history of one instance of myr_exgd_grad*: x_s, x_bar_s, lam_s of every step and the final x (`per` doubles); the batch runs in chunks of the
+// returned number of instances where the whole would pass the bound
+static int exgd_grad_chunk(myr_handle h, int B, int nsteps, size_t* per) {
+  const myr_dims& dm = h->dims;
+  *per = (size_t)nsteps * (2 * (size_t)dm.n + dm.m) + dm.n;
+  size_t bound = (size_t)1 << 30;
+  if (const char* e = getenv("MYRIAD_EXGD_GRAD_HIST_BYTES")) { const long long v = atoll(e); if (v > 0) bound = (size_t)v; }      // tests: force the chunked path
+  const size_t chunk = bound / (*per * 8);
+  return (int)(chunk < 1 ? 1 : (chunk > (size_t)B ? (size_t)B : chunk));
+}
+
 // device pointers throughout (a.hist, a.chunk and, for the batch sum, a.rows are set here); grad: [B][np] rows (grad_stride == np) or their sum
 static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, bool node = false) {
   const myr_dims& dm = h->dims;
-  // history of one instance: x_s, x_bar_s, lam_s of every step and the final x; the batch runs in chunks where the whole would pass the bound
-  const size_t per = ((size_t)a.nsteps * (2 * (size_t)dm.n + dm.m) + dm.n) * 8;
-  size_t bound = (size_t)1 << 30;
-  if (const char* e = getenv("MYRIAD_EXGD_GRAD_HIST_BYTES")) { const long long v = atoll(e); if (v > 0) bound = (size_t)v; }      // tests: force the chunked path
-  size_t chunk = bound / per;
-  a.chunk = (int)(chunk < 1 ? 1 : (chunk > (size_t)a.B ? (size_t)a.B : chunk));
+  size_t per;
+  a.chunk = exgd_grad_chunk(h, a.B, a.nsteps, &per);
   DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
-  st.scratch(a.hist, (size_t)a.chunk * (per / 8));
+  st.scratch(a.hist, (size_t)a.chunk * per);
   if (grad_stride) a.rows = grad;
   else st.scratch(a.rows, (size_t)a.B * dm.np);
   if (int rc = st.commit()) return rc;
@@ -2248,6 +2351,69 @@ extern "C" int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, cons
   st.out(a.dlam0, dlam0, nl);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, true)) return rc;
+  return st.finish();
+}
+
+// the same derivative under SHOOTING (shoot_exgd_grad.h).  Device pointers throughout (a.hist, a.work, a.chunk, a.Pp and, for the batch sum, a.rows are set here)
+static int dispatch_exgd_grad_shoot(myr_handle h, ShootExgdGradArgs a, double* grad, int grad_stride) {
+  const myr_dims& dm = h->dims;
+  const long I = h->d.intervals;
+  if ((long)a.B * I > (1L << 30)) return fail(MYR_E_CAPACITY, "myr_exgd_grad_shoot: more than 2^30 (instance, interval) pairs in one call");
+  size_t per;
+  a.chunk = exgd_grad_chunk(h, a.B, a.nsteps, &per);
+  const long P = (long)a.chunk * I;
+  a.Pp = (P + 63) / 64 * 64;
+  if (((a.Pp / 64) & 1) == 0) a.Pp += 64;      // an odd number of wavefronts, as padded_lanes
+  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
+  st.scratch(a.hist, (size_t)a.chunk * per);
+  st.scratch(a.work, shoot_exgd_grad_work_doubles(h, (size_t)a.chunk, (size_t)a.Pp));
+  if (grad_stride) a.rows = grad;
+  else st.scratch(a.rows, (size_t)a.B * dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
+  const int rc = for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_shoot_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, grad);
+  const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
+  return rc ? rc : rc_end;
+}
+
+extern "C" int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub, const double* params,
+                                   int32_t params_stride, double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam,
+                                   double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
+  const char* who = "myr_exgd_grad_shoot";
+  if (int rc = check_products_args(h, who, B, z, lam, lb, params, params_stride)) return rc;
+  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_shoot: null ub");
+  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_shoot: negative nsteps");
+  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_shoot: null seed_z or grad");
+  if (grad_stride != 0 && grad_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_exgd_grad_shoot: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (h->d.system_id >= 100)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: an elastic twin has no model of its own to differentiate; use the handle of its system");
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: the network system is not built (second derivatives in 4 804 weights); myr_exgd_grad_node has HERMITE_SIMPSON");
+  if (h->d.transcription != MYR_TR_SHOOTING)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: this handle's transcription is not SHOOTING; use myr_exgd_grad");
+  if (int rc = check_mem(who, mem)) return rc;
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
+  ShootExgdGradArgs a{};
+  a.B = B; a.pstride = params_stride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
+  double* g = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lb, lb, nz);
+  st.in(a.ub, ub, nz);
+  st.in(a.lam, lam, nl);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.in(a.seed_z, seed_z, nz);
+  st.in(a.seed_lam, seed_lam, nl);
+  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  st.out(a.dz0, dz0, nz);
+  st.out(a.dlam0, dlam0, nl);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_exgd_grad_shoot(h, a, g, grad_stride)) return rc;
   return st.finish();
 }
 

@@ -181,8 +181,13 @@ struct ShootHvp {
   // One (instance, interval) pair.  zb, vb: the instance's z and v ([I+1][NS] nodes, then [M S + 1][NU] control rows); lk: lam_k [NS] or null;
   // hist: hist_doubles(cpi) doubles and side: side_doubles(cpi) doubles of this pair, consecutive doubles `stride` apart (1 on the host, the padded
   // number of pairs on the device: batch-minor).  side = ad at the node [NS] | second-order cotangent of the interval's M cpi + 1 control rows | gp [NP]
+  // SEEDED (shoot_exgd_grad.h; myr_hvp runs SEEDED = false, where al and scale are not read): al [NS], `stride` apart, gets the pair's rows of J v,
+  // xd_end - v_{x_{k+1}}, added, and the reverse starts from ad = alpha = scale al instead of 0: it is linear in ad, so side then holds
+  // H v + (d x_end / d (x_k, u))^T alpha and gp gains (dc_k/dp)^T alpha
+  template <bool SEEDED = false>
   MYR_HD static inline void interval(int method, int I, int cpi, int k, double T, const double* zb, const double* vb, const double* lk,
-                                     const double* p, int with_cost, double* hist, double* side, long stride) {
+                                     const double* p, int with_cost, double* hist, double* side, long stride, double* al = nullptr,
+                                     double scale = 0.0) {
     const int S = I * cpi;
     const double h = T / S, cw = with_cost ? 1.0 : 0.0;
     const double* zu = zb + (long)(I + 1) * NS;
@@ -201,6 +206,14 @@ struct ShootHvp {
     double a[NS], ad[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) { a[q] = lk ? lk[q] : 0.0; ad[q] = 0.0; }
+    if constexpr (SEEDED) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) {
+        const double al_q = al[(long)q * stride] + (xd[q] - vb[(long)(k + 1) * NS + q]);
+        al[(long)q * stride] = al_q;
+        ad[q] = scale * al_q;
+      }
+    }
     if constexpr (Sys::HAS_TERMINAL) {
       // the terminal cost sits on the INTEGRATED end state of the last interval and the last control row: its (constant) gradient joins the costate,
       // and its p-derivative along the end state's tangent goes to out_p

@@ -4,17 +4,19 @@ The reference fits the model parameters so that PLANNING WITH THE MODEL reproduc
 guess by NUM_UNROLLED extragradient steps under the current parameters, then differentiates NUM_UNROLLED further steps from the advanced
 point in the parameters (`many_steps_grad`, forward mode, :148-177), contracts with the gradient of the imitation loss taken AT THAT SAME
 advanced point (`lookahead_update`, :209-218) and lets optax.adam(hp.adam_lr) move the parameters.  Here the steps are one device call
-(myr_exgd) and the contracted derivative another (myr_exgd_grad: one reverse sweep, csrc/exgd_grad.h); the loss, its gradient and Adam run in
-numpy on the host.  Two deviations from the reference's loop: nothing is pickled -- what it writes to disk every `save_and_reset_time` epochs is
+(myr_exgd) and the contracted derivative another (myr_exgd_grad: one reverse sweep, csrc/exgd_grad.h; under SHOOTING myr_exgd_grad_shoot,
+csrc/shoot_exgd_grad.h); the loss, its gradient and Adam run in numpy on the host.  Two deviations from the reference's loop: nothing is
+pickled -- what it writes to disk every `save_and_reset_time` epochs is
 returned instead, and a run never resumes from saved parameters (:233-241) --; and at a reset (:257-262) the reference splits hp.key and rebuilds the
 optimizer, which the reference's collocation optimisers answer with the same deterministic guess (no key enters hermite_simpson.py:37-48 /
-trapezoidal.py:34-50): the driver reuses the guess it started from.
+trapezoidal.py:34-50; nor the shooting guess: shooting.py:47 has its noise commented out): the driver reuses the guess it started from.
 
 EXTENSION: `start_states [B][ns]` runs B instances at once, each with its own true optimum (one batched solve) and its own guess; the loss is
 the mean over the batch and its gradient the batch sum of myr_exgd_grad (grad_stride 0) divided by B.
 
-The derivative is built for the collocation transcriptions.  The reference's default hyperparameters select SHOOTING: the library refuses
-that (NotImplementedError with its message) before anything is solved; the driver does not switch transcription on its own."""
+The reference's default hyperparameters select SHOOTING (intervals = 1, controls_per_interval = 100, HEUN).  That route is opt-in:
+`run_endtoend(..., shooting=True)` with a SHOOTING optimizer runs the same loop on myr_exgd_grad_shoot.  Without it myr_exgd_grad is asked, which
+refuses SHOOTING (NotImplementedError with its message) before anything is solved; the driver does not switch transcription on its own."""
 from __future__ import annotations
 
 from typing import Optional
@@ -52,25 +54,32 @@ def simple_imitation_loss(optimizer, xs_and_us, true_opt_us, epoch):
 
 def lookahead_gradient(optimizer, params, xs_and_us, lmbdas, true_opt_us, epoch, lb, ub, eta_x, eta_v) -> dict:
   """dJ/dp of lookahead_update (:209-218) in the keys of `params`: NUM_UNROLLED steps differentiated from (xs_and_us, lmbdas), contracted with
-  the loss gradient taken at that same point; for a batch the gradient of the mean loss (the batch sum of myr_exgd_grad divided by B)."""
+  the loss gradient taken at that same point; for a batch the gradient of the mean loss (the batch sum of myr_exgd_grad divided by B).  A SHOOTING
+  optimizer goes through myr_exgd_grad_shoot."""
   system = optimizer.system
   p, sign = split_params(system, params)
   _, dJ_dx = simple_imitation_loss(optimizer, xs_and_us, true_opt_us, epoch)
   B = 1 if np.ndim(xs_and_us) == 1 else np.shape(xs_and_us)[0]
-  g = optimizer.engine.exgd_grad(xs_and_us, lmbdas, lb, ub, eta_x, eta_v, NUM_UNROLLED, dJ_dx, params=p, reduce=True, want_start=False)["grad"]
+  call = optimizer.engine.exgd_grad_shoot if optimizer.transcription == "SHOOTING" else optimizer.engine.exgd_grad
+  g = call(xs_and_us, lmbdas, lb, ub, eta_x, eta_v, NUM_UNROLLED, dJ_dx, params=p, reduce=True, want_start=False)["grad"]
   g = g * sign / B
   return {k: float(g[system.param_names.index(k)]) for k in params}
 
 
-def run_endtoend(hp: HParams, cfg: Config, num_epochs: int = 10_000, start_states=None, save_and_reset_time: int = 1_000) -> Optional[dict]:
-  """e2e_sysid.py:29-297.  Returns {"params", "saved_params" {epoch: params}, "ts", "imitation_losses", "primal_guesses", "dual_guesses",
+def run_endtoend(hp: HParams, cfg: Config, num_epochs: int = 10_000, start_states=None, save_and_reset_time: int = 1_000,
+                 shooting: bool = False) -> Optional[dict]:
+  """e2e_sysid.py:29-297.  shooting=True admits a SHOOTING optimizer (myr_exgd_grad_shoot).  Returns {"params", "saved_params" {epoch: params}, "ts",
+  "imitation_losses", "primal_guesses", "dual_guesses",
   "true_opt_us"}; None for a system without parameter guesses (:30-32)."""
   if hp.system not in param_guesses:
     print("We do not currently support that kind of system for sysid. Exiting...")
     return None
   true_system = hp.system()
   optimizer = get_optimizer(hp, cfg, true_system)
-  optimizer.engine.exgd_grad_probe()                       # the library's own refusal (SHOOTING, ...), before the true optimum is solved for
+  if shooting and optimizer.transcription == "SHOOTING":   # the library's own refusal (SHOOTING without the opt-in, ...), before the true optimum is solved for
+    optimizer.engine.exgd_grad_shoot_probe()
+  else:
+    optimizer.engine.exgd_grad_probe()
   batched = start_states is not None
   if batched:
     x0s = np.asarray(start_states, dtype=np.float64)

@@ -216,7 +216,7 @@ class TrajectoryOptimizer(object):
   def unrolled_grad(self, variables, lmbdas, params, seed, nsteps, eta_x=None, eta_v=None, lb=None, ub=None, reduce=False):
     """seed . d x_nsteps / d params of `nsteps` extragradient steps from (variables, lmbdas) held fixed -- what the reference's
     many_steps_grad + lookahead_update compute (experiments/e2e_sysid.py:148-177, 209-218) --, by one reverse sweep on the device
-    (myr_exgd_grad).  variables [n] or [B,n], seed likewise (dJ/dx); params: a parameter mapping (None: the system's own).  Returns the
+    (myr_exgd_grad; myr_exgd_grad_shoot on a SHOOTING optimizer).  variables [n] or [B,n], seed likewise (dJ/dx); params: a parameter mapping (None: the system's own).  Returns the
     gradient in the device order of system.param_names, [np] ([B,np] for a batch; its sum over the batch with reduce).  lb / ub: bounds per
     instance (default: this optimizer's).  Over a NodeSystem `params` is the Haiku mapping of the weights and the gradient comes back as
     such a mapping (a list of them for a batch without reduce), through myr_exgd_grad_node."""
@@ -233,9 +233,9 @@ class TrajectoryOptimizer(object):
       return [mapping_from_flat(row) for row in out]
     from myriad_amd.experiments.mle_sysid import split_params
     p, sign = (self.system.device_params(), 1.0) if params is None else split_params(self.system, params)
-    out = self.engine.exgd_grad(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
-                                ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, seed, params=p, reduce=reduce,
-                                want_start=False)["grad"] * sign
+    call = self.engine.exgd_grad_shoot if self.transcription == "SHOOTING" else self.engine.exgd_grad      # (myr_exgd_grad_shoot / myr_exgd_grad)
+    out = call(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
+               ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, seed, params=p, reduce=reduce, want_start=False)["grad"] * sign
     return out[0] if single and not reduce else out
 
   # ---- what stands in for IPOPT's restoration phase ---------------------------------------------------------------------
