@@ -276,6 +276,12 @@ int myr_rollout(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, cons
  * z [B][n], lam [B][m], v [B][n]; layouts and row order as in myr_eval.  Collocation: pointwise / intervalwise kernels;
  * SHOOTING (EULER, HEUN, MIDPOINT, RK4 -- whatever hp.integration_method selects, utils.py:91-96, shooting.py:230-241): reverse
  * sweep seeded with lam / forward tangents through the steps (RK4: two control rows per step, u[2i], u[2i+1], u[2i+2]).
+ * MYR_SYS_NODE_CARTPOLE (library version 0.7): HERMITE_SIMPSON and SHOOTING with all four integration rules; params required,
+ * params_stride 0 or np; MYR_TR_TRAPEZOIDAL is MYR_E_UNSUPPORTED.  Under SHOOTING a lane holds one (instance, interval) pair and the 64
+ * lanes of a wavefront pairs of different instances, so that a network pass fills up to four 16-point matrix-core tiles
+ * (csrc/node_shoot_products.h); a workgroup owns whole instances (params_stride == np: one).  How many depends on intervals,
+ * controls_per_interval and params_stride only: an instance's result has the same bits whatever its batch.  MYR_E_CAPACITY beyond
+ * ~12 000 intervals.
  */
 int myr_vjp(myr_handle h, int32_t B, const double* z, const double* lam, const double* params, int32_t params_stride,
             double* out, int32_t add_gradf, int32_t mem);
@@ -287,6 +293,8 @@ int myr_jvp(myr_handle h, int32_t B, const double* z, const double* v, const dou
  *   x_bar = clip(x - eta_x dL/dx(x, lam), lb, ub);  x_new = clip(x - eta_x dL/dx(x_bar, lam), lb, ub);
  *   lam_new = lam + eta_v c(x_new)
  * z [B][n] and lam [B][m] are updated in place; lb, ub [B][n].
+ * MYR_SYS_NODE_CARTPOLE under SHOOTING (version 0.7): ONE launch for the whole call -- the workgroup that owns an instance loops over the steps
+ * with z, x_bar, the gradient and lam in LDS (in the handle's global scratch where one instance does not fit); coverage and packing as myr_vjp.
  */
 int myr_exgd(myr_handle h, int32_t B, double* z, double* lam, const double* lb, const double* ub, const double* params,
              int32_t params_stride, double eta_x, double eta_v, int32_t nsteps, int32_t mem);

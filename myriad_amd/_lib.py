@@ -426,6 +426,12 @@ class Engine:
     _chk(getattr(self.lib, _call)(self._h, 0, _addr(d), _addr(d), _addr(d), _addr(d), None, 0, 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None, None,
                                   MEM_HOST), _call)
 
+  def exgd_grad_node_probe(self):
+    """Raises the library's error when myr_exgd_grad_node is not built for this handle (an empty batch: the checks run, nothing else)."""
+    d = np.zeros(1)
+    _chk(self.lib.myr_exgd_grad_node(self._h, 0, _addr(d), _addr(d), _addr(d), _addr(d), _addr(d), 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None, None,
+                                     MEM_HOST), "myr_exgd_grad_node")
+
   def exgd_grad_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam=None, params=None, params_stride=0,
                        dz0=None, dlam0=None, _call="myr_exgd_grad"):
     """Zero-copy variant of exgd_grad: every array is a device tensor on this handle's device."""

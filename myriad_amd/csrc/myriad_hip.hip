@@ -30,6 +30,7 @@
 #include "colloc_hvp.h"
 #include "shoot_hvp.h"
 #include "shoot_exgd_grad.h"
+#include "node_shoot_products.h"
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
@@ -143,6 +144,7 @@ struct myr_handle_s {
   bool plan_frozen = false;                     //   (second starts re-launch on this handle: they leave the first attempt's record alone)
   int reg_fill = 0;                    // MYRIAD_REG_FILL (tests): pattern left in every VGPR / AGPR of every SIMD before every solver launch (1 nan, 2 finite, 3 big, 4 zero)
   unsigned long long stack_fill = 0;   // MYRIAD_STACK_FILL (tests / experiments): bit pattern left in the queue's private-segment memory before every solver launch
+  int prod_lane = 0;                   // MYRIAD_PROD_MODE=lane (developer switch): the products of a NODE system under SHOOTING by the per-lane kernels (cross-check, timing baseline)
 };
 
 static int device_cus(myr_handle h) {
@@ -506,10 +508,59 @@ static int launch_shoot_products(myr_handle h, const ProdArgs& a) {
   return h->d.integration_method == MYR_INT_RK4 ? launch_shoot_products_m<Sys, 2>(h, a) : launch_shoot_products_m<Sys, 1>(h, a);
 }
 
+// NODE systems under shooting: ONE launch per call, lane = (instance, interval) pair, the network by matrix-core passes (node_shoot_products.h).
+// G instances per workgroup from I, cpi and params_stride alone -- never from the batch size: an instance's bits do not depend on its batch.
+template <class Sys, int M>
+static int launch_node_shoot_products(myr_handle h, const ProdArgs& a) {
+  if constexpr (NodeTraits<Sys>::mlp) {
+    using P = NodeShootProd<Sys, M>;
+    using L = NspLds<Sys, M>;
+    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+    const long lds_max = 160 * 1024 / 8;
+    const long fixed = L::fixed_doubles(I), per = L::iter_doubles(I, cpi);
+    if (fixed > lds_max) return fail(MYR_E_CAPACITY, "products: intervals too large for the LDS slots of the shared control rows");
+    NspArgs k{};
+    k.op = a.op == PRODOP_VJP ? NSP_VJP : (a.op == PRODOP_JVP ? NSP_JVP : NSP_EXGD);
+    k.B = a.B; k.I = I; k.cpi = cpi; k.method = h->d.integration_method; k.T = h->d.T;
+    k.z = a.z; k.w = a.w; k.params = a.params; k.pstride = a.pstride; k.out = a.out; k.add_gradf = a.add_gradf;
+    k.zio = a.zio; k.lamio = a.lamio; k.lb = a.lb; k.ub = a.ub; k.eta_x = a.eta_x; k.eta_v = a.eta_v; k.nsteps = a.nsteps;
+    int G = (a.pstride != 0 || I > 64) ? 1 : 64 / I;
+    bool iter_global = false;
+    if (a.op == PRODOP_EXGD) {      // z, x_bar, g, lam of the group in LDS: fewer instances per workgroup where 64 lanes' worth do not fit, global scratch where one does not
+      const long fit = (lds_max - fixed) / per;
+      if (fit < 1) iter_global = true;
+      else if (fit < G) G = (int)fit;
+    }
+    k.G = G;
+    const long groups = ((long)a.B + G - 1) / G;
+    const long pairs = (long)a.B * I;
+    k.Pp = (pairs + 63) / 64 * 64;
+    const size_t scr_bytes = (size_t)P::pair_doubles(cpi) * (size_t)k.Pp * 8;
+    const size_t iter_bytes = iter_global ? (size_t)groups * (size_t)G * (size_t)per * 8 : 0;
+    if (int rc = ensure_buf(&h->sbuf, &h->sbuf_bytes, scr_bytes + iter_bytes)) return rc;
+    k.scr = (double*)h->sbuf;
+    k.iter = iter_global ? k.scr + scr_bytes / 8 : nullptr;
+    k.lds_doubles = fixed + (a.op == PRODOP_EXGD && !iter_global ? (long)G * per : 0);
+    k.poison = h->poison;
+    auto kern = node_shoot_products_kernel<Sys, M>;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(64), (size_t)k.lds_doubles * 8, h->stream, k);
+    return timed_end(h, MYR_K_PROD);
+  } else {
+    (void)a;
+    return fail(MYR_E_UNSUPPORTED, "products: this NODE system has no matrix-core passes");
+  }
+}
+
 template <class Sys>
 int products_for_system(myr_handle h, const ProdArgs& a) {
   if constexpr (Sys::PARAMS_BY_POINTER) {
-    if (h->d.transcription != MYR_TR_HERMITE_SIMPSON) return fail(MYR_E_UNSUPPORTED, "products: NODE systems are built for HERMITE_SIMPSON");
+    if (h->d.transcription == MYR_TR_SHOOTING) {      // the reference's default route for a NodeSystem (config.py:66): matrix-core passes over pairs (node_shoot_products.h)
+      if (h->prod_lane) return launch_shoot_products<Sys>(h, a);
+      return h->d.integration_method == MYR_INT_RK4 ? launch_node_shoot_products<Sys, 2>(h, a) : launch_node_shoot_products<Sys, 1>(h, a);
+    }
+    if (h->d.transcription != MYR_TR_HERMITE_SIMPSON) return fail(MYR_E_UNSUPPORTED, "products: NODE systems are built for HERMITE_SIMPSON and SHOOTING");
     return launch_products<Sys, PROD_HS>(h, a);
   } else {
     switch (h->d.transcription) {
@@ -1314,7 +1365,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.6 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.7 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -1403,6 +1454,7 @@ extern "C" int myr_create(const myr_problem_desc* desc, myr_handle* out) {
   if (l) { int v = atoi(l); if (v >= 1 && v <= 64) h->solve_lpw = v; }
   if (const char* e = getenv("MYRIAD_REG_FILL")) h->reg_fill = !strcmp(e, "nan") ? 1 : (!strcmp(e, "random") ? 2 : (!strcmp(e, "big") ? 3 : (!strcmp(e, "zero") ? 4 : 0)));
   if (const char* e = getenv("MYRIAD_STACK_FILL")) h->stack_fill = !strcmp(e, "nan") ? 1 : (!strcmp(e, "random") ? 2 : (!strcmp(e, "big") ? 3 : (!strcmp(e, "zero") ? 4 : 0)));
+  if (const char* e = getenv("MYRIAD_PROD_MODE")) h->prod_lane = !strcmp(e, "lane");      // developer switch: see prod_lane
   if (const char* e = getenv("MYRIAD_NODE_EXGD_WPI")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->node_exgd_wpi = v; }      // developer knob
   if (const char* e = getenv("MYRIAD_NODE_HELPERS")) h->node_helpers = atoi(e);   // developer knob: helper workgroups per trajectory of the network kernel (0 = none)
   if (const char* e = getenv("MYRIAD_PARK_ITER")) h->park_iter = atoi(e);         // developer knob: iterations of phase 1 of the two-phase launch (0 = off)

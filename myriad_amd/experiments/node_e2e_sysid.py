@@ -77,6 +77,8 @@ def run_node_endtoend(hp: HParams, cfg: Config, num_epochs: int = 10_000, node: 
   true_system = hp.system()
   true_optimizer = get_optimizer(hp, cfg, true_system)           # :49
   node_optimizer = get_optimizer(hp, cfg, NodeSystem(node=node, true_system=true_system))      # :50-51
+  if node_optimizer.transcription != "HERMITE_SIMPSON":      # the library's own refusal (the weight gradient is built for Hermite-Simpson), before the true optimum is solved for
+    node_optimizer.engine.exgd_grad_node_probe()
   batched = start_states is not None
   if batched:
     x0s = np.asarray(start_states, dtype=np.float64)
