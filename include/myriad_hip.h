@@ -22,6 +22,7 @@
  *                                                experiments/node_e2e_sysid.py:139-166, 187-196  myr_exgd_grad_node
  *   many_steps_grad / lookahead_update under SHOOTING (the default hyperparameters)
  *                                                experiments/e2e_sysid.py:148-177, 209-218  myr_exgd_grad_shoot
+ *   ... in the network weights under SHOOTING     experiments/node_e2e_sysid.py:139-166, 187-196  myr_exgd_grad_node_shoot
  *   jax.hessian / jax.jvp(jax.grad(lagrangian))  (no call site in the reference: the exact second derivative
  *                                                an external second-order method asks for)  myr_hvp
  *
@@ -389,6 +390,28 @@ int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, const double* 
                         const double* params, int32_t params_stride, double eta_x, double eta_v, int32_t nsteps,
                         const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
                         double* dz0, double* dlam0, int32_t mem);
+
+/*
+ * myr_exgd_grad_node under MYR_TR_SHOOTING (the transcription the reference's experiments/node_e2e_sysid.py runs with its default
+ * hyperparameters; library version 0.8): the step is myr_exgd's on a MYR_SYS_NODE_CARTPOLE + MYR_TR_SHOOTING handle, with all four
+ * integrators.  Arguments, null rules, outputs and MYR_E_ARG cases are myr_exgd_grad_node's: ONE weight set params [np], required; grad [B][np]
+ * if grad_stride == np, [np] = their fixed-order sum if grad_stride == 0; seed_lam, dz0, dlam0 may be NULL; nsteps == 0 gives grad = 0,
+ * dz0 = seed_z, dlam0 = seed_lam; B == 0 writes nothing; inputs are not modified; a variable on a bound or pinned passes nothing on; the same
+ * history in the handle's scratch (chunks under the same 1 GiB bound, chunked and unchunked the same bits), the same bits for MYR_MEM_HOST
+ * and MYR_MEM_DEVICE, on every call, and for an instance alone or inside any batch.
+ * One workgroup of 1, 2 or 4 wavefronts (from the number of intervals alone) per instance, one wavefront per (instance, interval) pair, lane j =
+ * hidden unit j of both layers; myr_exgd_grad_shoot's 2 nsteps + 1 pair passes with the network differentiated layer by layer at every
+ * stage point, the running cost of the true system included at each (csrc/node_shoot_exgd_grad.h).
+ * MYR_E_UNSUPPORTED: a handle whose system is not MYR_SYS_NODE_CARTPOLE (use myr_exgd_grad_shoot), MYR_TR_HERMITE_SIMPSON (use
+ * myr_exgd_grad_node), MYR_TR_TRAPEZOIDAL; MYR_E_CAPACITY: the weight copy (5 064 doubles) and the sweep's
+ * 3 n + I (3 ns + 2 ns cpi + (M cpi + 1) nu) doubles (M = 2 for RK4, 1 otherwise) pass the 160 KiB LDS -- about 1 250 integration steps
+ * I cpi in all, 950 under RK4 (1 x 100 HEUN needs 50 KiB; 1 x 2 000 is refused).  myr_exgd_grad_node keeps refusing every transcription but Hermite-Simpson,
+ * myr_exgd_grad_shoot and myr_hvp the network system.
+ */
+int myr_exgd_grad_node_shoot(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub,
+                             const double* params, double eta_x, double eta_v, int32_t nsteps,
+                             const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
+                             double* dz0, double* dlam0, int32_t mem);
 
 /*
  * Lagrangian Hessian-vector product, matrix-free and exact, for all three transcriptions (library version 0.4).  With

@@ -31,7 +31,7 @@ STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr
 EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
            "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
            "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp",
-           "myr_exgd_grad_node", "myr_exgd_grad_shoot"]
+           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot"]
 
 
 class ProblemDesc(C.Structure):
@@ -115,6 +115,8 @@ def load() -> C.CDLL:
   lib.myr_exgd_grad_shoot.restype = C.c_int
   lib.myr_exgd_grad_node.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
   lib.myr_exgd_grad_node.restype = C.c_int
+  lib.myr_exgd_grad_node_shoot.argtypes = lib.myr_exgd_grad_node.argtypes
+  lib.myr_exgd_grad_node_shoot.restype = C.c_int
   lib.myr_hvp.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, C.c_int32, C.c_int32]
   lib.myr_hvp.restype = C.c_int
   lib.myr_fbsm.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_double, C.c_double, C.c_int32,
@@ -426,11 +428,11 @@ class Engine:
     _chk(getattr(self.lib, _call)(self._h, 0, _addr(d), _addr(d), _addr(d), _addr(d), None, 0, 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None, None,
                                   MEM_HOST), _call)
 
-  def exgd_grad_node_probe(self):
+  def exgd_grad_node_probe(self, _call="myr_exgd_grad_node"):
     """Raises the library's error when myr_exgd_grad_node is not built for this handle (an empty batch: the checks run, nothing else)."""
     d = np.zeros(1)
-    _chk(self.lib.myr_exgd_grad_node(self._h, 0, _addr(d), _addr(d), _addr(d), _addr(d), _addr(d), 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None, None,
-                                     MEM_HOST), "myr_exgd_grad_node")
+    _chk(getattr(self.lib, _call)(self._h, 0, _addr(d), _addr(d), _addr(d), _addr(d), _addr(d), 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None, None,
+                                  MEM_HOST), _call)
 
   def exgd_grad_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam=None, params=None, params_stride=0,
                        dz0=None, dlam0=None, _call="myr_exgd_grad"):
@@ -452,7 +454,8 @@ class Engine:
     self.exgd_grad_device(B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam, params, params_stride, dz0, dlam0,
                           _call="myr_exgd_grad_shoot")
 
-  def exgd_grad_node(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
+  def exgd_grad_node(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True,
+                     _call="myr_exgd_grad_node"):
     """myr_exgd_grad_node: exgd_grad in the 4 804 shared weights of the network system (`params`: the flat vector of csrc/node_system.h's order;
     Hermite-Simpson).  Returns {"grad" [B,np], or [np] = the sum over the batch with reduce=True, "dz0" [B,n], "dlam0" [B,m]}."""
     z = self._batch2(z, self.n, "z"); lam = self._batch2(lam, self.m, "lam")
@@ -469,19 +472,32 @@ class Engine:
     grad = np.empty(self.np) if reduce else np.empty((B, self.np))
     dz0 = np.empty((B, self.n)) if want_start else None
     dlam0 = np.empty((B, self.m)) if want_start else None
-    _chk(self.lib.myr_exgd_grad_node(self._h, B, _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(p), float(eta_x), float(eta_v), int(nsteps),
-                                     _addr(sz), _addr(sl), _addr(grad), 0 if reduce else self.np, _addr(dz0), _addr(dlam0), MEM_HOST),
-         "myr_exgd_grad_node")
+    _chk(getattr(self.lib, _call)(self._h, B, _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(p), float(eta_x), float(eta_v), int(nsteps),
+                                  _addr(sz), _addr(sl), _addr(grad), 0 if reduce else self.np, _addr(dz0), _addr(dlam0), MEM_HOST), _call)
     out = {"grad": grad}
     if want_start:
       out["dz0"] = dz0; out["dlam0"] = dlam0
     return out
 
-  def exgd_grad_node_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None, dlam0=None):
+  def exgd_grad_node_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None, dlam0=None,
+                            _call="myr_exgd_grad_node"):
     """Zero-copy variant of exgd_grad_node: every array is a device tensor on this handle's device."""
-    _chk(self.lib.myr_exgd_grad_node(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), float(eta_x), float(eta_v),
-                                     int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
-                                     MEM_DEVICE), "myr_exgd_grad_node")
+    _chk(getattr(self.lib, _call)(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), float(eta_x), float(eta_v),
+                                  int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
+                                  MEM_DEVICE), _call)
+
+  # myr_exgd_grad_node_shoot: the same derivative in the weights on a SHOOTING handle (csrc/node_shoot_exgd_grad.h) -- the signatures, the return
+  # dict and the checks of the three methods above; myr_exgd_grad_node itself keeps refusing SHOOTING
+  def exgd_grad_node_shoot(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
+    return self.exgd_grad_node(z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam, reduce, want_start, _call="myr_exgd_grad_node_shoot")
+
+  def exgd_grad_node_shoot_probe(self):
+    self.exgd_grad_node_probe(_call="myr_exgd_grad_node_shoot")
+
+  def exgd_grad_node_shoot_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None,
+                                  dlam0=None):
+    self.exgd_grad_node_device(B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam, dz0, dlam0,
+                               _call="myr_exgd_grad_node_shoot")
 
   def hvp(self, z, lam, v, params=None, with_cost=True, want_z=True, want_p=False, reduce=False):
     """myr_hvp: Lagrangian Hessian-vector product.  With L = f + lam^T c (f dropped when with_cost is false) and psi = <grad_z L, v>:

@@ -31,6 +31,7 @@
 #include "shoot_hvp.h"
 #include "shoot_exgd_grad.h"
 #include "node_shoot_products.h"
+#include "node_shoot_exgd_grad.h"
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
@@ -1313,6 +1314,39 @@ int exgd_grad_shoot_for_system(myr_handle h, const ShootExgdGradArgs& a) {
   return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: not built for this system");
 }
 
+// ------------------------------------------------------------------------------------------------
+// derivative of the unrolled extragradient steps in the weights of the network system under SHOOTING (node_shoot_exgd_grad.h: one launch per chunk;
+// myr_exgd_grad_node_shoot has checked system, transcription and that the LDS carve fits)
+// ------------------------------------------------------------------------------------------------
+template <int M>
+static int launch_node_shoot_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
+  const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+  const myr_dims& dm = h->dims;
+  const size_t lds = node_shoot_exgd_grad_lds_bytes<M>(I, cpi);
+  const int wpi = node_shoot_exgd_grad_wpi(I);
+  auto kern = node_shoot_exgd_grad_kernel<M>;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  for (long b0 = 0; b0 < a.B; b0 += a.chunk) {      // (chunks that share one history buffer, as launch_node_exgd_grad)
+    NseArgs k{};
+    k.B = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
+    k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.nsteps = a.nsteps;
+    k.T = h->d.T; k.eta_x = a.eta_x; k.eta_v = a.eta_v;
+    k.z = a.z + b0 * dm.n; k.lam = a.lam + b0 * dm.m; k.lb = a.lb + b0 * dm.n; k.ub = a.ub + b0 * dm.n; k.params = a.params;
+    k.seed_z = a.seed_z + b0 * dm.n; k.seed_lam = a.seed_lam ? a.seed_lam + b0 * dm.m : nullptr;
+    k.hist = a.hist; k.grad = a.rows + b0 * dm.np;
+    k.dz0 = a.dz0 ? a.dz0 + b0 * dm.n : nullptr; k.dlam0 = a.dlam0 ? a.dlam0 + b0 * dm.m : nullptr;
+    hipLaunchKernelGGL(kern, dim3((unsigned)k.B), dim3(64 * wpi), lds, h->stream, k);
+  }
+  return MYR_OK;
+}
+
+template <class Sys>
+int exgd_grad_node_shoot_for_system(myr_handle h, const ExgdGradArgs& a) {
+  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value)      // the kernel lives in the network system's object only
+    return h->d.integration_method == MYR_INT_RK4 ? launch_node_shoot_exgd_grad<2>(h, a) : launch_node_shoot_exgd_grad<1>(h, a);
+  return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: the network system only; use myr_exgd_grad_shoot");
+}
+
 // ---- per-system entry points: explicit instantiation (system objects) / extern declaration (main object) -----------------
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
   LINK template int eval_for_system<S>(myr_handle, const EvalArgs&);          \
@@ -1325,10 +1359,11 @@ int exgd_grad_shoot_for_system(myr_handle h, const ShootExgdGradArgs& a) {
   LINK template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
   LINK template int hvp_shoot_for_system<S>(myr_handle, const HvpArgs&);      \
   LINK template int exgd_grad_shoot_for_system<S>(myr_handle, const ShootExgdGradArgs&); \
+  LINK template int exgd_grad_node_shoot_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
 // a system's object in parts (the build splits the slow ones): -DMYR_TU_PART=1 the Hermite-Simpson wavefront solvers and the dispatch, 3 the trapezoidal
-// wavefront solvers, 4 the shooting solvers, the shooting Hessian-vector product and the shooting derivative of the extragradient steps, 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
+// wavefront solvers, 4 the shooting solvers, the shooting Hessian-vector product and the shooting derivatives of the extragradient steps (closed-form and network), 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
 #if MYR_TU_PART == 1
 template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 template int solve_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
@@ -1338,6 +1373,7 @@ template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const Solv
 template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 template int hvp_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const HvpArgs&);
 template int exgd_grad_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ShootExgdGradArgs&);
+template int exgd_grad_node_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ExgdGradArgs&);
 #elif MYR_TU_PART == 5
 template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 6
@@ -1365,7 +1401,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.7 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.8 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -2307,7 +2343,8 @@ static int exgd_grad_chunk(myr_handle h, int B, int nsteps, size_t* per) {
 }
 
 // device pointers throughout (a.hist, a.chunk and, for the batch sum, a.rows are set here); grad: [B][np] rows (grad_stride == np) or their sum
-static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, bool node = false) {
+enum { EXGD_GRAD_CLOSED_FORM = 0, EXGD_GRAD_NODE = 1, EXGD_GRAD_NODE_SHOOT = 2 };      // which kernel family runs the sweep
+static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, int route = EXGD_GRAD_CLOSED_FORM) {
   const myr_dims& dm = h->dims;
   size_t per;
   a.chunk = exgd_grad_chunk(h, a.B, a.nsteps, &per);
@@ -2317,8 +2354,9 @@ static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int gr
   else st.scratch(a.rows, (size_t)a.B * dm.np);
   if (int rc = st.commit()) return rc;
   if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
-  const int rc = node ? exgd_grad_node_for_system<SysNODE_CARTPOLE>(h, a)
-                      : for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+  const int rc = route == EXGD_GRAD_NODE_SHOOT ? exgd_grad_node_shoot_for_system<SysNODE_CARTPOLE>(h, a)
+                 : route == EXGD_GRAD_NODE ? exgd_grad_node_for_system<SysNODE_CARTPOLE>(h, a)
+                 : for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
   if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, grad);
   const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
   return rc ? rc : rc_end;
@@ -2402,7 +2440,56 @@ extern "C" int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, cons
   st.out(a.dz0, dz0, nz);
   st.out(a.dlam0, dlam0, nl);
   if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, true)) return rc;
+  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, EXGD_GRAD_NODE)) return rc;
+  return st.finish();
+}
+
+// ... and under SHOOTING (node_shoot_exgd_grad.h): the arguments, null rules and outputs of myr_exgd_grad_node
+extern "C" int myr_exgd_grad_node_shoot(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub,
+                                        const double* params, double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam,
+                                        double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
+  const char* who = "myr_exgd_grad_node_shoot";
+  if (!h || !z || !lam || !lb) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: null handle or array");
+  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: null ub");
+  if (int rc = check_batch(who, B)) return rc;
+  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: negative nsteps");
+  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: null seed_z or grad");
+  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: this handle's system is not the network system; use myr_exgd_grad_shoot");
+  if (h->d.transcription == MYR_TR_HERMITE_SIMPSON)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: this handle's transcription is HERMITE_SIMPSON, not SHOOTING; use myr_exgd_grad_node");
+  if (h->d.transcription != MYR_TR_SHOOTING)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: TRAPEZOIDAL is not built for the network system; SHOOTING only");
+  if (int rc = check_node_weights(h, who, params)) return rc;
+  if (grad_stride != 0 && grad_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_mem(who, mem)) return rc;
+  {
+    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_shoot_exgd_grad_lds_bytes<2>(I, cpi) : node_shoot_exgd_grad_lds_bytes<1>(I, cpi);
+    if (lds > 160 * 1024)
+      return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_shoot: intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy");
+  }
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
+  ExgdGradArgs a{};
+  a.B = B; a.pstride = 0; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
+  double* g = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lb, lb, nz);
+  st.in(a.ub, ub, nz);
+  st.in(a.lam, lam, nl);
+  st.in(a.params, params, (size_t)dm.np);
+  st.in(a.seed_z, seed_z, nz);
+  st.in(a.seed_lam, seed_lam, nl);
+  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  st.out(a.dz0, dz0, nz);
+  st.out(a.dlam0, dlam0, nl);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, EXGD_GRAD_NODE_SHOOT)) return rc;
   return st.finish();
 }
 

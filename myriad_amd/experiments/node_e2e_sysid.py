@@ -4,7 +4,11 @@ The reference trains the weights of the (64, 64) MLP so that PLANNING THROUGH TH
 guess advances by hp.num_unrolled extragradient steps under the current weights (:276-277), then hp.num_unrolled further steps are
 differentiated in the weights from the advanced point (`many_steps_grad`, :139-166), contracted with the gradient of the imitation loss taken at
 that same point (`lookahead_update`, :187-196), and optax.adam(1e-4) -- hard-coded, :94 -- moves the weights.  Here the steps are one device call
-(myr_exgd) and the contracted derivative another (myr_exgd_grad_node: one reverse sweep, csrc/node_exgd_grad.h); loss and Adam run in numpy.
+(myr_exgd) and the contracted derivative another (myr_exgd_grad_node: one reverse sweep, csrc/node_exgd_grad.h; under SHOOTING
+myr_exgd_grad_node_shoot, csrc/node_shoot_exgd_grad.h); loss and Adam run in numpy.
+
+`run_node_endtoend(..., shooting=True)` with a SHOOTING optimizer -- the reference's default hyperparameters -- runs the same loop on
+myr_exgd_grad_node_shoot.  Without it myr_exgd_grad_node is asked, which refuses every transcription but Hermite-Simpson before anything is solved.
 
 As e2e_sysid.run_endtoend: nothing is pickled or plotted in the loop -- what the reference writes to disk is returned --, a run never resumes
 from saved weights, and the guess a reset rebuilds (:231-234) is the deterministic one the run started from.  The imitation loss carries NO
@@ -58,16 +62,17 @@ def simple_imitation_loss(optimizer, xs_and_us, true_opt_us):
 
 def lookahead_gradient(optimizer, true_optimizer, flat, xs_and_us, lmbdas, true_opt_us, lb, ub, eta_x, eta_v, nsteps) -> np.ndarray:
   """dJ/dweights of lookahead_update (:187-196) as the flat row: `nsteps` steps differentiated from (xs_and_us, lmbdas), contracted with the loss
-  gradient taken at that same point; for a batch the gradient of the mean loss"""
+  gradient taken at that same point; for a batch the gradient of the mean loss.  A SHOOTING optimizer goes through myr_exgd_grad_node_shoot."""
   _, dJ_dx = simple_imitation_loss(true_optimizer, xs_and_us, true_opt_us)
   B = 1 if np.ndim(xs_and_us) == 1 else np.shape(xs_and_us)[0]
-  g = optimizer.engine.exgd_grad_node(xs_and_us, lmbdas, lb, ub, eta_x, eta_v, nsteps, dJ_dx, flat, reduce=True, want_start=False)["grad"]
+  call = optimizer.engine.exgd_grad_node_shoot if optimizer.transcription == "SHOOTING" else optimizer.engine.exgd_grad_node
+  g = call(xs_and_us, lmbdas, lb, ub, eta_x, eta_v, nsteps, dJ_dx, flat, reduce=True, want_start=False)["grad"]
   return g / B
 
 
 def run_node_endtoend(hp: HParams, cfg: Config, num_epochs: int = 10_000, node: Optional[NeuralODE] = None, start_states=None,
-                      save_and_reset_time: int = 1_000) -> Optional[dict]:
-  """node_e2e_sysid.py:24-291.  Returns {"params" (Haiku mapping), "saved_params" {epoch: mapping}, "ts", "imitation_losses", "primal_guesses",
+                      save_and_reset_time: int = 1_000, shooting: bool = False) -> Optional[dict]:
+  """node_e2e_sysid.py:24-291.  shooting=True admits a SHOOTING optimizer (myr_exgd_grad_node_shoot).  Returns {"params" (Haiku mapping), "saved_params" {epoch: mapping}, "ts", "imitation_losses", "primal_guesses",
   "dual_guesses", "true_opt_us"}; None for a system without parameter guesses (:25-27)."""
   if hp.system not in param_guesses:
     print("We do not currently support that kind of system for sysid. Exiting...")
@@ -77,7 +82,9 @@ def run_node_endtoend(hp: HParams, cfg: Config, num_epochs: int = 10_000, node: 
   true_system = hp.system()
   true_optimizer = get_optimizer(hp, cfg, true_system)           # :49
   node_optimizer = get_optimizer(hp, cfg, NodeSystem(node=node, true_system=true_system))      # :50-51
-  if node_optimizer.transcription != "HERMITE_SIMPSON":      # the library's own refusal (the weight gradient is built for Hermite-Simpson), before the true optimum is solved for
+  if shooting and node_optimizer.transcription == "SHOOTING":      # the library's own refusals, before the true optimum is solved for
+    node_optimizer.engine.exgd_grad_node_shoot_probe()
+  elif node_optimizer.transcription != "HERMITE_SIMPSON":      # (without the opt-in the weight gradient is asked of myr_exgd_grad_node: Hermite-Simpson only)
     node_optimizer.engine.exgd_grad_node_probe()
   batched = start_states is not None
   if batched:

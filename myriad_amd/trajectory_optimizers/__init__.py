@@ -219,15 +219,15 @@ class TrajectoryOptimizer(object):
     (myr_exgd_grad; myr_exgd_grad_shoot on a SHOOTING optimizer).  variables [n] or [B,n], seed likewise (dJ/dx); params: a parameter mapping (None: the system's own).  Returns the
     gradient in the device order of system.param_names, [np] ([B,np] for a batch; its sum over the batch with reduce).  lb / ub: bounds per
     instance (default: this optimizer's).  Over a NodeSystem `params` is the Haiku mapping of the weights and the gradient comes back as
-    such a mapping (a list of them for a batch without reduce), through myr_exgd_grad_node."""
+    such a mapping (a list of them for a batch without reduce), through myr_exgd_grad_node (myr_exgd_grad_node_shoot on a SHOOTING optimizer)."""
     ex, ev = self.step_sizes()
     single = np.ndim(variables) == 1
     if self.system.name == "NODE_CARTPOLE":      # a Haiku mapping in, the gradient as a mapping out (myr_exgd_grad_node; a batch: the sum with reduce)
       from myriad_amd.systems.neural_ode import flat_from_mapping, mapping_from_flat
       flat = self.system.device_params() if params is None else flat_from_mapping(params)
-      out = self.engine.exgd_grad_node(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
-                                       ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, seed, flat, reduce=reduce,
-                                       want_start=False)["grad"]
+      node_call = self.engine.exgd_grad_node_shoot if self.transcription == "SHOOTING" else self.engine.exgd_grad_node
+      out = node_call(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
+                      ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, seed, flat, reduce=reduce, want_start=False)["grad"]
       if reduce or single:
         return mapping_from_flat(out if reduce else out[0])
       return [mapping_from_flat(row) for row in out]
