@@ -17,7 +17,8 @@
 //
 // ExgdGradPoint holds the point / interval algebra as functions of values (host and device; combine / grad_point restate CollocProducts' device-only
 // combine / vjp_point, so that both phases of kernel and twin run one text); colloc_exgd_grad_kernel runs it with one
-// wavefront per instance, exgd_grad_host is the same sequence as plain loops (tests/hostsim/exgd_grad_twin.cpp).
+// wavefront per instance, colloc_exgd_grad_host<ExgdGradClosedPoint> (= exgd_grad_host) is the same sequence as plain loops
+// (tests/hostsim/exgd_grad_twin.cpp).
 #pragma once
 #include "systems_gen.h"
 #include "systems_dp_gen.h"
@@ -178,13 +179,41 @@ struct ExgdGradPoint {
   }
 };
 
-// One instance on the host, the sequence of colloc_exgd_grad_kernel as plain loops.  p: the instance's parameter buffer (SysParams::get());
-// hist: hist_doubles(N, nsteps) doubles; work: 3 n + 2 m + K NS doubles; seed_lam, dz0, dlam0 may be null; gp[NP].
-template <class Sys, int SCHEME>
-inline void exgd_grad_host(int N, double h, const double* z, const double* lam, const double* lb, const double* ub, const double* p,
-                           double eta_x, double eta_v, int nsteps, const double* seed_z, const double* seed_lam, double* hist, double* work,
-                           double* gp, double* dz0, double* dlam0) {
+// The point policy of the closed-form systems for colloc_exgd_grad_host: ExgdGradPoint's functions at w = [x; u], gp[k] += ... from the point's gs
+template <class Sys_, int SCHEME>
+struct ExgdGradClosedPoint {
+  using Sys = Sys_;
   using G = ExgdGradPoint<Sys, SCHEME>;
+  static constexpr int NS = G::NS, NP = G::NP;
+  // grad_z L at the point (the forward steps)
+  static inline void grad(const double* w, const double* p, const double* a, const double* e, double wq, bool last, double t, double* g) {
+    G::grad_point(w, w + NS, p, a, e, wq, last, t, g, g + NS);
+  }
+  // item 1 from (a, e) = combine(a_lam): jt, the point's share of gp, and a_x+ of entry r
+  static inline void constraint(const double* w, const double* p, const double* a, const double* e, double t, double eta_v, double* jt, double* gp) {
+    double gs[NP];
+    G::back_constraint(w, w + NS, p, a, e, t, jt, gs);
+    for (int k = 0; k < NP; ++k) gp[k] += eta_v * gs[k];
+  }
+  static inline double step_ax(double ax, int r, double eta_v, const double* e, const double* jt) { (void)e; return ax + eta_v * jt[r]; }
+  // items 3 and 5: hd = H d at the point, wo = A d_x + B d_u, the point's share of gp
+  static inline void hess(const double* w, const double* p, const double* mu, double wq, bool last, double t, const double* d, double* hd, double* wo,
+                          double* gp) {
+    double gs[NP];
+    G::back_grad(w, w + NS, p, mu, wq, last, t, d, hd, wo, gs);
+    for (int k = 0; k < NP; ++k) gp[k] += gs[k];
+  }
+};
+
+// One instance on the host, the sequence of colloc_exgd_grad_kernel (and of node_exgd_grad_kernel) as plain loops: the forward steps, items 1-5,
+// the buffer swap and the history, once for both; every floating-point expression of a point is the policy's (ExgdGradClosedPoint above,
+// NodeExgdPoint in node_exgd_grad.h).  p: the instance's parameter buffer (SysParams::get(); the shared weights); hist: hist_doubles(N, nsteps)
+// doubles; work: 3 n + 2 m + K NS doubles; seed_lam, dz0, dlam0 may be null; gp[NP].
+template <class Point>
+inline void colloc_exgd_grad_host(int N, double h, const double* z, const double* lam, const double* lb, const double* ub, const double* p,
+                                  double eta_x, double eta_v, int nsteps, const double* seed_z, const double* seed_lam, double* hist, double* work,
+                                  double* gp, double* dz0, double* dlam0) {
+  using G = typename Point::G;
   constexpr int NS = G::NS, NU = G::NU, NW = G::NW, NP = G::NP;
   const int K = G::points(N), n = K * NW, m = G::rows(N);
   const long hs = 2L * n + m;
@@ -194,11 +223,8 @@ inline void exgd_grad_host(int N, double h, const double* z, const double* lam, 
   double* sl = sd + n;
   double* sal = sl + m;
   double* sdf = sal + m;
-  auto load_point = [&](const double* src, int j, double* x, double* u) {
-    for (int q = 0; q < NS; ++q) x[q] = src[j * NS + q];
-    for (int c = 0; c < NU; ++c) u[c] = src[K * NS + j * NU + c];
-  };
   auto idx = [&](int j, int r) { return r < NS ? j * NS + r : K * NS + j * NU + (r - NS); };
+  auto load_point = [&](const double* src, int j, double* w) { for (int r = 0; r < NW; ++r) w[r] = src[idx(j, r)]; };
   // forward: sx = z, sax = x_bar, sl = lam, sdf = f
   for (int i = 0; i < n; ++i) sx[i] = z[i];
   for (int i = 0; i < m; ++i) sl[i] = lam[i];
@@ -210,18 +236,18 @@ inline void exgd_grad_host(int N, double h, const double* z, const double* lam, 
       const double* src = pass == 0 ? sx : sax;
       double* dst = pass == 0 ? sax : sx;
       for (int j = 0; j < K; ++j) {
-        double x[NS], u[NU], a[NS], e[NS], g[NW];
-        load_point(src, j, x, u);
+        double w[NW], a[NS], e[NS], g[NW];
+        load_point(src, j, w);
         G::combine(sl, N, j, h, a, e);
-        G::grad_point(x, u, p, a, e, G::wq(K, j, h), j == K - 1, G::time_of(j, h), g, g + NS);
+        Point::grad(w, p, a, e, G::wq(K, j, h), j == K - 1, G::time_of(j, h), g);
         for (int r = 0; r < NW; ++r) { const int i = idx(j, r); dst[i] = G::clip(sx[i] - eta_x * g[r], lb[i], ub[i]); }
       }
       if (pass == 0) for (int i = 0; i < n; ++i) H[n + i] = sax[i];
     }
     for (int j = 0; j < K; ++j) {
-      double x[NS], u[NU], f[NS];
-      load_point(sx, j, x, u);
-      Sys::f(x, u, p, f);
+      double w[NW], f[NS];
+      load_point(sx, j, w);
+      Point::Sys::f(w, w + NS, p, f);
       for (int q = 0; q < NS; ++q) sdf[j * NS + q] = f[q];
     }
     for (int k = 0; k < N; ++k)
@@ -237,66 +263,61 @@ inline void exgd_grad_host(int N, double h, const double* z, const double* lam, 
   for (int i = 0; i < n; ++i) sax[i] = seed_z[i];
   for (int i = 0; i < m; ++i) sal[i] = seed_lam ? seed_lam[i] : 0.0;
   for (int k = 0; k < NP; ++k) gp[k] = 0.0;
-  auto add_jd = [&]() {
-    for (int k = 0; k < N; ++k)
-      for (int q = 0; q < NS; ++q) {
-        double r0, r1;
-        G::jd_rows(sd, sdf, k, q, h, r0, r1);
-        sal[k * NS + q] += r0;
-        if (G::HS) sal[N * NS + k * NS + q] += r1;
-      }
-  };
   for (int s = nsteps - 1; s >= 0; --s) {
     const double* H = hist + s * hs;
     for (int i = 0; i < m; ++i) sl[i] = H[2 * n + i];
     for (int j = 0; j < K; ++j) {                                // items 1, 2 (sx = x+)
-      double x[NS], u[NU], a[NS], e[NS], jt[NW], gs[NP];
-      load_point(sx, j, x, u);
+      double w[NW], a[NS], e[NS], jt[NW];
+      load_point(sx, j, w);
       G::combine(sal, N, j, h, a, e);
-      G::back_constraint(x, u, p, a, e, G::time_of(j, h), jt, gs);
-      for (int k = 0; k < NP; ++k) gp[k] += eta_v * gs[k];
+      Point::constraint(w, p, a, e, G::time_of(j, h), eta_v, jt, gp);
       for (int r = 0; r < NW; ++r) {
         const int i = idx(j, r);
-        const double ax = sax[i] + eta_v * jt[r];
+        const double ax = Point::step_ax(sax[i], r, eta_v, e, jt);
         const double m2 = G::inside(sx[i], lb[i], ub[i]) ? ax : 0.0;
         sax[i] = m2;
         sd[i] = -eta_x * m2;
       }
     }
     for (int i = 0; i < n; ++i) sx[i] = H[n + i];
-    for (int j = 0; j < K; ++j) {                                // items 3, 4 (sx = x_bar; the new direction replaces x_bar)
-      double x[NS], u[NU], mu[NS], e[NS], d[NW], hd[NW], w[NS], gs[NP];
-      load_point(sx, j, x, u);
-      load_point(sd, j, d, d + NS);
-      G::combine(sl, N, j, h, mu, e);
-      G::back_grad(x, u, p, mu, G::wq(K, j, h), j == K - 1, G::time_of(j, h), d, hd, w, gs);
-      for (int k = 0; k < NP; ++k) gp[k] += gs[k];
-      for (int q = 0; q < NS; ++q) sdf[j * NS + q] = w[q];
-      for (int r = 0; r < NW; ++r) {
-        const int i = idx(j, r);
-        const double m1 = G::inside(sx[i], lb[i], ub[i]) ? hd[r] : 0.0;
-        sax[i] += m1;
-        sx[i] = -eta_x * m1;
+    for (int item = 3; item <= 5; item += 2) {                   // items 3, 4 (sx = x_bar, whose place the new direction takes), then 5 (sx = x)
+      for (int j = 0; j < K; ++j) {
+        double w[NW], mu[NS], e[NS], d[NW], hd[NW], wo[NS];
+        load_point(sx, j, w);
+        load_point(sd, j, d);
+        G::combine(sl, N, j, h, mu, e);
+        Point::hess(w, p, mu, G::wq(K, j, h), j == K - 1, G::time_of(j, h), d, hd, wo, gp);
+        for (int q = 0; q < NS; ++q) sdf[j * NS + q] = wo[q];
+        for (int r = 0; r < NW; ++r) {
+          const int i = idx(j, r);
+          if (item == 3) {
+            const double m1 = G::inside(sx[i], lb[i], ub[i]) ? hd[r] : 0.0;
+            sax[i] += m1;
+            sx[i] = -eta_x * m1;
+          } else {
+            sax[i] += hd[r];
+          }
+        }
+      }
+      for (int k = 0; k < N; ++k)
+        for (int q = 0; q < NS; ++q) {
+          double r0, r1;
+          G::jd_rows(sd, sdf, k, q, h, r0, r1);
+          sal[k * NS + q] += r0;
+          if (G::HS) sal[N * NS + k * NS + q] += r1;
+        }
+      if (item == 3) {
+        double* t = sd; sd = sx; sx = t;
+        for (int i = 0; i < n; ++i) sx[i] = H[i];
       }
     }
-    add_jd();
-    { double* t = sd; sd = sx; sx = t; }
-    for (int i = 0; i < n; ++i) sx[i] = H[i];
-    for (int j = 0; j < K; ++j) {                                // item 5 (sx = x)
-      double x[NS], u[NU], mu[NS], e[NS], d[NW], hd[NW], w[NS], gs[NP];
-      load_point(sx, j, x, u);
-      load_point(sd, j, d, d + NS);
-      G::combine(sl, N, j, h, mu, e);
-      G::back_grad(x, u, p, mu, G::wq(K, j, h), j == K - 1, G::time_of(j, h), d, hd, w, gs);
-      for (int k = 0; k < NP; ++k) gp[k] += gs[k];
-      for (int q = 0; q < NS; ++q) sdf[j * NS + q] = w[q];
-      for (int r = 0; r < NW; ++r) sax[idx(j, r)] += hd[r];
-    }
-    add_jd();
   }
   if (dz0) for (int i = 0; i < n; ++i) dz0[i] = sax[i];
   if (dlam0) for (int i = 0; i < m; ++i) dlam0[i] = sal[i];
 }
+
+template <class Sys, int SCHEME, class... A>
+inline void exgd_grad_host(A... a) { colloc_exgd_grad_host<ExgdGradClosedPoint<Sys, SCHEME>>(a...); }
 
 #if defined(__HIPCC__)
 // One wavefront per instance (blockIdx.x: the instance within this launch's chunk; every pointer is the chunk's).  Dynamic LDS:

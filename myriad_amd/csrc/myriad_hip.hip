@@ -330,13 +330,10 @@ struct FitArgs {      // xh: [num_steps+1][NS][Bp] state scratch; loss [B] or nu
 struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of one chunk of `chunk` instances; seed_lam, dz0, dlam0 may be null
   int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
   double *rows, *dz0, *dlam0, *hist; int chunk;
+  double* work; long Pp;      // SHOOTING (closed form) only: the scratch of one chunk (launch_shoot_exgd_grad carves it) and its pair columns
 };
 struct HvpArgs {      // lam, out_z, rows ([B][NP] parameter rows) may be null; hist, side: shooting scratch, batch-minor with Pp columns (one per pair)
   int B; const double *z, *lam, *v, *params; int pstride, with_cost; double *out_z, *rows, *hist, *side; long Pp;
-};
-struct ShootExgdGradArgs {      // as ExgdGradArgs; hist, work: the scratch of one chunk of `chunk` instances (launch_shoot_exgd_grad carves work); Pp: its pair columns
-  int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
-  double *rows, *dz0, *dlam0, *hist, *work; int chunk; long Pp;
 };
 struct FbsmArgs {      // X, A [N+1][NS][Bp], U [N+1 | N][NU][Bp]: batch-minor
   int B; long Bp; int N; const double *x0, *adjT, *params; int pstride; VarScale lo, hi; double bang, delta; int max_sweeps;
@@ -1157,24 +1154,36 @@ int fit_for_system(myr_handle h, const FitArgs& a) {
 // ------------------------------------------------------------------------------------------------
 // derivative of the unrolled extragradient steps in the model parameters (exgd_grad.h: colloc_exgd_grad_kernel)
 // ------------------------------------------------------------------------------------------------
+// The batch in chunks of a.chunk instances that share one history buffer (launches on one stream: a chunk starts when the one before has ended).
+// `launch` gets the chunk's record: B its instances, every batch pointer at its first one (null stays null; params advances by pstride)
+template <class F>
+static int for_exgd_grad_chunks(myr_handle h, const ExgdGradArgs& a, F launch) {
+  const myr_dims& dm = h->dims;
+  for (long b0 = 0; b0 < a.B; b0 += a.chunk) {
+    auto at = [b0](auto* p, long stride) { return p ? p + b0 * stride : nullptr; };
+    ExgdGradArgs c = a;
+    c.B = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
+    c.z = at(a.z, dm.n); c.lam = at(a.lam, dm.m); c.lb = at(a.lb, dm.n); c.ub = at(a.ub, dm.n); c.params = at(a.params, a.pstride);
+    c.seed_z = at(a.seed_z, dm.n); c.seed_lam = at(a.seed_lam, dm.m);
+    c.rows = at(a.rows, dm.np); c.dz0 = at(a.dz0, dm.n); c.dlam0 = at(a.dlam0, dm.m);
+    if (int rc = launch(c)) return rc;
+  }
+  return MYR_OK;
+}
+
 template <class Sys, int SCHEME>
 static int launch_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
   const int N = h->d.intervals;
-  const myr_dims& dm = h->dims;
   const size_t lds = colloc_exgd_grad_lds_bytes<Sys, SCHEME>(N);
   if (lds > 160 * 1024) return fail(MYR_E_CAPACITY, "myr_exgd_grad: intervals too large for the LDS-resident reverse sweep");
   auto kern = colloc_exgd_grad_kernel<Sys, SCHEME>;
   // (the limit is a property of the FUNCTION, shared by every handle of the process: the hardware's 160 KB, not this handle's size -- kernel_blocks_per_cu)
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  // the batch in chunks of instances that share one history buffer (launches on one stream: a chunk starts when the one before has ended)
-  for (long b0 = 0; b0 < a.B; b0 += a.chunk) {
-    const int nb = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64), lds, h->stream, nb, N, h->d.T / N, a.z + b0 * dm.n, a.lam + b0 * dm.m, a.lb + b0 * dm.n,
-                       a.ub + b0 * dm.n, a.params ? a.params + b0 * a.pstride : nullptr, a.pstride, a.eta_x, a.eta_v, a.nsteps, a.seed_z + b0 * dm.n,
-                       a.seed_lam ? a.seed_lam + b0 * dm.m : nullptr, a.hist, a.rows + b0 * dm.np, a.dz0 ? a.dz0 + b0 * dm.n : nullptr,
-                       a.dlam0 ? a.dlam0 + b0 * dm.m : nullptr);
-  }
-  return MYR_OK;
+  return for_exgd_grad_chunks(h, a, [&](const ExgdGradArgs& c) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)c.B), dim3(64), lds, h->stream, c.B, N, h->d.T / N, c.z, c.lam, c.lb, c.ub, c.params, c.pstride, c.eta_x,
+                       c.eta_v, c.nsteps, c.seed_z, c.seed_lam, c.hist, c.rows, c.dz0, c.dlam0);
+    return (int)MYR_OK;
+  });
 }
 
 template <class Sys>
@@ -1191,17 +1200,14 @@ int exgd_grad_for_system(myr_handle h, const ExgdGradArgs& a) {
 template <int WPI>
 static int launch_node_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
   const int N = h->d.intervals;
-  const myr_dims& dm = h->dims;
   const size_t lds = node_exgd_grad_lds_bytes(N);
   auto kern = node_exgd_grad_kernel<WPI>;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  for (long b0 = 0; b0 < a.B; b0 += a.chunk) {      // (chunks that share one history buffer, as launch_exgd_grad)
-    const int nb = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64 * WPI), lds, h->stream, nb, N, h->d.T / N, a.z + b0 * dm.n, a.lam + b0 * dm.m, a.lb + b0 * dm.n,
-                       a.ub + b0 * dm.n, a.params, a.eta_x, a.eta_v, a.nsteps, a.seed_z + b0 * dm.n, a.seed_lam ? a.seed_lam + b0 * dm.m : nullptr, a.hist,
-                       a.rows + b0 * dm.np, a.dz0 ? a.dz0 + b0 * dm.n : nullptr, a.dlam0 ? a.dlam0 + b0 * dm.m : nullptr);
-  }
-  return MYR_OK;
+  return for_exgd_grad_chunks(h, a, [&](const ExgdGradArgs& c) {      // (params: the one shared weight set, pstride 0)
+    hipLaunchKernelGGL(kern, dim3((unsigned)c.B), dim3(64 * WPI), lds, h->stream, c.B, N, h->d.T / N, c.z, c.lam, c.lb, c.ub, c.params, c.eta_x, c.eta_v,
+                       c.nsteps, c.seed_z, c.seed_lam, c.hist, c.rows, c.dz0, c.dlam0);
+    return (int)MYR_OK;
+  });
 }
 
 template <class Sys>
@@ -1257,8 +1263,9 @@ int hvp_shoot_for_system(myr_handle h, const HvpArgs& a) {
 // derivative of the unrolled extragradient steps under SHOOTING (shoot_exgd_grad.h: the seeded pair pass and the mask pass behind it)
 // ------------------------------------------------------------------------------------------------
 template <class Sys, int M>
-static int launch_shoot_exgd_grad(myr_handle h, const ShootExgdGradArgs& a) {
+static int launch_shoot_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
   using HV = ShootHvp<Sys, M>;
+  using G = ShootExgdGrad<Sys, M>;
   const int I = h->d.intervals, cpi = h->d.controls_per_interval, method = h->d.integration_method;
   const long n = h->dims.n, m = h->dims.m, np = h->dims.np, C = a.chunk, Pp = a.Pp;
   // the chunk's scratch: the iterate of the forward steps and what they need, a_x, the direction, and a column per pair of a_lam, history and side record
@@ -1266,37 +1273,31 @@ static int launch_shoot_exgd_grad(myr_handle h, const ShootExgdGradArgs& a) {
   double* cbuf = zbar + C * n;     double* scr = cbuf + C * m;      double* ax = scr + C * (long)(cpi + 1) * Sys::NS;
   double* dir = ax + C * n;        double* al = dir + C * n;        double* phist = al + Pp * Sys::NS;
   double* side = phist + Pp * HV::hist_doubles(cpi);
-  for (long b0 = 0; b0 < a.B; b0 += C) {      // chunks that share one history buffer, as launch_exgd_grad
-    const int nb = (int)(a.B - b0 < C ? a.B - b0 : C);
+  return for_exgd_grad_chunks(h, a, [&](const ExgdGradArgs& c) {
+    const int nb = c.B;
     const long P = (long)nb * I, tz = (long)nb * n, tl = (long)nb * m, hs = 2 * tz + tl;
-    const double* lb = a.lb + b0 * n; const double* ub = a.ub + b0 * n;
-    const double* params = a.params ? a.params + b0 * a.pstride : nullptr;
-    double* rows = a.rows + b0 * np;
-    if (int rc = copy_doubles(h, zio, a.z + b0 * n, tz)) return rc;
-    if (int rc = copy_doubles(h, lamio, a.lam + b0 * m, tl)) return rc;
-    if (int rc = shoot_exgd_steps<Sys, M>(h, nb, zio, lamio, lb, ub, params, a.pstride, a.eta_x, a.eta_v, a.nsteps, scr, g, zbar, cbuf, a.hist)) return rc;
-    if (int rc = copy_doubles(h, ax, a.seed_z + b0 * n, tz)) return rc;
+    if (int rc = copy_doubles(h, zio, c.z, tz)) return rc;
+    if (int rc = copy_doubles(h, lamio, c.lam, tl)) return rc;
+    if (int rc = shoot_exgd_steps<Sys, M>(h, nb, zio, lamio, c.lb, c.ub, c.params, c.pstride, c.eta_x, c.eta_v, c.nsteps, scr, g, zbar, cbuf, c.hist)) return rc;
+    if (int rc = copy_doubles(h, ax, c.seed_z, tz)) return rc;
     hipLaunchKernelGGL(shoot_exgd_grad_lam_kernel, dim3(grid_for(Pp * Sys::NS + tz + nb * np)), dim3(256), 0, h->stream, 1, nb, Pp, I, (int)Sys::NS, n, (int)np,
-                       a.seed_lam ? a.seed_lam + b0 * m : nullptr, al, dir, rows, (double*)nullptr);
-    auto pass = [&](const double* pt, const double* lam, double scale, int mode) {
+                       c.seed_lam, al, dir, c.rows, (double*)nullptr);
+    for (int ps = 0; ps < G::passes(c.nsteps); ++ps) {      // (the pass at x_n runs on the direction the kernel above has cleared)
+      const typename G::Pass q = G::pass_of(ps, c.nsteps, c.eta_v);
+      const double* H = c.hist + q.s * hs;
+      const double* pt = q.at_bar ? H + tz : H;
       hipLaunchKernelGGL((shoot_exgd_grad_pair_kernel<Sys, M>), dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, nb, Pp, I, cpi, method, h->d.T, pt,
-                         lam, (const double*)dir, params, a.pstride, scale, al, phist, side);
-      hipLaunchKernelGGL((shoot_exgd_grad_mask_kernel<Sys, M>), dim3(grid_for(tz + nb * np)), dim3(256), 0, h->stream, nb, Pp, I, cpi, mode, scale, a.eta_x,
-                         (const double*)side, (const double*)al, pt, lb, ub, ax, dir, rows);
-    };
-    if (a.nsteps > 0) pass(a.hist + a.nsteps * hs, nullptr, a.eta_v, SHOOT_MASK_STEP);      // at x_n, on the zero direction
-    for (int s = a.nsteps - 1; s >= 0; --s) {
-      const double* H = a.hist + s * hs;
-      pass(H + tz, H + 2 * tz, 0.0, SHOOT_MASK_BAR);
-      pass(H, H + 2 * tz, s > 0 ? a.eta_v : 0.0, s > 0 ? SHOOT_MASK_STEP : SHOOT_MASK_LAST);
+                         q.alone ? (const double*)nullptr : H + 2 * tz, (const double*)dir, c.params, c.pstride, q.scale, al, phist, side);
+      hipLaunchKernelGGL((shoot_exgd_grad_mask_kernel<Sys, M>), dim3(grid_for(tz + nb * np)), dim3(256), 0, h->stream, nb, Pp, I, cpi, q.mode, q.scale,
+                         c.eta_x, (const double*)side, (const double*)al, pt, c.lb, c.ub, ax, dir, c.rows);
     }
-    if (a.dz0)
-      if (int rc = copy_doubles(h, a.dz0 + b0 * n, ax, tz)) return rc;
-    if (a.dlam0)
+    if (c.dz0)
+      if (int rc = copy_doubles(h, c.dz0, ax, tz)) return rc;
+    if (c.dlam0)
       hipLaunchKernelGGL(shoot_exgd_grad_lam_kernel, dim3(grid_for(P * Sys::NS)), dim3(256), 0, h->stream, 0, nb, Pp, I, (int)Sys::NS, n, (int)np,
-                         (const double*)nullptr, al, (double*)nullptr, (double*)nullptr, a.dlam0 + b0 * m);
-  }
-  return MYR_OK;
+                         (const double*)nullptr, al, (double*)nullptr, (double*)nullptr, c.dlam0);
+    return (int)MYR_OK;
+  });
 }
 
 // doubles of `work` for a chunk of C instances with Pp pair columns (the carve of launch_shoot_exgd_grad)
@@ -1308,7 +1309,7 @@ static size_t shoot_exgd_grad_work_doubles(myr_handle h, size_t C, size_t Pp) {
 
 // myr_exgd_grad_shoot has refused the twins, the network system and the collocation transcriptions, each with its own message
 template <class Sys>
-int exgd_grad_shoot_for_system(myr_handle h, const ShootExgdGradArgs& a) {
+int exgd_grad_shoot_for_system(myr_handle h, const ExgdGradArgs& a) {
   if constexpr (SysDpw<Sys>::SUPPORTED)
     return h->d.integration_method == MYR_INT_RK4 ? launch_shoot_exgd_grad<Sys, 2>(h, a) : launch_shoot_exgd_grad<Sys, 1>(h, a);
   return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: not built for this system");
@@ -1321,23 +1322,19 @@ int exgd_grad_shoot_for_system(myr_handle h, const ShootExgdGradArgs& a) {
 template <int M>
 static int launch_node_shoot_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
   const int I = h->d.intervals, cpi = h->d.controls_per_interval;
-  const myr_dims& dm = h->dims;
   const size_t lds = node_shoot_exgd_grad_lds_bytes<M>(I, cpi);
   const int wpi = node_shoot_exgd_grad_wpi(I);
   auto kern = node_shoot_exgd_grad_kernel<M>;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  for (long b0 = 0; b0 < a.B; b0 += a.chunk) {      // (chunks that share one history buffer, as launch_node_exgd_grad)
+  return for_exgd_grad_chunks(h, a, [&](const ExgdGradArgs& c) {
     NseArgs k{};
-    k.B = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
-    k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.nsteps = a.nsteps;
-    k.T = h->d.T; k.eta_x = a.eta_x; k.eta_v = a.eta_v;
-    k.z = a.z + b0 * dm.n; k.lam = a.lam + b0 * dm.m; k.lb = a.lb + b0 * dm.n; k.ub = a.ub + b0 * dm.n; k.params = a.params;
-    k.seed_z = a.seed_z + b0 * dm.n; k.seed_lam = a.seed_lam ? a.seed_lam + b0 * dm.m : nullptr;
-    k.hist = a.hist; k.grad = a.rows + b0 * dm.np;
-    k.dz0 = a.dz0 ? a.dz0 + b0 * dm.n : nullptr; k.dlam0 = a.dlam0 ? a.dlam0 + b0 * dm.m : nullptr;
+    k.B = c.B; k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.nsteps = c.nsteps;
+    k.T = h->d.T; k.eta_x = c.eta_x; k.eta_v = c.eta_v;
+    k.z = c.z; k.lam = c.lam; k.lb = c.lb; k.ub = c.ub; k.params = c.params; k.seed_z = c.seed_z; k.seed_lam = c.seed_lam;
+    k.hist = c.hist; k.grad = c.rows; k.dz0 = c.dz0; k.dlam0 = c.dlam0;
     hipLaunchKernelGGL(kern, dim3((unsigned)k.B), dim3(64 * wpi), lds, h->stream, k);
-  }
-  return MYR_OK;
+    return (int)MYR_OK;
+  });
 }
 
 template <class Sys>
@@ -1358,7 +1355,7 @@ int exgd_grad_node_shoot_for_system(myr_handle h, const ExgdGradArgs& a) {
   LINK template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
   LINK template int hvp_shoot_for_system<S>(myr_handle, const HvpArgs&);      \
-  LINK template int exgd_grad_shoot_for_system<S>(myr_handle, const ShootExgdGradArgs&); \
+  LINK template int exgd_grad_shoot_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int exgd_grad_node_shoot_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
@@ -1372,7 +1369,7 @@ template int solve_trap_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const Solv
 #elif MYR_TU_PART == 4
 template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 template int hvp_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const HvpArgs&);
-template int exgd_grad_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ShootExgdGradArgs&);
+template int exgd_grad_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ExgdGradArgs&);
 template int exgd_grad_node_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ExgdGradArgs&);
 #elif MYR_TU_PART == 5
 template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, const SolveCall&);
@@ -2342,24 +2339,63 @@ static int exgd_grad_chunk(myr_handle h, int B, int nsteps, size_t* per) {
   return (int)(chunk < 1 ? 1 : (chunk > (size_t)B ? (size_t)B : chunk));
 }
 
-// device pointers throughout (a.hist, a.chunk and, for the batch sum, a.rows are set here); grad: [B][np] rows (grad_stride == np) or their sum
-enum { EXGD_GRAD_CLOSED_FORM = 0, EXGD_GRAD_NODE = 1, EXGD_GRAD_NODE_SHOOT = 2 };      // which kernel family runs the sweep
-static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, int route = EXGD_GRAD_CLOSED_FORM) {
+// device pointers throughout (a.hist, a.chunk, under EXGD_GRAD_SHOOT a.work and a.Pp and, for the batch sum, a.rows are set here); grad: [B][np] rows
+// (grad_stride == np) or their sum
+enum { EXGD_GRAD_CLOSED_FORM = 0, EXGD_GRAD_NODE = 1, EXGD_GRAD_NODE_SHOOT = 2, EXGD_GRAD_SHOOT = 3 };      // which kernel family runs the sweep
+static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, int route) {
   const myr_dims& dm = h->dims;
+  const long I = h->d.intervals;
+  if (route == EXGD_GRAD_SHOOT && (long)a.B * I > (1L << 30))
+    return fail(MYR_E_CAPACITY, "myr_exgd_grad_shoot: more than 2^30 (instance, interval) pairs in one call");
   size_t per;
   a.chunk = exgd_grad_chunk(h, a.B, a.nsteps, &per);
   DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
   st.scratch(a.hist, (size_t)a.chunk * per);
+  if (route == EXGD_GRAD_SHOOT) {      // a column per pair of the chunk
+    a.Pp = ((long)a.chunk * I + 63) / 64 * 64;
+    if (((a.Pp / 64) & 1) == 0) a.Pp += 64;      // an odd number of wavefronts, as padded_lanes
+    st.scratch(a.work, shoot_exgd_grad_work_doubles(h, (size_t)a.chunk, (size_t)a.Pp));
+  }
   if (grad_stride) a.rows = grad;
   else st.scratch(a.rows, (size_t)a.B * dm.np);
   if (int rc = st.commit()) return rc;
   if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
   const int rc = route == EXGD_GRAD_NODE_SHOOT ? exgd_grad_node_shoot_for_system<SysNODE_CARTPOLE>(h, a)
                  : route == EXGD_GRAD_NODE ? exgd_grad_node_for_system<SysNODE_CARTPOLE>(h, a)
-                 : for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+                 : route == EXGD_GRAD_SHOOT
+                     ? for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_shoot_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; })
+                     : for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
   if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, grad);
   const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
   return rc ? rc : rc_end;
+}
+
+// what the four myr_exgd_grad* entry points share behind their own checks: the staging, the sweep of `route`, the copies back.
+// n_param_doubles: what `params` holds (a row per instance, or one shared set)
+static int run_exgd_grad(myr_handle h, int route, int mem, int B, const double* z, const double* lam, const double* lb, const double* ub,
+                         const double* params, size_t n_param_doubles, int pstride, double eta_x, double eta_v, int nsteps, const double* seed_z,
+                         const double* seed_lam, double* grad, int grad_stride, double* dz0, double* dlam0) {
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
+  ExgdGradArgs a{};
+  a.B = B; a.pstride = pstride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
+  double* g = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lb, lb, nz);
+  st.in(a.ub, ub, nz);
+  st.in(a.lam, lam, nl);
+  st.in(a.params, params, n_param_doubles);
+  st.in(a.seed_z, seed_z, nz);
+  st.in(a.seed_lam, seed_lam, nl);
+  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  st.out(a.dz0, dz0, nz);
+  st.out(a.dlam0, dlam0, nl);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, route)) return rc;
+  return st.finish();
 }
 
 extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub, const double* params,
@@ -2378,27 +2414,8 @@ extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const dou
   if (h->d.transcription == MYR_TR_SHOOTING)
     return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: SHOOTING is not built (it needs the second-order adjoint of the rollout); use a collocation transcription");
   if (int rc = check_mem(who, mem)) return rc;
-  if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
-  ExgdGradArgs a{};
-  a.B = B; a.pstride = params_stride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
-  double* g = nullptr;
-  DevStage st = call_stage(h, mem);
-  st.in(a.z, z, nz);
-  st.in(a.lb, lb, nz);
-  st.in(a.ub, ub, nz);
-  st.in(a.lam, lam, nl);
-  st.in(a.params, params, n_params(h, params, params_stride, B));
-  st.in(a.seed_z, seed_z, nz);
-  st.in(a.seed_lam, seed_lam, nl);
-  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
-  st.out(a.dz0, dz0, nz);
-  st.out(a.dlam0, dlam0, nl);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride)) return rc;
-  return st.finish();
+  return run_exgd_grad(h, EXGD_GRAD_CLOSED_FORM, mem, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps,
+                       seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
 }
 
 // the same call for the weights of the network system: one shared weight set (no params_stride), Hermite-Simpson
@@ -2421,27 +2438,8 @@ extern "C" int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, cons
   if (int rc = check_mem(who, mem)) return rc;
   if (node_exgd_grad_lds_bytes(h->d.intervals) > 160 * 1024)
     return fail(MYR_E_CAPACITY, "myr_exgd_grad_node: intervals too large for the LDS-resident reverse sweep beside the weight copy");
-  if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
-  ExgdGradArgs a{};
-  a.B = B; a.pstride = 0; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
-  double* g = nullptr;
-  DevStage st = call_stage(h, mem);
-  st.in(a.z, z, nz);
-  st.in(a.lb, lb, nz);
-  st.in(a.ub, ub, nz);
-  st.in(a.lam, lam, nl);
-  st.in(a.params, params, (size_t)dm.np);
-  st.in(a.seed_z, seed_z, nz);
-  st.in(a.seed_lam, seed_lam, nl);
-  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
-  st.out(a.dz0, dz0, nz);
-  st.out(a.dlam0, dlam0, nl);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, EXGD_GRAD_NODE)) return rc;
-  return st.finish();
+  return run_exgd_grad(h, EXGD_GRAD_NODE, mem, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
+                       dz0, dlam0);
 }
 
 // ... and under SHOOTING (node_shoot_exgd_grad.h): the arguments, null rules and outputs of myr_exgd_grad_node
@@ -2470,52 +2468,11 @@ extern "C" int myr_exgd_grad_node_shoot(myr_handle h, int32_t B, const double* z
     if (lds > 160 * 1024)
       return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_shoot: intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy");
   }
-  if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
-  ExgdGradArgs a{};
-  a.B = B; a.pstride = 0; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
-  double* g = nullptr;
-  DevStage st = call_stage(h, mem);
-  st.in(a.z, z, nz);
-  st.in(a.lb, lb, nz);
-  st.in(a.ub, ub, nz);
-  st.in(a.lam, lam, nl);
-  st.in(a.params, params, (size_t)dm.np);
-  st.in(a.seed_z, seed_z, nz);
-  st.in(a.seed_lam, seed_lam, nl);
-  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
-  st.out(a.dz0, dz0, nz);
-  st.out(a.dlam0, dlam0, nl);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, EXGD_GRAD_NODE_SHOOT)) return rc;
-  return st.finish();
+  return run_exgd_grad(h, EXGD_GRAD_NODE_SHOOT, mem, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad,
+                       grad_stride, dz0, dlam0);
 }
 
-// the same derivative under SHOOTING (shoot_exgd_grad.h).  Device pointers throughout (a.hist, a.work, a.chunk, a.Pp and, for the batch sum, a.rows are set here)
-static int dispatch_exgd_grad_shoot(myr_handle h, ShootExgdGradArgs a, double* grad, int grad_stride) {
-  const myr_dims& dm = h->dims;
-  const long I = h->d.intervals;
-  if ((long)a.B * I > (1L << 30)) return fail(MYR_E_CAPACITY, "myr_exgd_grad_shoot: more than 2^30 (instance, interval) pairs in one call");
-  size_t per;
-  a.chunk = exgd_grad_chunk(h, a.B, a.nsteps, &per);
-  const long P = (long)a.chunk * I;
-  a.Pp = (P + 63) / 64 * 64;
-  if (((a.Pp / 64) & 1) == 0) a.Pp += 64;      // an odd number of wavefronts, as padded_lanes
-  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
-  st.scratch(a.hist, (size_t)a.chunk * per);
-  st.scratch(a.work, shoot_exgd_grad_work_doubles(h, (size_t)a.chunk, (size_t)a.Pp));
-  if (grad_stride) a.rows = grad;
-  else st.scratch(a.rows, (size_t)a.B * dm.np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
-  const int rc = for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_shoot_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
-  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, grad);
-  const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
-  return rc ? rc : rc_end;
-}
-
+// the same derivative under SHOOTING (shoot_exgd_grad.h)
 extern "C" int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub, const double* params,
                                    int32_t params_stride, double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam,
                                    double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
@@ -2533,27 +2490,8 @@ extern "C" int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, con
   if (h->d.transcription != MYR_TR_SHOOTING)
     return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: this handle's transcription is not SHOOTING; use myr_exgd_grad");
   if (int rc = check_mem(who, mem)) return rc;
-  if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
-  ShootExgdGradArgs a{};
-  a.B = B; a.pstride = params_stride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
-  double* g = nullptr;
-  DevStage st = call_stage(h, mem);
-  st.in(a.z, z, nz);
-  st.in(a.lb, lb, nz);
-  st.in(a.ub, ub, nz);
-  st.in(a.lam, lam, nl);
-  st.in(a.params, params, n_params(h, params, params_stride, B));
-  st.in(a.seed_z, seed_z, nz);
-  st.in(a.seed_lam, seed_lam, nl);
-  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
-  st.out(a.dz0, dz0, nz);
-  st.out(a.dlam0, dlam0, nl);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_exgd_grad_shoot(h, a, g, grad_stride)) return rc;
-  return st.finish();
+  return run_exgd_grad(h, EXGD_GRAD_SHOOT, mem, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps,
+                       seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
 }
 
 // device pointers throughout (a.hist, a.side, a.Pp and, for the batch sum, a.rows are set here); out_p: [B][np] rows (p_stride == np), their sum, or null

@@ -12,7 +12,8 @@
 //        dW1[c][i] += d_c t1_i + w_c c1_i;  db1 += c1;  hd = W1 c1.                         (b3 has no share)
 // The running cost is the TRUE system's: it has no weights, adds wq dg to the gradient of the Lagrangian and wq d2g d to hd.
 //
-// NodeExgdHost: (a)-(c) as plain loops, and node_exgd_grad_host, the sequence of exgd_grad_host with them (tests/hostsim/node_exgd_grad_twin.cpp).
+// NodeExgdHost: (a)-(c) as plain loops; NodeExgdPoint hands them to colloc_exgd_grad_host (exgd_grad.h), the one host sequence of K10 and K12
+// (node_exgd_grad_host, tests/hostsim/node_exgd_grad_twin.cpp).
 // NodeExgdWave: the same on one wavefront, lane j = hidden unit j of both layers, weights from the LDS copy of NodeMfma64::load_weights,
 // activations broadcast by v_readlane (NodeFit::fwd / bcast / wsum, fit.h); the weight gradient in NodeFit::Acc.
 // node_exgd_grad_kernel<WPI>: one workgroup of WPI wavefronts per instance.
@@ -131,119 +132,38 @@ struct NodeExgdHost {
   }
 };
 
-// One instance on the host: exgd_grad_host's sequence with the point functions above.  p: the NP shared weights (node_system.h's order);
-// hist: hist_doubles(N, nsteps) doubles; work: 3 n + 2 m + K NS doubles; seed_lam, dz0, dlam0 may be null; gp[NP].
-inline void node_exgd_grad_host(int N, double h, const double* z, const double* lam, const double* lb, const double* ub, const double* p,
-                                double eta_x, double eta_v, int nsteps, const double* seed_z, const double* seed_lam, double* hist, double* work,
-                                double* gp, double* dz0, double* dlam0) {
+// The point policy of the network system for colloc_exgd_grad_host (exgd_grad.h): the point functions above at w = [x; u], the weight gradient
+// accumulated into gp directly.  p: the NP shared weights (node_system.h's order)
+struct NodeExgdPoint {
   using P = NodeExgdHost;
+  using Sys = P::Sys;
   using G = P::G;
-  constexpr int NS = P::NS, NU = P::NU, NW = P::NW, NP = P::NP;
-  const int K = G::points(N), n = K * NW, m = G::rows(N);
-  const long hs = 2L * n + m;
-  double* sx = work;
-  double* sax = sx + n;
-  double* sd = sax + n;
-  double* sl = sd + n;
-  double* sal = sl + m;
-  double* sdf = sal + m;
-  auto idx = [&](int j, int r) { return r < NS ? j * NS + r : K * NS + j * NU + (r - NS); };
-  auto load_point = [&](const double* src, int j, double* w) { for (int r = 0; r < NW; ++r) w[r] = src[idx(j, r)]; };
-  for (int i = 0; i < n; ++i) sx[i] = z[i];
-  for (int i = 0; i < m; ++i) sl[i] = lam[i];
-  for (int s = 0; s < nsteps; ++s) {
-    double* Hh = hist + s * hs;
-    for (int i = 0; i < n; ++i) Hh[i] = sx[i];
-    for (int i = 0; i < m; ++i) Hh[2 * n + i] = sl[i];
-    for (int pass = 0; pass < 2; ++pass) {
-      const double* src = pass == 0 ? sx : sax;
-      double* dst = pass == 0 ? sax : sx;
-      for (int j = 0; j < K; ++j) {
-        double w[NW], a[NS], e[NS], f[NS], jt[NW], g[NW];
-        load_point(src, j, w);
-        G::combine(sl, N, j, h, a, e);
-        P::first(w, p, a, f, jt, nullptr);
-        P::assemble(w, p, e, jt, G::wq(K, j, h), g);
-        for (int r = 0; r < NW; ++r) { const int i = idx(j, r); dst[i] = G::clip(sx[i] - eta_x * g[r], lb[i], ub[i]); }
-      }
-      if (pass == 0) for (int i = 0; i < n; ++i) Hh[n + i] = sax[i];
-    }
-    for (int j = 0; j < K; ++j) {
-      double w[NW], f[NS];
-      load_point(sx, j, w);
-      P::Sys::f(w, w + NS, p, f);
-      for (int q = 0; q < NS; ++q) sdf[j * NS + q] = f[q];
-    }
-    for (int k = 0; k < N; ++k)
-      for (int q = 0; q < NS; ++q) {
-        double r0, r1;
-        G::jd_rows(sx, sdf, k, q, h, r0, r1);
-        sl[k * NS + q] += eta_v * r0;
-        sl[N * NS + k * NS + q] += eta_v * r1;
-      }
+  static constexpr int NS = P::NS, NW = P::NW;
+  static inline void grad(const double* w, const double* p, const double* a, const double* e, double wq, bool, double, double* g) {
+    double f[NS], jt[NW];
+    P::first(w, p, a, f, jt, nullptr);
+    P::assemble(w, p, e, jt, wq, g);
   }
-  for (int i = 0; i < n; ++i) hist[nsteps * hs + i] = sx[i];
-  for (int i = 0; i < n; ++i) sax[i] = seed_z[i];
-  for (int i = 0; i < m; ++i) sal[i] = seed_lam ? seed_lam[i] : 0.0;
-  for (int k = 0; k < NP; ++k) gp[k] = 0.0;
-  auto add_jd = [&]() {
-    for (int k = 0; k < N; ++k)
-      for (int q = 0; q < NS; ++q) {
-        double r0, r1;
-        G::jd_rows(sd, sdf, k, q, h, r0, r1);
-        sal[k * NS + q] += r0;
-        sal[N * NS + k * NS + q] += r1;
-      }
-  };
-  for (int s = nsteps - 1; s >= 0; --s) {
-    const double* Hh = hist + s * hs;
-    for (int i = 0; i < m; ++i) sl[i] = Hh[2 * n + i];
-    for (int j = 0; j < K; ++j) {                                // items 1, 2 (sx = x+): the cotangent eta_v a(a_lam) on f
-      double w[NW], a[NS], e[NS], v[NS], f[NS], jt[NW];
-      load_point(sx, j, w);
-      G::combine(sal, N, j, h, a, e);
-      for (int q = 0; q < NS; ++q) v[q] = eta_v * a[q];
-      P::first(w, p, v, f, jt, gp);
-      for (int r = 0; r < NW; ++r) {
-        const int i = idx(j, r);
-        const double ax = sax[i] + ((r < NS ? eta_v * e[r] : 0.0) + jt[r]);
-        const double m2 = G::inside(sx[i], lb[i], ub[i]) ? ax : 0.0;
-        sax[i] = m2;
-        sd[i] = -eta_x * m2;
-      }
-    }
-    for (int i = 0; i < n; ++i) sx[i] = Hh[n + i];
-    for (int item = 3; item <= 5; item += 2) {                   // items 3, 4 (sx = x_bar, whose place the new direction takes), then 5 (sx = x)
-      for (int j = 0; j < K; ++j) {
-        double w[NW], mu[NS], e[NS], d[NW], hd[NW], hc[NW], wo[NS];
-        load_point(sx, j, w);
-        load_point(sd, j, d);
-        G::combine(sl, N, j, h, mu, e);
-        P::second(w, p, mu, d, wo, hd, gp);
-        P::cost_hd(w, G::wq(K, j, h), d, hc);
-        for (int q = 0; q < NS; ++q) sdf[j * NS + q] = wo[q];
-        for (int r = 0; r < NW; ++r) {
-          const int i = idx(j, r);
-          const double v = hd[r] + hc[r];
-          if (item == 3) {
-            const double m1 = G::inside(sx[i], lb[i], ub[i]) ? v : 0.0;
-            sax[i] += m1;
-            sx[i] = -eta_x * m1;
-          } else {
-            sax[i] += v;
-          }
-        }
-      }
-      add_jd();
-      if (item == 3) {
-        double* t = sd; sd = sx; sx = t;
-        for (int i = 0; i < n; ++i) sx[i] = Hh[i];
-      }
-    }
+  // item 1: the cotangent eta_v a(a_lam) on f
+  static inline void constraint(const double* w, const double* p, const double* a, const double*, double, double eta_v, double* jt, double* gp) {
+    double v[NS], f[NS];
+    for (int q = 0; q < NS; ++q) v[q] = eta_v * a[q];
+    P::first(w, p, v, f, jt, gp);
   }
-  if (dz0) for (int i = 0; i < n; ++i) dz0[i] = sax[i];
-  if (dlam0) for (int i = 0; i < m; ++i) dlam0[i] = sal[i];
-}
+  static inline double step_ax(double ax, int r, double eta_v, const double* e, const double* jt) {
+    return ax + ((r < NS ? eta_v * e[r] : 0.0) + jt[r]);
+  }
+  static inline void hess(const double* w, const double* p, const double* mu, double wq, bool, double, const double* d, double* hd, double* wo,
+                          double* gp) {
+    double hc[NW];
+    P::second(w, p, mu, d, wo, hd, gp);
+    P::cost_hd(w, wq, d, hc);
+    for (int r = 0; r < NW; ++r) hd[r] = hd[r] + hc[r];
+  }
+};
+
+template <class... A>
+inline void node_exgd_grad_host(A... a) { colloc_exgd_grad_host<NodeExgdPoint>(a...); }
 
 #if defined(__HIPCC__)
 struct NodeExgdWave {
@@ -329,6 +249,7 @@ struct NodeExgdWave {
       hd[c] = F::wsum(wl[NM::L_W1 + c * H + lane] * c1);
     }
   }
+
 };
 
 inline size_t node_exgd_grad_lds_bytes(int N) {

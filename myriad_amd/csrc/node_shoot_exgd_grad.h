@@ -2,7 +2,8 @@
 // transcription (K15 in DESIGN.md; C-ABI myr_exgd_grad_node_shoot).  The route the reference's experiments/node_e2e_sysid.py runs by default.
 //
 // The sweep is K13's (shoot_exgd_grad.h: items 1-5 over the shooting Lagrangian, 2 nsteps + 1 pair passes with the masks between them, a_lam in a
-// column per pair, item 5 of step s fused with item 1 of step s - 1); ShootExgdGrad::out_z / mask and ShootHvp::gather_z are used as they stand.
+// column per pair, item 5 of step s fused with item 1 of step s - 1); ShootExgdGrad::pass_of / out_z / mask and ShootHvp::gather_z are used as
+// they stand.
 // The stage tableaux and control-row rules are K14's (NodeShootProd::rule / stage_point).  The network at a stage point is K12's
 // (node_exgd_grad.h).  What is new is the pair pass that joins them: ShootHvp::interval<true> with the closed-form stage rule replaced by the
 // layer-by-layer one.  For a stage point w_j = [X_j; U_j] of a step with tangent d_j, costate kap_j on f(w_j), its tangent kapd_j and cost
@@ -212,18 +213,6 @@ struct NodeShootExgd {
 #pragma unroll
     for (int q = 0; q < NS; ++q) ck[q] = x[q] - zb[(long)(k + 1) * NS + q];
   }
-
-  // which pass of the reverse sweep: ps = 0 stands at x_n, then per step s = nsteps - 1 ... 0 one pass at x_bar_s and one at x_s
-  struct Pass { int s, at_bar, mode; double scale; };
-  MYR_HD static inline Pass pass_of(int ps, int nsteps, double eta_v) {
-    Pass q;
-    if (ps == 0) { q.s = nsteps; q.at_bar = 0; q.mode = SHOOT_MASK_STEP; q.scale = eta_v; return q; }
-    q.s = nsteps - 1 - (ps - 1) / 2;
-    q.at_bar = (ps & 1);
-    if (q.at_bar) { q.mode = SHOOT_MASK_BAR; q.scale = 0.0; }
-    else { q.mode = q.s > 0 ? SHOOT_MASK_STEP : SHOOT_MASK_LAST; q.scale = q.s > 0 ? eta_v : 0.0; }
-    return q;
-  }
 };
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -258,7 +247,7 @@ struct NseHostNet {
 
 // One instance on the host.  p: the NP shared weights; hist: hist_doubles(I, cpi, nsteps) doubles; work: work_doubles(I, cpi) + n doubles (the
 // carve of the kernel's LDS, then a zero direction for the unfused order); seed_lam, dz0, dlam0 may be null; gp[NP].  fused == false runs
-// items 1 .. 5 as THREE passes a step (item 1 as a pass of its own at x+ with v = 0), as shoot_exgd_grad_host does, for the test of the fusion.
+// items 1 .. 5 as THREE passes a step (ShootExgdGrad::pass_of_unfused), as shoot_exgd_grad_host does, for the test of the fusion.
 template <int M>
 inline void node_shoot_exgd_grad_host(int method, int I, int cpi, double T, const double* z, const double* lam, const double* lb, const double* ub,
                                       const double* p, double eta_x, double eta_v, int nsteps, const double* seed_z, const double* seed_lam,
@@ -315,19 +304,10 @@ inline void node_shoot_exgd_grad_host(int method, int I, int cpi, double T, cons
       A::template interval<true>(net, R, I, cpi, k, h, pt, v, lk ? lc + k : nullptr, p, 1.0, phist + k, side + k, I, al + k, scale);
     for (long i = 0; i < n; ++i) G::mask(mode, G::out_z(I, cpi, i, side, al, scale, I), pt[i], lb[i], ub[i], eta_x, ax[i], zb[i]);
   };
-  if (fused) {
-    for (int ps = 0; ps < (nsteps > 0 ? 2 * nsteps + 1 : 0); ++ps) {
-      const typename A::Pass q = A::pass_of(ps, nsteps, eta_v);
-      const double* Hh = hist + q.s * hs;
-      pass(q.at_bar ? Hh + n : Hh, q.s < nsteps ? Hh + 2 * n : nullptr, zb, q.scale, q.mode);
-    }
-  } else {
-    for (int s = nsteps - 1; s >= 0; --s) {
-      const double* Hh = hist + s * hs;
-      pass(hist + (s + 1) * hs, nullptr, zero, eta_v, SHOOT_MASK_STEP);      // items 1, 2 at x_{s+1} (x_n behind the last step)
-      pass(Hh + n, Hh + 2 * n, zb, 0.0, SHOOT_MASK_BAR);
-      pass(Hh, Hh + 2 * n, zb, 0.0, SHOOT_MASK_LAST);
-    }
+  for (int ps = 0; ps < (fused ? G::passes(nsteps) : G::passes_unfused(nsteps)); ++ps) {
+    const typename G::Pass q = fused ? G::pass_of(ps, nsteps, eta_v) : G::pass_of_unfused(ps, nsteps, eta_v);
+    const double* Hh = hist + q.s * hs;
+    pass(q.at_bar ? Hh + n : Hh, q.alone ? nullptr : Hh + 2 * n, q.alone ? zero : zb, q.scale, q.mode);
   }
   if (dz0) for (long i = 0; i < n; ++i) dz0[i] = ax[i];
   if (dlam0)
@@ -461,12 +441,12 @@ void node_shoot_exgd_grad_kernel(NseArgs a) {
   for (long i = tid; i < n; i += NT) { ax[i] = a.seed_z[b * n + i]; zb[i] = 0.0; }
   for (long i = tid; i < m; i += NT) { const long k = i / NS, q = i - k * NS; al[k + q * I] = a.seed_lam ? a.seed_lam[b * m + i] : 0.0; }
   __syncthreads();
-  const int npass = nsteps > 0 ? 2 * nsteps + 1 : 0;
+  const int npass = G::passes(nsteps);
   for (int ps = 0; ps < npass; ++ps) {
-    const typename A::Pass q = A::pass_of(ps, nsteps, a.eta_v);
+    const typename G::Pass q = G::pass_of(ps, nsteps, a.eta_v);
     const double* Hh = hb + q.s * hs;
     const double* pt = q.at_bar ? Hh + n : Hh;
-    const bool has_lam = q.s < nsteps;
+    const bool has_lam = q.s < nsteps;                             // (= !q.alone in this order; the pass at x_n runs on the cleared direction zb)
     for (long i = tid; i < n; i += NT) zx[i] = pt[i];
     if (has_lam)
       for (long i = tid; i < m; i += NT) { const long k = i / NS, r = i - k * NS; lc[k + r * I] = Hh[2 * n + i]; }

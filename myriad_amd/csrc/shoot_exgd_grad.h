@@ -63,6 +63,35 @@ struct ShootExgdGrad {
     for (int k = 0; k < I; ++k) row += side0[k + (NS + H::ctrl_doubles(cpi) + e) * stride];
     return row;
   }
+
+  // The schedule of the reverse sweep, for the kernels, the launcher and the host twins of K13 and K15 alike.  A pass stands at x_s (x_n for
+  // s = nsteps) or, with at_bar, at x_bar_s; `alone` marks items 1, 2 as a pass of their own: on the zero direction and without multipliers
+  // (alpha = scale a_lam is all that drives it); every other pass takes lam_s and the direction the mask before it wrote.
+  struct Pass { int s, at_bar, alone, mode; double scale; };
+  // the fused order: pass 0 at x_n, then per step s = nsteps - 1 ... 0 one pass at x_bar_s and one at x_s (item 5 of step s with item 1 of s - 1)
+  MYR_HD static inline int passes(int nsteps) { return nsteps > 0 ? 2 * nsteps + 1 : 0; }
+  MYR_HD static inline Pass pass_of(int ps, int nsteps, double eta_v) {
+    Pass q;
+    q.alone = ps == 0;
+    if (ps == 0) { q.s = nsteps; q.at_bar = 0; q.mode = SHOOT_MASK_STEP; q.scale = eta_v; return q; }
+    q.s = nsteps - 1 - (ps - 1) / 2;
+    q.at_bar = (ps & 1);
+    if (q.at_bar) { q.mode = SHOOT_MASK_BAR; q.scale = 0.0; }
+    else { q.mode = q.s > 0 ? SHOOT_MASK_STEP : SHOOT_MASK_LAST; q.scale = q.s > 0 ? eta_v : 0.0; }
+    return q;
+  }
+  // the unfused order of exgd_grad.h, three passes a step: items 1, 2 alone at x_{s+1}, then x_bar_s, then x_s (the host twins' test of the fusion)
+  MYR_HD static inline int passes_unfused(int nsteps) { return 3 * nsteps; }
+  MYR_HD static inline Pass pass_of_unfused(int ps, int nsteps, double eta_v) {
+    const int s = nsteps - 1 - ps / 3, r = ps % 3;
+    Pass q;
+    q.alone = r == 0;
+    q.s = r == 0 ? s + 1 : s;
+    q.at_bar = r == 1;
+    q.mode = r == 0 ? SHOOT_MASK_STEP : (r == 1 ? SHOOT_MASK_BAR : SHOOT_MASK_LAST);
+    q.scale = r == 0 ? eta_v : 0.0;
+    return q;
+  }
 };
 
 // ---- one instance on the host: the forward steps (the arithmetic of shoot_eval_kernel + exgd_update_kernel + axpy_kernel) and the passes as loops ----
@@ -115,7 +144,7 @@ inline void shoot_lagrangian_host(int method, int I, int cpi, double T, const do
 
 // p: the instance's parameter buffer (SysParams::get()); hist: hist_doubles(I, cpi, nsteps) doubles; work: 5 n + 2 m + (cpi + 1) NS + I (NS +
 // ShootHvp::hist_doubles + side_doubles) doubles; seed_lam, dz0, dlam0 may be null; gp[NP].  fused == false runs items 1 .. 5 as THREE passes a step
-// (item 1 as a pass of its own at x+ with v = 0), the order of exgd_grad.h, for the test of the fusion.
+// (item 1 as a pass of its own at x+ with v = 0: ShootExgdGrad::pass_of_unfused), the order of exgd_grad.h, for the test of the fusion.
 template <class Sys, int M>
 inline void shoot_exgd_grad_host(int method, int I, int cpi, double T, const double* z, const double* lam, const double* lb, const double* ub,
                                  const double* p, double eta_x, double eta_v, int nsteps, const double* seed_z, const double* seed_lam, double* hist,
@@ -162,16 +191,11 @@ inline void shoot_exgd_grad_host(int method, int I, int cpi, double T, const dou
     for (long i = 0; i < n; ++i) G::mask(mode, G::out_z(I, cpi, i, side, al, scale, I), pt[i], lb[i], ub[i], eta_x, ax[i], dir[i]);
     for (int e = 0; e < NP; ++e) gp[e] = G::add_rows(I, cpi, e, side, I, gp[e]);
   };
-  if (nsteps > 0) {
-    for (long i = 0; i < n; ++i) zx[i] = 0.0;
-    if (fused) pass(hist + nsteps * hs, nullptr, zx, eta_v, SHOOT_MASK_STEP);
-  }
-  for (int s = nsteps - 1; s >= 0; --s) {
-    const double* Hh = hist + s * hs;
-    if (!fused) pass(hist + (s + 1) * hs, nullptr, zx, eta_v, SHOOT_MASK_STEP);      // items 1, 2 at x_{s+1} (x_n behind the last step)
-    pass(Hh + n, Hh + 2 * n, dir, 0.0, SHOOT_MASK_BAR);
-    if (fused) pass(Hh, Hh + 2 * n, dir, s > 0 ? eta_v : 0.0, s > 0 ? SHOOT_MASK_STEP : SHOOT_MASK_LAST);
-    else pass(Hh, Hh + 2 * n, dir, 0.0, SHOOT_MASK_LAST);
+  for (long i = 0; i < n; ++i) zx[i] = 0.0;
+  for (int ps = 0; ps < (fused ? G::passes(nsteps) : G::passes_unfused(nsteps)); ++ps) {
+    const typename G::Pass q = fused ? G::pass_of(ps, nsteps, eta_v) : G::pass_of_unfused(ps, nsteps, eta_v);
+    const double* Hh = hist + q.s * hs;
+    pass(q.at_bar ? Hh + n : Hh, q.alone ? nullptr : Hh + 2 * n, q.alone ? zx : dir, q.scale, q.mode);
   }
   if (dz0) for (long i = 0; i < n; ++i) dz0[i] = ax[i];
   if (dlam0)

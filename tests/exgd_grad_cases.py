@@ -61,23 +61,25 @@ def _transcription(name, scheme, N, T, prow):
     return sysm, O.make_transcription(sysm, "COLLOCATION", N, quadrature_rule=scheme)
 
 
-def oracle_run(name, scheme, N, T, z, lam, lb, ub, prow, eta_x, eta_v, nsteps, grad_params=True):
-  """One instance through `nsteps` steps in torch.  Returns (z_n, lam_n, leaves, pre, pts): the leaf tensors (parameters, z0, lam0), the values in
-  front of every clamp and every point the run evaluated the Lagrangian's gradient at."""
-  pt = [torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for v in prow] if grad_params else [float(v) for v in prow]
-  _, tr = _transcription(name, scheme, N, T, pt)
-  x = torch.tensor(np.asarray(z), dtype=torch.float64, requires_grad=True)
-  lm = torch.tensor(np.asarray(lam), dtype=torch.float64, requires_grad=True)
-  lo, hi = torch.tensor(np.asarray(lb)), torch.tensor(np.asarray(ub))
+def start_leaves(z, lam):
+  """(z0, lam0): the starting point of a run as leaf tensors"""
+  return (torch.tensor(np.asarray(z), dtype=torch.float64, requires_grad=True),
+          torch.tensor(np.asarray(lam), dtype=torch.float64, requires_grad=True))
+
+
+def unrolled_steps(tr, x, lm, lo, hi, eta_x, eta_v, nsteps):
+  """`nsteps` steps of `Lagrangian.step` (extra_gradient.py:25-33) over the transcription `tr`, restated with `torch.clamp`, from the tensors
+  (x, lm) between the bounds (lo, hi).  Returns (x_n, lam_n, pre, pts): the values in front of every clamp and every point the run evaluated the
+  Lagrangian's gradient at.  The one statement of the step for the four case modules of the family."""
+  lo, hi = torch.tensor(np.asarray(lo)), torch.tensor(np.asarray(hi))
   L = lambda xx, ll: tr.objective(xx) + ll @ tr.constraints(xx)      # extra_gradient.py:21-23
 
   def gx(xx, ll):                                                   # the PARTIAL gradient in x: lam_s is itself a function of x_s, so the
     xi = xx * 1.0                                                    # derivative is taken in a copy that lam_s does not hang on
     return torch.autograd.grad(L(xi, ll), xi, create_graph=True)[0]
 
-  z0, lam0 = x, lm
   pre, pts = [], []
-  for _ in range(nsteps):                                            # Lagrangian.step, extra_gradient.py:25-33
+  for _ in range(nsteps):
     pts.append(x)
     v = x - eta_x * gx(x, lm)
     pre.append(v)
@@ -88,6 +90,55 @@ def oracle_run(name, scheme, N, T, z, lam, lb, ub, prow, eta_x, eta_v, nsteps, g
     x = torch.clamp(v, lo, hi)
     pts.append(x)
     lm = lm + eta_v * tr.constraints(x)
+  return x, lm, pre, pts
+
+
+def draw_boxes(rng, z, delta, ns):
+  """(lb, ub) around z [B][n] for first half-steps of length delta: the first point's state (the first ns entries) pinned; a box of 0.3 delta,
+  which the first half-step leaves, around 30 % of the other, FREE variables of every instance, taken from those whose half-step is longer than
+  1e-5; of the rest about half get finite bounds far away.  Draws from rng one permutation per instance, then one random((B, n))."""
+  batch, n = z.shape
+  lb = np.full((batch, n), -np.inf)
+  ub = np.full((batch, n), np.inf)
+  clipv = np.zeros((batch, n), dtype=bool)
+  for b in range(batch):
+    cand = ns + np.flatnonzero(delta[b, ns:] > 1e-5)
+    clipv[b, rng.permutation(cand)[:int(round(0.3 * (n - ns)))]] = True
+  wide = ~clipv & (rng.random((batch, n)) < 0.5)
+  lb[clipv] = (z - 0.3 * delta)[clipv]; ub[clipv] = (z + 0.3 * delta)[clipv]
+  lb[wide] = (z - 1.0 - 100.0 * delta)[wide]; ub[wide] = (z + 1.0 + 100.0 * delta)[wide]
+  lb[:, :ns] = z[:, :ns]; ub[:, :ns] = z[:, :ns]
+  return lb, ub
+
+
+def clamp_conditions(pre, lo, hi):
+  """(tie, outside) of one instance from the values in front of its clamps: the smallest distance of an unclipped value (lo < v < hi) to a
+  bound -- 0 where a clipped one meets its bound exactly: clamp passes it, the mask does not --, and which variables clipped in some half-step"""
+  tie, outside = np.inf, np.zeros(np.shape(lo), dtype=bool)
+  for v in pre:
+    v = v.detach().numpy()
+    out = (v <= lo) | (v >= hi)
+    with np.errstate(invalid="ignore"):
+      dist = np.minimum(np.abs(v - lo), np.abs(v - hi))
+    tie = min(tie, float(dist[~out].min()) if (~out).any() else np.inf)
+    if (dist[out] == 0.0).any():
+      tie = 0.0
+    outside |= out
+  return tie, outside
+
+
+def clipped_fraction(clipped, lb, ub):
+  """of the FREE variables (lb < ub; a pinned one is clipped by construction) the fraction that clipped, the smallest over the instances"""
+  free = lb < ub
+  return float(min((clipped[b] & free[b]).sum() / free[b].sum() for b in range(len(lb))))
+
+
+def oracle_run(name, scheme, N, T, z, lam, lb, ub, prow, eta_x, eta_v, nsteps, grad_params=True):
+  """One instance through `nsteps` steps in torch.  Returns (z_n, lam_n, leaves, pre, pts): the leaf tensors (parameters, z0, lam0), the values in
+  front of every clamp and every point the run evaluated the Lagrangian's gradient at."""
+  pt = [torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for v in prow] if grad_params else [float(v) for v in prow]
+  z0, lam0 = start_leaves(z, lam)
+  x, lm, pre, pts = unrolled_steps(_transcription(name, scheme, N, T, pt)[1], z0, lam0, lb, ub, eta_x, eta_v, nsteps)
   return x, lm, (pt, z0, lam0), pre, pts
 
 
@@ -146,18 +197,7 @@ def _draw(name, scheme, N, nsteps, batch, seed):
   eta_x = 0.2 / max(lip, 1e-12)
   eta_v = 0.2 / max(eta_x * jn, 1e-12)
   delta = eta_x * np.abs(g0)
-  lb = np.full((batch, n), -np.inf)
-  ub = np.full((batch, n), np.inf)
-  # a box the first half-step leaves around 30 % of the FREE variables (all but the pinned state of the first point) of every instance, taken
-  # from those whose first half-step is longer than 1e-5; of the others about half get finite bounds far away
-  clipv = np.zeros((batch, n), dtype=bool)
-  for b in range(batch):
-    cand = ns + np.flatnonzero(delta[b, ns:] > 1e-5)
-    clipv[b, rng.permutation(cand)[:int(round(0.3 * (n - ns)))]] = True
-  wide = ~clipv & (rng.random((batch, n)) < 0.5)
-  lb[clipv] = (z - 0.3 * delta)[clipv]; ub[clipv] = (z + 0.3 * delta)[clipv]
-  lb[wide] = (z - 1.0 - 100.0 * delta)[wide]; ub[wide] = (z + 1.0 + 100.0 * delta)[wide]
-  lb[:, :ns] = z[:, :ns]; ub[:, :ns] = z[:, :ns]       # the first point's state is pinned
+  lb, ub = draw_boxes(rng, z, delta, ns)
   return dict(name=name, scheme=scheme, N=N, T=T, nsteps=nsteps, z=z, lam=lam, lb=lb, ub=ub, params=params, eta_x=float(eta_x), eta_v=float(eta_v),
               seed_z=seed_z, seed_lam=seed_lam, K=K, n=n, m=m, ns=ns, nu=nu)
 
@@ -169,7 +209,6 @@ def _oracle(case):
   batch, npar = c["z"].shape[0], c["params"].shape[1]
   grad, dz0, dlam0 = np.empty((batch, npar)), np.empty((batch, c["n"])), np.empty((batch, c["m"]))
   tie, kink, clipped = np.inf, np.inf, np.zeros((batch, c["n"]), dtype=bool)
-  free = c["lb"] < c["ub"]                             # a pinned variable is clipped by construction: it does not count
   fd = c["name"] in FD_SYSTEMS
 
   def out_of(b, prow, grad_params):
@@ -190,18 +229,10 @@ def _oracle(case):
         grad[b, k] = (float(out_of(b, pp, False)[0].detach()) - float(out_of(b, pm, False)[0].detach())) / (2.0 * d)
     else:
       grad[b] = [float(g) for g in gs[:npar]]
-    lo, hi = c["lb"][b], c["ub"][b]
-    for v in pre:
-      v = v.detach().numpy()
-      out = (v <= lo) | (v >= hi)
-      with np.errstate(invalid="ignore"):
-        dist = np.minimum(np.abs(v - lo), np.abs(v - hi))
-      tie = min(tie, float(dist[~out].min()) if (~out).any() else np.inf)      # an unclipped value near a bound
-      if (dist[out] == 0.0).any():                                                # a value that meets its bound exactly: clamp passes it, the mask does not
-        tie = 0.0
-      clipped[b] |= out
+    t, out = clamp_conditions(pre, c["lb"][b], c["ub"][b])
+    tie, clipped[b] = min(tie, t), out
     kink = min(kink, _kink_distance(c["name"], c["K"], c["ns"], c["nu"], pts))
-  return grad, dz0, dlam0, tie, kink, float(min((clipped[b] & free[b]).sum() / free[b].sum() for b in range(batch)))
+  return grad, dz0, dlam0, tie, kink, clipped_fraction(clipped, c["lb"], c["ub"])
 
 
 @functools.lru_cache(maxsize=None)

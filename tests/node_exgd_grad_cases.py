@@ -58,25 +58,8 @@ def oracle_run(N, T, z, lam, lb, ub, eta_x, eta_v, nsteps, grad_params=True):
   """exgd_grad_cases.oracle_run for the network system: (z_n, lam_n, (weight leaves in the device order, z0, lam0), values in front of every clamp)"""
   tp = _leaves(grad_params)
   tr = _transcription(N, T, tp)
-  x = torch.tensor(np.asarray(z), dtype=torch.float64, requires_grad=True)
-  lm = torch.tensor(np.asarray(lam), dtype=torch.float64, requires_grad=True)
-  lo, hi = torch.tensor(np.asarray(lb)), torch.tensor(np.asarray(ub))
-  L = lambda xx, ll: tr.objective(xx) + ll @ tr.constraints(xx)
-
-  def gx(xx, ll):                                                   # the PARTIAL gradient in x (exgd_grad_cases.oracle_run)
-    xi = xx * 1.0
-    return torch.autograd.grad(L(xi, ll), xi, create_graph=True)[0]
-
-  z0, lam0 = x, lm
-  pre = []
-  for _ in range(nsteps):
-    v = x - eta_x * gx(x, lm)
-    pre.append(v)
-    xb = torch.clamp(v, lo, hi)
-    v = x - eta_x * gx(xb, lm)
-    pre.append(v)
-    x = torch.clamp(v, lo, hi)
-    lm = lm + eta_v * tr.constraints(x)
+  z0, lam0 = E.start_leaves(z, lam)
+  x, lm, pre, _ = E.unrolled_steps(tr, z0, lam0, lb, ub, eta_x, eta_v, nsteps)
   return x, lm, ([tp[k][f] for k in KEYS for f in ("w", "b")], z0, lam0), pre
 
 
@@ -105,16 +88,7 @@ def _draw(N, nsteps, batch, seed):
     lip, v = np.linalg.norm(hv), hv
   eta_x, eta_v = 0.2 / max(lip, 1e-12), 0.5
   delta = eta_x * np.abs(g0)
-  lb = np.full((batch, n), -np.inf)
-  ub = np.full((batch, n), np.inf)
-  clipv = np.zeros((batch, n), dtype=bool)
-  for b in range(batch):
-    cand = NS + np.flatnonzero(delta[b, NS:] > 1e-5)
-    clipv[b, rng.permutation(cand)[:int(round(0.3 * (n - NS)))]] = True
-  wide = ~clipv & (rng.random((batch, n)) < 0.5)
-  lb[clipv] = (z - 0.3 * delta)[clipv]; ub[clipv] = (z + 0.3 * delta)[clipv]
-  lb[wide] = (z - 1.0 - 100.0 * delta)[wide]; ub[wide] = (z + 1.0 + 100.0 * delta)[wide]
-  lb[:, :NS] = z[:, :NS]; ub[:, :NS] = z[:, :NS]
+  lb, ub = E.draw_boxes(rng, z, delta, NS)
   return dict(N=N, T=T, nsteps=nsteps, z=z, lam=lam, lb=lb, ub=ub, params=weights()[1], eta_x=float(eta_x), eta_v=float(eta_v), seed_z=seed_z,
               seed_lam=seed_lam, K=K, n=n, m=m, ns=NS, nu=NU)
 
@@ -123,7 +97,6 @@ def _oracle(c):
   batch = c["z"].shape[0]
   grad, dz0, dlam0 = np.empty((batch, NP)), np.empty((batch, c["n"])), np.empty((batch, c["m"]))
   tie, clipped = np.inf, np.zeros((batch, c["n"]), dtype=bool)
-  free = c["lb"] < c["ub"]
   for b in range(batch):
     xn, ln, (pt, z0, lam0), pre = oracle_run(c["N"], c["T"], c["z"][b], c["lam"][b], c["lb"][b], c["ub"][b], c["eta_x"], c["eta_v"], c["nsteps"])
     out = (torch.tensor(c["seed_z"][b]) * xn).sum() + (torch.tensor(c["seed_lam"][b]) * ln).sum()
@@ -131,17 +104,9 @@ def _oracle(c):
     gs = [torch.zeros_like(t) if g is None else g for g, t in zip(gs, pt + [z0, lam0])]
     grad[b] = np.concatenate([g.numpy().ravel() for g in gs[:-2]])
     dz0[b], dlam0[b] = gs[-2].numpy(), gs[-1].numpy()
-    lo, hi = c["lb"][b], c["ub"][b]
-    for v in pre:
-      v = v.detach().numpy()
-      outside = (v <= lo) | (v >= hi)
-      with np.errstate(invalid="ignore"):
-        dist = np.minimum(np.abs(v - lo), np.abs(v - hi))
-      tie = min(tie, float(dist[~outside].min()) if (~outside).any() else np.inf)
-      if (dist[outside] == 0.0).any():
-        tie = 0.0
-      clipped[b] |= outside
-  return grad, dz0, dlam0, tie, float(min((clipped[b] & free[b]).sum() / free[b].sum() for b in range(batch)))
+    t, outside = E.clamp_conditions(pre, c["lb"][b], c["ub"][b])
+    tie, clipped[b] = min(tie, t), outside
+  return grad, dz0, dlam0, tie, E.clipped_fraction(clipped, c["lb"], c["ub"])
 
 
 @functools.lru_cache(maxsize=None)

@@ -55,25 +55,8 @@ def oracle_run(name, I, cpi, method, T, z, lam, lb, ub, prow, eta_x, eta_v, nste
   front of every clamp; `visited` collects every point the field is evaluated at."""
   pt = [torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for v in prow] if grad_params else [float(v) for v in prow]
   _, tr = H._transcription(name, "SHOOTING", I, cpi, method, T, pt, visited)
-  x = torch.tensor(np.asarray(z), dtype=torch.float64, requires_grad=True)
-  lm = torch.tensor(np.asarray(lam), dtype=torch.float64, requires_grad=True)
-  lo, hi = torch.tensor(np.asarray(lb)), torch.tensor(np.asarray(ub))
-  L = lambda xx, ll: tr.objective(xx) + ll @ tr.constraints(xx)      # extra_gradient.py:21-23
-
-  def gx(xx, ll):                                                   # the PARTIAL gradient in x (exgd_grad_cases.oracle_run)
-    xi = xx * 1.0
-    return torch.autograd.grad(L(xi, ll), xi, create_graph=True)[0]
-
-  z0, lam0 = x, lm
-  pre = []
-  for _ in range(nsteps):                                            # Lagrangian.step, extra_gradient.py:25-33
-    v = x - eta_x * gx(x, lm)
-    pre.append(v)
-    xb = torch.clamp(v, lo, hi)
-    v = x - eta_x * gx(xb, lm)
-    pre.append(v)
-    x = torch.clamp(v, lo, hi)
-    lm = lm + eta_v * tr.constraints(x)
+  z0, lam0 = E.start_leaves(z, lam)
+  x, lm, pre, _ = E.unrolled_steps(tr, z0, lam0, lb, ub, eta_x, eta_v, nsteps)
   return x, lm, (pt, z0, lam0), pre
 
 
@@ -98,16 +81,7 @@ def _draw(name, I, cpi, method, nsteps, batch, seed):
   eta_x = 0.2 / max(lip, 1e-12)
   eta_v = 0.2 / max(eta_x * jn, 1e-12)
   delta = eta_x * np.abs(g0)
-  lb = np.full((batch, n), -np.inf)
-  ub = np.full((batch, n), np.inf)
-  clipv = np.zeros((batch, n), dtype=bool)
-  for b in range(batch):
-    cand = ns + np.flatnonzero(delta[b, ns:] > 1e-5)
-    clipv[b, rng.permutation(cand)[:int(round(0.3 * (n - ns)))]] = True
-  wide = ~clipv & (rng.random((batch, n)) < 0.5)
-  lb[clipv] = (z - 0.3 * delta)[clipv]; ub[clipv] = (z + 0.3 * delta)[clipv]
-  lb[wide] = (z - 1.0 - 100.0 * delta)[wide]; ub[wide] = (z + 1.0 + 100.0 * delta)[wide]
-  lb[:, :ns] = z[:, :ns]; ub[:, :ns] = z[:, :ns]                     # the first node's state is pinned
+  lb, ub = E.draw_boxes(rng, z, delta, ns)
   return dict(name=name, I=I, cpi=cpi, method=method, T=T, nsteps=nsteps, z=z, lam=lam, lb=lb, ub=ub, params=params, eta_x=float(eta_x),
               eta_v=float(eta_v), seed_z=seed_z, seed_lam=seed_lam, n=n, m=m, ns=ns, nu=base["nu"])
 
@@ -119,7 +93,6 @@ def _oracle(case):
   batch, npar = c["z"].shape[0], c["params"].shape[1]
   grad, dz0, dlam0 = np.empty((batch, npar)), np.empty((batch, c["n"])), np.empty((batch, c["m"]))
   tie, kink, clipped = np.inf, np.inf, np.zeros((batch, c["n"]), dtype=bool)
-  free = c["lb"] < c["ub"]
   fd = c["name"] in FD_SYSTEMS
   grad2 = np.empty((batch, npar))                      # the quotient with twice the step (FD_SELF)
 
@@ -144,20 +117,12 @@ def _oracle(case):
         grad2[b, k] = (float(out_of(b, pp, False)[0].detach()) - float(out_of(b, pm, False)[0].detach())) / (4.0 * d)
     else:
       grad[b] = [float(g) for g in gs[:npar]]
-    lo, hi = c["lb"][b], c["ub"][b]
-    for v in pre:
-      v = v.detach().numpy()
-      outside = (v <= lo) | (v >= hi)
-      with np.errstate(invalid="ignore"):
-        dist = np.minimum(np.abs(v - lo), np.abs(v - hi))
-      tie = min(tie, float(dist[~outside].min()) if (~outside).any() else np.inf)
-      if (dist[outside] == 0.0).any():
-        tie = 0.0
-      clipped[b] |= outside
+    t, outside = E.clamp_conditions(pre, c["lb"][b], c["ub"][b])
+    tie, clipped[b] = min(tie, t), outside
     kink = min(kink, H._kink_distance(c["name"], visited))
   with np.errstate(invalid="ignore"):
     self_check = rel_error(grad2, grad) if fd else 0.0
-  return grad, dz0, dlam0, tie, kink, float(min((clipped[b] & free[b]).sum() / free[b].sum() for b in range(batch))), self_check
+  return grad, dz0, dlam0, tie, kink, E.clipped_fraction(clipped, c["lb"], c["ub"]), self_check
 
 
 @functools.lru_cache(maxsize=None)
