@@ -25,6 +25,7 @@
  *   ... in the network weights under SHOOTING     experiments/node_e2e_sysid.py:139-166, 187-196  myr_exgd_grad_node_shoot
  *   jax.hessian / jax.jvp(jax.grad(lagrangian))  (no call site in the reference: the exact second derivative
  *                                                an external second-order method asks for)  myr_hvp
+ *   ... of the network system                    (the same, in the 4 804 weights)                 myr_hvp_node
  *
  * Conventions
  *   - all floating point is IEEE fp64 (the reference sets jax_enable_x64, run.py:15);
@@ -91,7 +92,9 @@ enum { MYR_STATUS_CONVERGED = 0, MYR_STATUS_MAXITER = 1, MYR_STATUS_NAN = 2, MYR
           whose elastic twin converges with a slack that does not vanish as its penalty grows */
        MYR_STATUS_INFEASIBLE = 4 };
 /* kernel ids for myr_kernel_time */
-enum { MYR_K_EVAL = 0, MYR_K_SOLVE = 1, MYR_K_ROLLOUT = 2, MYR_K_RESID = 3, MYR_K_PROD = 4, MYR_K_FBSM = 5, MYR_K_FIT = 6, MYR_K_COUNT = 7 };
+enum { MYR_K_EVAL = 0, MYR_K_SOLVE = 1, MYR_K_ROLLOUT = 2, MYR_K_RESID = 3, MYR_K_PROD = 4, MYR_K_FBSM = 5, MYR_K_FIT = 6,
+       MYR_K_HVP_NODE = 7, MYR_K_HVP_NODE_SHOOT = 8,      /* myr_hvp_node: the Hermite-Simpson kernel / the SHOOTING kernel (each with its batch sum) */
+       MYR_K_COUNT = 9 };
 /* error codes */
 enum { MYR_OK = 0, MYR_E_ARG = -1, MYR_E_UNSUPPORTED = -2, MYR_E_HIP = -3, MYR_E_CAPACITY = -4 };
 
@@ -431,6 +434,29 @@ int myr_exgd_grad_node_shoot(myr_handle h, int32_t B, const double* z, const dou
  */
 int myr_hvp(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params,
             int32_t params_stride, int32_t with_cost, double* out_z, double* out_p, int32_t p_stride, int32_t mem);
+
+/*
+ * myr_hvp for the network system (library version 0.9): the same two products on a MYR_SYS_NODE_CARTPOLE handle under
+ * MYR_TR_HERMITE_SIMPSON or MYR_TR_SHOOTING (all four integrators), out_p in the 4 804 weights in the order of csrc/node_system.h.
+ * With L = with_cost f + lam^T c and psi = <grad_z L, v>:  out_z[b] = grad_z psi,  out_p[b] = grad_p psi.
+ *   z [B][n]; lam [B][m] or NULL (= 0); v [B][n]; params [np]: ONE weight set shared by the batch, required (no params_stride, as in
+ *   myr_exgd_grad_node); out_z [B][n] or NULL; out_p [B][np] if p_stride == np, [np] = the fixed-order sum over the batch if p_stride == 0
+ *   (no atomics), or NULL -- not both NULL.  Inputs are not modified; B == 0 writes nothing.
+ * The running cost is the TRUE system's: it has no weights, but its second derivative enters out_z, and under SHOOTING its gradient enters
+ * every stage costate and so out_p.  The same bits on every call, for MYR_MEM_HOST and MYR_MEM_DEVICE, for an instance alone or inside any
+ * batch, whatever ran on the handle before; out_z has the same bits with and without out_p.
+ * Hermite-Simpson: one workgroup of 4 wavefronts per instance, a wavefront per collocation point (lane j = hidden unit j), the inputs read
+ * where they lie -- no horizon is refused.  SHOOTING: one workgroup of 1, 2 or 4 wavefronts (from the number of intervals alone) per
+ * instance, a wavefront per (instance, interval) pair (csrc/node_hvp.h).
+ * MYR_E_UNSUPPORTED: a handle whose system is not MYR_SYS_NODE_CARTPOLE (use myr_hvp), MYR_TR_TRAPEZOIDAL -- both before the size checks;
+ * MYR_E_ARG: null h / z / v / params, both outputs NULL, a p_stride other than 0 and np, negative B, a bad mem;
+ * MYR_E_CAPACITY (SHOOTING only): the weight copy (5 064 doubles) and the pairs' records, I (3 ns + 2 ns cpi + (M cpi + 1) nu) doubles
+ * (M = 2 for RK4, 1 otherwise), pass the 160 KiB LDS: 15 414 doubles beside the weights -- single shooting up to 1 x 1 711 (1 x 1 540
+ * under RK4), 700 x 1, 20 x 84 (1 x 2 000 is refused).
+ * myr_hvp keeps refusing the network system.
+ */
+int myr_hvp_node(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params,
+                 int32_t with_cost, double* out_z, double* out_p, int32_t p_stride, int32_t mem);
 
 /* Average device time (HIP events on the handle's stream) of the launches of one kernel since the last reset. */
 int myr_kernel_time(myr_handle h, int32_t kernel_id, double* avg_ms, int32_t* launches);

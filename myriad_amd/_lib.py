@@ -24,14 +24,14 @@ SYS_IDS = {"CARTPOLE": 0, "VANDERPOL": 1, "CANCERTREATMENT": 2, "SIMPLECASE": 3,
 TR_IDS = {"HERMITE_SIMPSON": 0, "TRAPEZOIDAL": 1, "SHOOTING": 2}
 INT_IDS = {"EULER": 0, "HEUN": 1, "MIDPOINT": 2, "RK4": 3}
 MEM_HOST, MEM_DEVICE = 0, 1
-K_EVAL, K_SOLVE, K_ROLLOUT, K_RESID, K_PROD, K_FBSM, K_FIT = 0, 1, 2, 3, 4, 5, 6
+K_EVAL, K_SOLVE, K_ROLLOUT, K_RESID, K_PROD, K_FBSM, K_FIT, K_HVP_NODE, K_HVP_NODE_SHOOT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 STATUS_NAMES = {0: "CONVERGED", 1: "MAXITER", 2: "NAN", 3: "STALLED", 4: "INFEASIBLE"}
 STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr_solve (csrc/myriad_hip.hip: solve_restored), never by a kernel
 
 EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
            "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
            "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp",
-           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot"]
+           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot", "myr_hvp_node"]
 
 
 class ProblemDesc(C.Structure):
@@ -119,6 +119,8 @@ def load() -> C.CDLL:
   lib.myr_exgd_grad_node_shoot.restype = C.c_int
   lib.myr_hvp.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, C.c_int32, C.c_int32]
   lib.myr_hvp.restype = C.c_int
+  lib.myr_hvp_node.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
+  lib.myr_hvp_node.restype = C.c_int
   lib.myr_fbsm.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_double, C.c_double, C.c_int32,
                            dp, dp, dp, ip, C.c_int32]
   lib.myr_fbsm.restype = C.c_int
@@ -524,6 +526,38 @@ class Engine:
     """Zero-copy variant of hvp: every array is a device tensor on this handle's device (lam, out_z, out_p may be None); nothing is copied."""
     _chk(self.lib.myr_hvp(self._h, int(B), _addr(z), _addr(lam), _addr(v), _addr(params), int(params_stride), int(bool(with_cost)), _addr(out_z),
                           _addr(out_p), int(p_stride), MEM_DEVICE), "myr_hvp")
+
+  def hvp_node(self, z, lam, v, params, with_cost=True, want_z=True, want_p=False, reduce=False):
+    """myr_hvp_node: hvp on a handle of the network system (HERMITE_SIMPSON or SHOOTING); `params`: the 4 804 shared weights, the flat vector of
+    csrc/node_system.h's order.  Returns {"hz" [B,n] (with want_z), "hp" [B,np], or [np] = the sum over the batch with reduce=True (with want_p)}."""
+    z = self._batch2(z, self.n, "z"); v = self._batch2(v, self.n, "v")
+    B = z.shape[0]
+    lam = None if lam is None else self._batch2(lam, self.m, "lam")
+    if v.shape[0] != B or (lam is not None and lam.shape[0] != B):
+      raise ValueError("z, lam and v must have the same batch size")
+    p = None if params is None else np.ascontiguousarray(_f64(params))
+    if p is not None and p.shape != (self.np,):
+      raise ValueError(f"params must be the {self.np} shared weights")
+    hz = np.empty((B, self.n)) if want_z else None
+    hp = (np.empty(self.np) if reduce else np.empty((B, self.np))) if want_p else None
+    _chk(self.lib.myr_hvp_node(self._h, B, _addr(z), _addr(lam), _addr(v), _addr(p), int(bool(with_cost)), _addr(hz), _addr(hp),
+                               0 if reduce else self.np, MEM_HOST), "myr_hvp_node")
+    out = {}
+    if want_z:
+      out["hz"] = hz
+    if want_p:
+      out["hp"] = hp
+    return out
+
+  def hvp_node_device(self, B, z, lam, v, params, out_z=None, out_p=None, p_stride=0, with_cost=True):
+    """Zero-copy variant of hvp_node: every array is a device tensor on this handle's device (lam, out_z, out_p may be None); nothing is copied."""
+    _chk(self.lib.myr_hvp_node(self._h, int(B), _addr(z), _addr(lam), _addr(v), _addr(params), int(bool(with_cost)), _addr(out_z), _addr(out_p),
+                               int(p_stride), MEM_DEVICE), "myr_hvp_node")
+
+  def hvp_node_probe(self):
+    """Raises the library's error when myr_hvp_node is not built for this handle (an empty batch: the checks run, nothing else)."""
+    d = np.zeros(1)
+    _chk(self.lib.myr_hvp_node(self._h, 0, _addr(d), None, _addr(d), _addr(d), 1, _addr(d), None, 0, MEM_HOST), "myr_hvp_node")
 
   def products_device(self, op, B, z, w, out, params=None, params_stride=0, add_gradf=0):
     """Zero-copy vjp ('vjp') / jvp ('jvp') on device tensors."""

@@ -32,6 +32,7 @@
 #include "shoot_exgd_grad.h"
 #include "node_shoot_products.h"
 #include "node_shoot_exgd_grad.h"
+#include "node_hvp.h"
 #include "fbsm.h"
 #include "systems_gen.h"
 #include "node_system.h"
@@ -1344,6 +1345,42 @@ int exgd_grad_node_shoot_for_system(myr_handle h, const ExgdGradArgs& a) {
   return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: the network system only; use myr_exgd_grad_shoot");
 }
 
+// ------------------------------------------------------------------------------------------------
+// Lagrangian Hessian-vector product of the network system (node_hvp.h: node_hvp_colloc_kernel, node_hvp_shoot_kernel; myr_hvp_node has checked
+// system, transcription and that the SHOOTING carve fits).  One weight set: a.params [np], a.pstride is not read
+// ------------------------------------------------------------------------------------------------
+template <class Sys>
+int hvp_node_colloc_for_system(myr_handle h, const HvpArgs& a) {
+  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // the kernel lives in the network system's object only
+    constexpr int WPI = 4;
+    const int N = h->d.intervals;
+    hipLaunchKernelGGL(node_hvp_colloc_kernel<WPI>, dim3((unsigned)a.B), dim3(64 * WPI), node_hvp_colloc_lds_bytes(), h->stream, a.B, N, h->d.T / N, a.z,
+                       a.lam, a.v, a.params, a.with_cost, a.out_z, a.rows);
+    return MYR_OK;
+  }
+  return fail(MYR_E_UNSUPPORTED, "myr_hvp_node: the network system only; use myr_hvp");
+}
+
+template <int M>
+static int launch_node_hvp_shoot(myr_handle h, const HvpArgs& a) {
+  const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+  const size_t lds = node_hvp_shoot_lds_bytes<M>(I, cpi);
+  auto kern = node_hvp_shoot_kernel<M>;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  NodeHvpArgs k{};
+  k.B = a.B; k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.with_cost = a.with_cost; k.T = h->d.T;
+  k.z = a.z; k.lam = a.lam; k.v = a.v; k.params = a.params; k.out_z = a.out_z; k.rows = a.rows;
+  hipLaunchKernelGGL(kern, dim3((unsigned)k.B), dim3(64 * node_hvp_shoot_wpi(I)), lds, h->stream, k);
+  return MYR_OK;
+}
+
+template <class Sys>
+int hvp_node_shoot_for_system(myr_handle h, const HvpArgs& a) {
+  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value)
+    return h->d.integration_method == MYR_INT_RK4 ? launch_node_hvp_shoot<2>(h, a) : launch_node_hvp_shoot<1>(h, a);
+  return fail(MYR_E_UNSUPPORTED, "myr_hvp_node: the network system only; use myr_hvp");
+}
+
 // ---- per-system entry points: explicit instantiation (system objects) / extern declaration (main object) -----------------
 #define MYR_SYSTEM_ENTRY_POINTS(LINK, S)                                                                                          \
   LINK template int eval_for_system<S>(myr_handle, const EvalArgs&);          \
@@ -1357,10 +1394,12 @@ int exgd_grad_node_shoot_for_system(myr_handle h, const ExgdGradArgs& a) {
   LINK template int hvp_shoot_for_system<S>(myr_handle, const HvpArgs&);      \
   LINK template int exgd_grad_shoot_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int exgd_grad_node_shoot_for_system<S>(myr_handle, const ExgdGradArgs&); \
+  LINK template int hvp_node_colloc_for_system<S>(myr_handle, const HvpArgs&); \
+  LINK template int hvp_node_shoot_for_system<S>(myr_handle, const HvpArgs&); \
   LINK template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 #if defined(MYR_TU_SYSTEM) && defined(MYR_TU_PART)
 // a system's object in parts (the build splits the slow ones): -DMYR_TU_PART=1 the Hermite-Simpson wavefront solvers and the dispatch, 3 the trapezoidal
-// wavefront solvers, 4 the shooting solvers, the shooting Hessian-vector product and the shooting derivatives of the extragradient steps (closed-form and network), 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
+// wavefront solvers, 4 the shooting solvers, the shooting Hessian-vector products (closed-form and network) and the shooting derivatives of the extragradient steps (closed-form and network), 5 / 6 the lane kernels of the two collocation solvers, 2 everything else
 #if MYR_TU_PART == 1
 template int solve_hs_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
 template int solve_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const SolveCall&);
@@ -1371,6 +1410,7 @@ template int solve_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const Sol
 template int hvp_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const HvpArgs&);
 template int exgd_grad_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ExgdGradArgs&);
 template int exgd_grad_node_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const ExgdGradArgs&);
+template int hvp_node_shoot_for_system<myriad::MYR_TU_SYSTEM>(myr_handle, const HvpArgs&);
 #elif MYR_TU_PART == 5
 template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 0>(myr_handle, const SolveCall&);
 #elif MYR_TU_PART == 6
@@ -1384,6 +1424,7 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, 
   template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&);      \
   template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
   template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);          \
+  template int hvp_node_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
   template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
 MYR_SYSTEM_ENTRY_POINTS_REST(myriad::MYR_TU_SYSTEM)
 #endif
@@ -1398,7 +1439,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.8 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.9 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -2549,6 +2590,61 @@ extern "C" int myr_hvp(myr_handle h, int32_t B, const double* z, const double* l
   st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)dm.np);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_hvp(h, a, gp, p_stride)) return rc;
+  return st.finish();
+}
+
+// the product for the network system (node_hvp.h): device pointers throughout (for the batch sum a.rows is set here); out_p as in dispatch_hvp
+static int dispatch_hvp_node(myr_handle h, HvpArgs a, double* out_p, int p_stride) {
+  const myr_dims& dm = h->dims;
+  const bool shoot = h->d.transcription == MYR_TR_SHOOTING;
+  const int kt = shoot ? MYR_K_HVP_NODE_SHOOT : MYR_K_HVP_NODE;
+  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
+  if (out_p && p_stride) a.rows = out_p;
+  else if (out_p) st.scratch(a.rows, (size_t)a.B * dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = timed_begin(h, kt)) return rc;
+  const int rc = shoot ? hvp_node_shoot_for_system<SysNODE_CARTPOLE>(h, a) : hvp_node_colloc_for_system<SysNODE_CARTPOLE>(h, a);
+  if (!rc && out_p && !p_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, out_p);
+  const int rc_end = timed_end(h, kt);          // on every path
+  return rc ? rc : rc_end;
+}
+
+extern "C" int myr_hvp_node(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params, int32_t with_cost,
+                            double* out_z, double* out_p, int32_t p_stride, int32_t mem) {
+  const char* who = "myr_hvp_node";
+  if (!h || !z || !v) return fail(MYR_E_ARG, "myr_hvp_node: null handle, z or v");
+  if (!out_z && !out_p) return fail(MYR_E_ARG, "myr_hvp_node: both outputs are null");
+  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node: this handle's system is not the network system; use myr_hvp");
+  if (h->d.transcription != MYR_TR_HERMITE_SIMPSON && h->d.transcription != MYR_TR_SHOOTING)
+    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node: TRAPEZOIDAL is not built for the network system; HERMITE_SIMPSON and SHOOTING only");
+  if (int rc = check_node_weights(h, who, params)) return rc;
+  if (int rc = check_batch(who, B)) return rc;
+  if (p_stride != 0 && p_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_hvp_node: p_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_mem(who, mem)) return rc;
+  if (h->d.transcription == MYR_TR_SHOOTING) {
+    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_hvp_shoot_lds_bytes<2>(I, cpi) : node_hvp_shoot_lds_bytes<1>(I, cpi);
+    if (lds > 160 * 1024)
+      return fail(MYR_E_CAPACITY, "myr_hvp_node: intervals x controls_per_interval too large for the LDS-resident pair records beside the weight copy");
+  }
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n;
+  HvpArgs a{};
+  a.B = B; a.with_cost = with_cost != 0;
+  double* gp = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lam, lam, (size_t)B * dm.m);
+  st.in(a.v, v, nz);
+  st.in(a.params, params, (size_t)dm.np);
+  st.out(a.out_z, out_z, nz);
+  st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_hvp_node(h, a, gp, p_stride)) return rc;
   return st.finish();
 }
 

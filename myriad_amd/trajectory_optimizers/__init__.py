@@ -197,7 +197,12 @@ class TrajectoryOptimizer(object):
 
   def lagrangian_hessp(self, xs_and_us, lmbdas, v, params=None, with_cost=True):
     """(d2 lagrangian / dx dx) v, matrix-free and exact on the device (myr_hvp), for every transcription.  with_cost=False drops the objective:
-    sum_i lmbda_i (d2 c_i / dx dx) v, the `hess(x, v)` a SciPy NonlinearConstraint takes; lmbdas None with with_cost=True: the objective's Hessian."""
+    sum_i lmbda_i (d2 c_i / dx dx) v, the `hess(x, v)` a SciPy NonlinearConstraint takes; lmbdas None with with_cost=True: the objective's Hessian.
+    Over a NodeSystem `params` is the Haiku mapping of the weights (None: the system's own) and the product is myr_hvp_node's."""
+    if self.system.name == "NODE_CARTPOLE":
+      from myriad_amd.systems.neural_ode import flat_from_mapping
+      flat = self.system.device_params() if params is None else flat_from_mapping(params)
+      return self.engine.hvp_node(xs_and_us, lmbdas, v, flat, with_cost=with_cost)["hz"][0]
     p = self.system.device_params() if params is None else self.system.params_from_mapping(params)
     return self.engine.hvp(xs_and_us, lmbdas, v, params=p, with_cost=with_cost)["hz"][0]
 
