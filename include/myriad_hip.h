@@ -26,6 +26,10 @@
  *   jax.hessian / jax.jvp(jax.grad(lagrangian))  (no call site in the reference: the exact second derivative
  *                                                an external second-order method asks for)  myr_hvp
  *   ... of the network system                    (the same, in the 4 804 weights)                 myr_hvp_node
+ *   jax.grad(loss)(params, minibatch), one model per call
+ *                                                experiments/mle_sysid.py:89-136, neural_ode/node_training.py:31-61   myr_fit_grad
+ *   ... of many independent models at once (study_scripts.py:28-43 trains one per noise level, one after the
+ *                                                other; hp.num_experiments, seed sweeps)          myr_fit_grad_sets
  *
  * Conventions
  *   - all floating point is IEEE fp64 (the reference sets jax_enable_x64, run.py:15);
@@ -338,6 +342,29 @@ int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, const double*
 int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                  const double* wt, const double* params, int32_t params_stride,
                  double* loss, double* grad, int32_t grad_stride, int32_t mem);
+
+/*
+ * myr_fit_grad for E independent parameter sets (models) of R trajectories each, in one call (library version 0.10): ensembles over noise
+ * levels, seeds or initialisations of one architecture on data of one shape.
+ *   params [E][np], required (NODE: the 4 804 weights per set, in the order of csrc/node_system.h);
+ *   data_shared == 0: xs_obs [E][R][num_steps+1][ns], us [E][R][u_rows][nu];
+ *   data_shared == 1: xs_obs [R][num_steps+1][ns], us [R][u_rows][nu], read by every set (an ensemble over initialisations on one minibatch);
+ *   wt [num_steps+1] or NULL (= 1), shared by all sets; loss [E][R] or NULL;
+ *   grad [E][R][np] if grad_stride == np; [E][np] if grad_stride == 0: per set, the fixed-order sum over that set's R rows; NULL: the loss
+ *   only -- the reverse sweep is not run (validation and recorded losses).  loss and grad must not both be NULL.
+ * Contract: for every set e the outputs of set e have the bits of myr_fit_grad(h, R, ..., that set's data, wt, params + e * np, 0, ...,
+ * grad_stride, mem) on that set alone -- for MYR_MEM_HOST and MYR_MEM_DEVICE, on every call, whatever E is and whatever ran on the handle
+ * before.  The per-set sum runs in myr_fit_grad's order over the set's own row index, without atomics.
+ * When the rows behind the per-set sums (E * R * np doubles of scratch) would pass 1 GiB the call runs in chunks of whole sets, at least one
+ * set each, with the state scratch sized for one chunk; chunked and unchunked runs give the same bits.  MYRIAD_FIT_ROWS_BYTES, read at call
+ * time, lowers that bound (tests).  Timed on MYR_K_FIT.
+ * Errors, in this order: MYR_E_ARG -- a null h, xs_obs, us or params; loss and grad both NULL; E < 0, R < 1, num_steps < 1, u_rows < 1; a
+ * grad_stride other than 0 and np; a data_shared other than 0 and 1; a bad mem.  MYR_E_UNSUPPORTED, with myr_fit_grad's messages --
+ * INVASIVEPLANT, the elastic twins, systems without generated parameter derivatives.  E == 0 writes nothing and returns MYR_OK.
+ */
+int myr_fit_grad_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                      int32_t data_shared, const double* wt, const double* params, double* loss, double* grad, int32_t grad_stride,
+                      int32_t mem);
 
 /*
  * Derivative of `nsteps` extragradient steps (myr_exgd) in the model parameters, by one reverse sweep through the steps on the device

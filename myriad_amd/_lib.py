@@ -31,7 +31,7 @@ STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr
 EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
            "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
            "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp",
-           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot", "myr_hvp_node"]
+           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot", "myr_hvp_node", "myr_fit_grad_sets"]
 
 
 class ProblemDesc(C.Structure):
@@ -101,6 +101,8 @@ def load() -> C.CDLL:
   lib.myr_rollout.restype = C.c_int
   lib.myr_fit_grad.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
   lib.myr_fit_grad.restype = C.c_int
+  lib.myr_fit_grad_sets.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32]
+  lib.myr_fit_grad_sets.restype = C.c_int
   lib.myr_set_var_scale.argtypes = [vp, dp]
   lib.myr_set_var_scale.restype = C.c_int
   lib.myr_vjp.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32]
@@ -359,6 +361,36 @@ class Engine:
     """Zero-copy variant of fit_grad: every array is a device tensor on this handle's device."""
     _chk(self.lib.myr_fit_grad(self._h, int(B), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), _addr(wt), _addr(params),
                                int(params_stride), _addr(loss), _addr(grad), int(grad_stride), MEM_DEVICE), "myr_fit_grad")
+
+  def fit_grad_sets(self, xs_obs, us, params, wt=None, reduce=False, want_grad=True):
+    """myr_fit_grad_sets: fit_grad for E independent parameter sets of R trajectories each in one call.  params [E,np]; xs_obs [E,R,S+1,ns] and
+    us [E,R,u_rows,nu], or [R,S+1,ns] and [R,u_rows,nu]: one set of data that every parameter set reads; wt [S+1] (None: 1), shared by all sets.
+    Returns {"loss" [E,R], "grad" [E,R,np], or [E,np] = per set the sum over its trajectories with reduce=True}; want_grad=False: the loss only
+    (no reverse sweep, no "grad").  Set e has the bits of fit_grad on that set alone."""
+    xs_obs, us, params = _f64(xs_obs), _f64(us), _f64(params)
+    if params.ndim != 2 or params.shape[1] != self.np:
+      raise ValueError(f"params must be [E,{self.np}]")
+    E = params.shape[0]
+    if xs_obs.ndim not in (3, 4) or us.ndim != xs_obs.ndim:
+      raise ValueError("xs_obs and us must both be [E,R,...] (data per set) or both [R,...] (data shared by the sets)")
+    shared = xs_obs.ndim == 3
+    lead = () if shared else (E,)
+    R, S = xs_obs.shape[-3], xs_obs.shape[-2] - 1
+    if xs_obs.shape[:-3] != lead or xs_obs.shape[-1] != self.ns or S < 1 or R < 1:
+      raise ValueError(f"xs_obs must be [{'' if shared else 'E,'}R,S+1,{self.ns}] with R >= 1, S >= 1 and E = {E} as in params")
+    if us.shape[:-2] != lead + (R,) or us.shape[-1] != self.nu or us.shape[-2] < 1:
+      raise ValueError(f"us must be [{'' if shared else 'E,'}R,u_rows,{self.nu}]")
+    w = None if wt is None else _f64(wt, (S + 1,))
+    loss = np.empty((E, R))
+    grad = (np.empty((E, self.np)) if reduce else np.empty((E, R, self.np))) if want_grad else None
+    _chk(self.lib.myr_fit_grad_sets(self._h, E, R, S, int(us.shape[-2]), _addr(xs_obs), _addr(us), int(shared), _addr(w), _addr(params), _addr(loss),
+                                    _addr(grad), 0 if reduce else self.np, MEM_HOST), "myr_fit_grad_sets")
+    return {"loss": loss, "grad": grad} if want_grad else {"loss": loss}
+
+  def fit_grad_sets_device(self, E, R, num_steps, u_rows, xs_obs, us, params, grad=None, grad_stride=0, data_shared=False, wt=None, loss=None):
+    """Zero-copy variant of fit_grad_sets: every array is a device tensor on this handle's device; grad=None: the loss only."""
+    _chk(self.lib.myr_fit_grad_sets(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
+                                    _addr(params), _addr(loss), _addr(grad), int(grad_stride), MEM_DEVICE), "myr_fit_grad_sets")
 
   # ---- Lagrangian products / extragradient (collocation transcriptions) ------------------------
   def _batch2(self, a, width, name):

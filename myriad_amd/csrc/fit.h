@@ -89,9 +89,10 @@ struct FitLane {
 
   // xs_obs: [num_steps+1][NS] and us: [u_rows][NU] of this trajectory; wt: [num_steps+1] or null (= 1); p: the lane's parameter buffer.
   // xh: this lane's column of the state scratch, entry (t, i) at xh[(t * NS + i) * ld] (ld = padded batch on the device, 1 on the host).
-  // gp[NP] receives dl/dp; returns l.
+  // gp[NP] receives dl/dp; returns l.  want_grad == false (the same for every lane of a launch): the loss only, the reverse sweep is not run and
+  // gp is not written.
   MYR_HD static double run(int method, int num_steps, double h, int u_rows, const double* xs_obs, const double* us, const double* wt,
-                           const double* p, double* xh, long ld, double* gp) {
+                           const double* p, double* xh, long ld, double* gp, bool want_grad = true) {
     double x[NS], X[4][NS], Uc[4][NU], lam[NS];
     double loss = 0.0;
 #pragma unroll
@@ -111,6 +112,7 @@ struct FitLane {
       }
       loss += w * e;
     }
+    if (!want_grad) return loss;
 #pragma unroll
     for (int k = 0; k < NP; ++k) gp[k] = 0.0;
     {
@@ -159,25 +161,32 @@ struct FitLane {
 };
 
 #if defined(__HIPCC__)
-// One trajectory per lane.  The lanes of the last wavefront that have no trajectory redo the last one (the same loop trip counts and the
-// same branches for the whole wavefront) in a scratch column of their own; their stores of the results are masked.
+// One trajectory per lane: lane b of the launch is trajectory b mod R of parameter set b / R (B = E R lanes; myr_fit_grad is one set).  It reads
+// parameter row b / pdiv of `params` (pdiv = R: a row per set; pdiv = 1: a row per trajectory, myr_fit_grad with params_stride == np) and the data of
+// trajectory b, or of b mod R where every set reads the same R trajectories (data_shared).  Set boundaries fall inside wavefronts: a lane's arithmetic
+// depends on nothing but its own rows.  The lanes of the last wavefront that have no trajectory redo the last one, with its own set's parameters (the
+// same loop trip counts and the same branches for the whole wavefront), in a scratch column of their own; their stores of the results are masked.
+// grad == nullptr: the loss only.
 template <class Sys>
 __global__ __launch_bounds__(64)
-void fit_lane_kernel(int B, long Bp, int method, int num_steps, double h, int u_rows, const double* __restrict__ xs_obs,
-                     const double* __restrict__ us, const double* __restrict__ wt, const double* __restrict__ params, int params_stride,
-                     double* __restrict__ xh, double* __restrict__ loss, double* __restrict__ grad) {
+void fit_lane_kernel(int B, int R, int pdiv, int data_shared, long Bp, int method, int num_steps, double h, int u_rows,
+                     const double* __restrict__ xs_obs, const double* __restrict__ us, const double* __restrict__ wt,
+                     const double* __restrict__ params, double* __restrict__ xh, double* __restrict__ loss, double* __restrict__ grad) {
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;      // < Bp: the scratch has a column for every lane of the grid
   const bool live = b < B;
   const long bb = live ? b : (long)B - 1;
+  const long d = data_shared ? bb % R : bb;
   SysParams<Sys> pp;
-  pp.load(params, bb, params_stride);
+  pp.load(params, bb / pdiv, Sys::NP);
   double gp[Sys::NP];
-  const double l = FitLane<Sys>::run(method, num_steps, h, u_rows, xs_obs + bb * (long)(num_steps + 1) * Sys::NS, us + bb * (long)u_rows * Sys::NU,
-                                     wt, pp.get(), xh + b, Bp, gp);
+  const double l = FitLane<Sys>::run(method, num_steps, h, u_rows, xs_obs + d * (long)(num_steps + 1) * Sys::NS, us + d * (long)u_rows * Sys::NU,
+                                     wt, pp.get(), xh + b, Bp, gp, grad != nullptr);
   if (live) {
     if (loss) loss[b] = l;
+    if (grad) {
 #pragma unroll
-    for (int k = 0; k < Sys::NP; ++k) grad[b * Sys::NP + k] = gp[k];
+      for (int k = 0; k < Sys::NP; ++k) grad[b * Sys::NP + k] = gp[k];
+    }
   }
 }
 
@@ -261,22 +270,29 @@ struct NodeFit {
   }
 };
 
-// grid: ceil(B / WPB) workgroups of WPB wavefronts; xh: [num_steps+1][NS][Bp]; loss [B] or null; grad: [B][NP] rows.  (A template, so that only
-// the object that launches it holds its code.)
+// E weight sets of R trajectories each (myr_fit_grad: E = 1).  grid: E * ceil(R / WPB) workgroups of WPB wavefronts -- workgroup g serves set
+// g / ceil(R / WPB) alone, its LDS holds that set's weights, and its wavefront w takes row (g mod ceil(R / WPB)) WPB + w of the set.  params: [E][NP];
+// xs_obs, us: a trajectory per (set, row), or per row where every set reads the same R trajectories (data_shared); xh: [num_steps+1][NS][Bp], column
+// e R + r; loss [E][R] or null; grad: [E][R][NP] rows, or null: the loss only, the wavefront stops behind the forward rollout.  Every branch is
+// wave-uniform.  (A template, so that only the object that launches it holds its code.)
 template <class F>
 __global__ __launch_bounds__(64 * F::WPB)
-void node_fit_kernel(int B, long Bp, int method, int num_steps, double h, int u_rows, const double* __restrict__ xs_obs,
+void node_fit_kernel(int R, int data_shared, long Bp, int method, int num_steps, double h, int u_rows, const double* __restrict__ xs_obs,
                      const double* __restrict__ us, const double* __restrict__ wt, const double* __restrict__ params,
                      double* __restrict__ xh, double* __restrict__ loss, double* __restrict__ grad) {
   constexpr int NS = F::NS, NW = F::NW, H = F::H;
   __shared__ double wl[NodeMfma64::L_N];
-  NodeMfma64::load_weights(params, wl, threadIdx.x, 64 * F::WPB);
+  const int gps = (R + F::WPB - 1) / F::WPB;                     // workgroups per set
+  const int e = (int)(blockIdx.x / (unsigned)gps);
+  NodeMfma64::load_weights(params + (long)e * F::NP, wl, threadIdx.x, 64 * F::WPB);
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const long b = (long)blockIdx.x * F::WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (b >= B) return;                                            // a whole wavefront, behind the only barrier
-  const double* xo = xs_obs + b * (long)(num_steps + 1) * NS;
-  const double* ub = us + b * (long)u_rows;
+  const int r = (int)(blockIdx.x - (unsigned)e * (unsigned)gps) * F::WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (r >= R) return;                                            // a whole wavefront, behind the only barrier
+  const long b = (long)e * R + r;
+  const long d = data_shared ? (long)r : b;
+  const double* xo = xs_obs + d * (long)(num_steps + 1) * NS;
+  const double* ub = us + d * (long)u_rows;
   double* xc = xh + b;
   // per wavefront and stage: the stage point [x; u] (every lane writes the same values) and the two activation vectors.  Written and read by the
   // same wavefront only: no barrier
@@ -312,6 +328,10 @@ void node_fit_kernel(int B, long Bp, int method, int num_steps, double h, int u_
       e += d * d;
     }
     l += (wt ? wt[s + 1] : 1.0) * e;
+  }
+  if (!grad) {                                                   // (a kernel argument: the same for every wavefront)
+    if (loss) loss[b] = l;
+    return;
   }
   typename F::Acc g;
 #pragma unroll

@@ -325,8 +325,10 @@ struct SolveCall {
   double *lam, *cost; int32_t *status, *iters; double* kkt;      // each may be null
 };
 struct RolloutArgs { int B, num_steps, u_rows; const double *x0, *us, *params; int pstride; double *xs, *cost; };      // xs, cost may be null
-struct FitArgs {      // xh: [num_steps+1][NS][Bp] state scratch; loss [B] or null; grad [B][NP] rows
-  int B; long Bp; int num_steps, u_rows; const double *xs_obs, *us, *wt, *params; int pstride; double *xh, *loss, *grad;
+struct FitArgs {      // E parameter sets of R trajectories each (myr_fit_grad: E = 1, R = B).  xh: [num_steps+1][NS][Bp] state scratch; loss [E][R] or null;
+  // grad [E][R][NP] rows or null (the loss only); data_shared: xs_obs, us are [R][...], read by every set; params: [E][NP] (a closed-form system: may be
+  // null = the defaults), or with per_row -- myr_fit_grad with params_stride == np on a closed-form system, E = 1 -- [R][NP], a row per trajectory
+  int E, R, data_shared; long Bp; int num_steps, u_rows; const double *xs_obs, *us, *wt, *params; int per_row; double *xh, *loss, *grad;
 };
 struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of one chunk of `chunk` instances; seed_lam, dz0, dlam0 may be null
   int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
@@ -1139,15 +1141,17 @@ int rollout_for_system(myr_handle h, const RolloutArgs& a) {
 // ------------------------------------------------------------------------------------------------
 template <class Sys>
 int fit_for_system(myr_handle h, const FitArgs& a) {
-  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // shared weights only (myr_fit_grad has checked): one wavefront per trajectory
-    hipLaunchKernelGGL(node_fit_kernel<NodeFit>, dim3((unsigned)((a.B + NodeFit::WPB - 1) / NodeFit::WPB)), dim3(64 * NodeFit::WPB), 0, h->stream, a.B, a.Bp,
+  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // a set of weights per workgroup (never per trajectory: myr_fit_grad has checked), one wavefront per trajectory
+    const unsigned per_set = (unsigned)((a.R + NodeFit::WPB - 1) / NodeFit::WPB);
+    hipLaunchKernelGGL(node_fit_kernel<NodeFit>, dim3((unsigned)a.E * per_set), dim3(64 * NodeFit::WPB), 0, h->stream, a.R, a.data_shared, a.Bp,
                        (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.xh, a.loss, a.grad);
     return MYR_OK;
   } else if constexpr (!SysDp<Sys>::SUPPORTED) {
     return fail(MYR_E_UNSUPPORTED, std::string("myr_fit_grad: no parameter derivatives are generated for ") + Sys::NAME);
   } else {
-    hipLaunchKernelGGL(fit_lane_kernel<Sys>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, h->stream, a.B, a.Bp, (int)h->d.integration_method, a.num_steps,
-                       h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.pstride, a.xh, a.loss, a.grad);
+    const long B = (long)a.E * a.R;
+    hipLaunchKernelGGL(fit_lane_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, (int)B, a.R, a.per_row ? 1 : a.R, a.data_shared, a.Bp,
+                       (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.xh, a.loss, a.grad);
     return MYR_OK;
   }
 }
@@ -1439,7 +1443,7 @@ MYR_SYSTEM_ENTRY_POINTS(extern, SysNODE_CARTPOLE)
 
 #if !defined(MYR_TU_SYSTEM)   // ===== C-ABI and dispatch: the main object only ============================================
 extern "C" const char* myr_last_error(void) { return g_err.c_str(); }
-extern "C" const char* myr_version(void) { return "myriad_hip 0.9 (gfx950)"; }
+extern "C" const char* myr_version(void) { return "myriad_hip 0.10 (gfx950)"; }
 extern "C" int32_t myr_abi_sizeof(int32_t which) {
   switch (which) {
     case 0: return (int32_t)sizeof(myr_solve_opts);
@@ -2314,26 +2318,76 @@ static __global__ __launch_bounds__(256) void fit_reduce_kernel(int B, int np, c
   if (t == 0) out[k] = part[0];
 }
 
+// the same sum for each of E parameter sets of R rows (rows [E][R][np] -> out [E][np]): block (k, e) is fit_reduce_kernel's block k on the rows of set e
+// alone -- thread t adds rows t, t + 256, ... of that set, then the same tree --, so a set's sums have the bits of a call on that set alone.  Grid: np * E.
+static __global__ __launch_bounds__(256) void fit_reduce_sets_kernel(int R, int np, const double* __restrict__ rows, double* __restrict__ out) {
+  __shared__ double part[256];
+  const int k = (int)(blockIdx.x % (unsigned)np), t = threadIdx.x;
+  const long e = blockIdx.x / (unsigned)np;
+  rows += e * (long)R * np;
+  double a = 0.0;
+  for (long b = t; b < R; b += 256) a += rows[b * np + k];
+  part[t] = a;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) part[t] += part[t + w];
+    __syncthreads();
+  }
+  if (t == 0) out[e * np + k] = part[0];
+}
+
 static bool fit_supported(int id) {
   return for_system(id, true, [](auto t) { using S = SYS_OF(t); return std::is_same<S, SysNODE_CARTPOLE>::value || SysDp<S>::SUPPORTED; }, [] { return false; });
 }
 static bool sys_known(int id) { SysInfo si; return sys_info(id, &si); }
 
-// device pointers throughout (a.Bp, a.xh are set here); a.grad: [B][np] rows (grad_stride == np) or the [np] sum over the batch (grad_stride == 0, rows in sbuf)
+// parameter sets one launch of dispatch_fit takes: all of them, unless the per-set sums are asked for and the row scratch (E R np doubles) would pass
+// 1 GiB -- then whole sets, at least one; and never more than 2^30 trajectories (the kernels count them in an int)
+static int fit_sets_chunk(myr_handle h, int E, int R, bool row_scratch) {
+  size_t chunk = (size_t)E;
+  if (row_scratch) {
+    size_t bound = (size_t)1 << 30;
+    if (const char* e = getenv("MYRIAD_FIT_ROWS_BYTES")) { const long long v = atoll(e); if (v > 0) bound = (size_t)v; }      // tests: force the chunked path
+    chunk = bound / ((size_t)R * (size_t)(h->dims.np > 0 ? h->dims.np : 1) * 8);
+  }
+  const size_t cap = ((size_t)1 << 30) / (size_t)R;
+  if (chunk > cap) chunk = cap;
+  return (int)(chunk < 1 ? 1 : (chunk > (size_t)E ? (size_t)E : chunk));
+}
+
+// device pointers throughout (a.Bp, a.xh are set here); a.grad: [E][R][np] rows (grad_stride == np), the [E][np] per-set sums (grad_stride == 0, rows in
+// sbuf) or null (the loss only).  The sets run in chunks of fit_sets_chunk (launches on one stream: a chunk starts when the one before has ended); a
+// trajectory's arithmetic does not depend on the chunk it runs in
 static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
   const myr_dims& dm = h->dims;
-  double* const sum = a.grad;
-  a.Bp = padded_lanes(a.B);
-  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
-  st.scratch(a.xh, (size_t)(a.num_steps + 1) * dm.ns * (size_t)a.Bp);
-  if (!grad_stride) st.scratch(a.grad, (size_t)a.B * dm.np);
-  if (int rc = st.commit()) return rc;
-  if (!fit_supported(h->d.system_id))                  // refused before the timer starts: begin and end stay paired
+  if (!fit_supported(h->d.system_id))                  // refused before anything is sized by the system's np, and before the timer starts: begin and end stay paired
     return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
                                      : no_such_path(h, "myr_fit_grad");
+  const bool sums = a.grad && !grad_stride;
+  const int E = a.E, chunk = fit_sets_chunk(h, E, a.R, sums);
+  const size_t S1 = (size_t)a.num_steps + 1;
+  const double *xs_obs = a.xs_obs, *us = a.us, *params = a.params;
+  double *const loss = a.loss, *const out = a.grad, *rows = nullptr;
+  a.Bp = padded_lanes((int)((long)chunk * a.R));
+  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
+  st.scratch(a.xh, S1 * dm.ns * (size_t)a.Bp);
+  if (sums) st.scratch(rows, (size_t)chunk * a.R * dm.np);
+  if (int rc = st.commit()) return rc;
   if (int rc = timed_begin(h, MYR_K_FIT)) return rc;
-  const int rc = for_system(h->d.system_id, true, [&](auto t) { return fit_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
-  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.grad, sum);
+  int rc = MYR_OK;
+  for (int e0 = 0; e0 < E && !rc; e0 += chunk) {
+    const size_t r0 = (size_t)e0 * a.R, d0 = a.data_shared ? 0 : r0;
+    a.E = E - e0 < chunk ? E - e0 : chunk;
+    a.xs_obs = xs_obs + d0 * S1 * dm.ns;
+    a.us = us + d0 * a.u_rows * dm.nu;
+    a.params = params ? params + (size_t)e0 * dm.np : nullptr;      // (per_row: one set, e0 = 0)
+    a.loss = loss ? loss + r0 : nullptr;
+    a.grad = sums ? rows : (out ? out + r0 * dm.np : nullptr);
+    rc = for_system(h->d.system_id, true, [&](auto t) { return fit_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+    if (!rc && sums)
+      hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)dm.np * (unsigned)a.E), dim3(256), 0, h->stream, a.R, (int)dm.np, (const double*)rows,
+                         out + (size_t)e0 * dm.np);
+  }
   const int rc_end = timed_end(h, MYR_K_FIT);          // on every path
   return rc ? rc : rc_end;
 }
@@ -2356,7 +2410,7 @@ extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t 
   if (B == 0) return MYR_OK;                          // (nothing is written)
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
-  FitArgs a{B, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, params_stride, nullptr, nullptr, nullptr};
+  FitArgs a{1, B, 0, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, params && params_stride != 0, nullptr, nullptr, nullptr};      // one set
   DevStage st = call_stage(h, mem);
   st.in(a.xs_obs, xs_obs, (size_t)B * (num_steps + 1) * dm.ns);
   st.in(a.us, us, (size_t)B * u_rows * dm.nu);
@@ -2364,6 +2418,39 @@ extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t 
   st.in(a.params, params, n_params(h, params, params_stride, B));
   st.out(a.loss, loss, (size_t)B);
   st.out(a.grad, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_fit(h, a, grad_stride)) return rc;
+  return st.finish();
+}
+
+extern "C" int myr_fit_grad_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                                 int32_t data_shared, const double* wt, const double* params, double* loss, double* grad, int32_t grad_stride,
+                                 int32_t mem) {
+  const char* who = "myr_fit_grad_sets";
+  if (!h || !xs_obs || !us || !params) return fail(MYR_E_ARG, "myr_fit_grad_sets: null handle, xs_obs, us or params");
+  if (!loss && !grad) return fail(MYR_E_ARG, "myr_fit_grad_sets: loss and grad are both null");
+  if (E < 0 || R < 1 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_grad_sets: bad sizes");
+  if (grad_stride != 0 && grad_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_fit_grad_sets: grad_stride must be 0 (a row per set: the sum over its trajectories) or np (a row per trajectory)");
+  if (data_shared != 0 && data_shared != 1) return fail(MYR_E_ARG, "myr_fit_grad_sets: data_shared must be 0 (data per set) or 1 (one set of data, read by every set)");
+  if (int rc = check_mem(who, mem)) return rc;
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
+  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
+  if (!fit_supported(h->d.system_id))
+    return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
+                                     : no_such_path(h, who);
+  if (E == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t rows = (size_t)E * R, drows = data_shared ? (size_t)R : rows;
+  FitArgs a{E, R, data_shared, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+  DevStage st = call_stage(h, mem);
+  st.in(a.xs_obs, xs_obs, drows * (num_steps + 1) * dm.ns);
+  st.in(a.us, us, drows * u_rows * dm.nu);
+  st.in(a.wt, wt, (size_t)num_steps + 1);
+  st.in(a.params, params, (size_t)E * dm.np);
+  st.out(a.loss, loss, rows);
+  st.out(a.grad, grad, grad_stride ? rows * dm.np : (size_t)E * dm.np);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_fit(h, a, grad_stride)) return rc;
   return st.finish();

@@ -60,6 +60,25 @@ class FitLoss:
   def __call__(self, params, dataset, epoch=0) -> float:
     return self.value_and_grad(params, dataset, epoch)[0]
 
+  def values_and_grads(self, params_sets, datasets, epoch=0, want_grad=True):
+    """value_and_grad for E parameter mappings at once (one myr_fit_grad_sets call): datasets [E,M,S+1,ns+nu], or [M,S+1,ns+nu] read by every
+    set.  The sign rule of split_params applies per set.  Returns (values: E floats, grads: E mappings); want_grad=False: (values, None), no
+    reverse sweep.  Entry e is value_and_grad(params_sets[e], datasets[e], epoch) to the bit."""
+    ns = self.hp.state_size
+    datasets = np.asarray(datasets, dtype=np.float64)
+    split = [split_params(self.system, params) for params in params_sets]
+    out = self.engine.fit_grad_sets(datasets[..., :ns], datasets[..., ns:], np.stack([p for p, _ in split]),
+                                    wt=loss_weights(self.hp, datasets.shape[-3], epoch), reduce=True, want_grad=want_grad)
+    values = [float(row.sum()) for row in out["loss"]]
+    if not want_grad:
+      return values, None
+    names = self.system.param_names
+    grads = []
+    for params, (_, sign), row in zip(params_sets, split, out["grad"]):
+      g = row * sign
+      grads.append({k: float(g[names.index(k)]) for k in params})
+    return values, grads
+
 
 class Adam:
   """optax.adam(lr) with its defaults b1 = 0.9, b2 = 0.999, eps = 1e-8, eps_root = 0, on a mapping of floats."""
@@ -114,3 +133,50 @@ def run_mle_sysid(hp: HParams, cfg: Config, dataset=None, num_updates: Optional[
     params = opt.update(params, grads)
   fit.engine.close()
   return {"params": best_params, "last_params": params, "epochs": epochs, "train_losses": train_losses, "val_losses": val_losses}
+
+
+def run_mle_sysid_sets(hp: HParams, cfg: Config, datasets, guesses=None, num_updates: Optional[int] = None, check_frequency: int = 500) -> list:
+  """run_mle_sysid for E datasets [E][train+val+test][S+1][ns+nu] at once (noise levels, seeds; `guesses`: E starting mappings, default
+  defaults.param_guesses[hp.system] for every set): the fits run in lockstep, every update of all of them in one myr_fit_grad_sets call.  Each set has
+  its own Adam state, best parameters and early-stop counter, and leaves the later calls once it has stopped.  Returns E dictionaries; entry e is
+  what run_mle_sysid(hp, cfg, datasets[e]) returns (from guesses[e]): the same arithmetic, equal values."""
+  datasets = np.asarray(datasets, dtype=np.float64)
+  E = datasets.shape[0]
+  train_sets, val_sets = datasets[:, :hp.train_size], datasets[:, hp.train_size:-hp.test_size]
+  fit = FitLoss(hp)
+  params = [dict(param_guesses[hp.system] if guesses is None else guesses[e]) for e in range(E)]
+  opts = [Adam(1e-3) for _ in range(E)]
+  out = [{"params": None, "last_params": None, "epochs": [], "train_losses": [], "val_losses": []} for _ in range(E)]
+  best_val_loss, count = [None] * E, [0] * E
+  live = list(range(E))
+  for epoch in range(hp.num_epochs * 10 if num_updates is None else num_updates):
+    if not live:
+      break
+    if epoch % check_frequency == 0:
+      cur = [params[e] for e in live]
+      cur_losses = fit.values_and_grads(cur, train_sets[live], epoch, want_grad=False)[0]
+      val_losses = fit.values_and_grads(cur, val_sets[live], epoch, want_grad=False)[0]
+      for e, cur_loss, val_loss in zip(list(live), cur_losses, val_losses):
+        o = out[e]
+        o["epochs"].append(epoch); o["train_losses"].append(cur_loss); o["val_losses"].append(val_loss)
+        if cfg.verbose:
+          print(e, "loss", cur_loss, "val loss", val_loss)
+        if np.isnan(cur_loss):
+          raise FloatingPointError(f"mle_sysid: the loss of set {e} is NaN at params {params[e]}")
+        if best_val_loss[e] is None or val_loss < best_val_loss[e]:
+          best_val_loss[e], o["params"], count[e] = val_loss, dict(params[e]), 0
+        elif count[e] > hp.early_stop_threshold:
+          if cfg.verbose:
+            print(e, "stopping early at epoch", epoch)
+          live.remove(e)
+          continue
+        count[e] += check_frequency
+      if not live:
+        break
+    _, grads = fit.values_and_grads([params[e] for e in live], train_sets[live], epoch)
+    for e, g in zip(live, grads):
+      params[e] = opts[e].update(params[e], g)
+  fit.engine.close()
+  for e in range(E):
+    out[e]["last_params"] = params[e]
+  return out
