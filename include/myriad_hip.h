@@ -30,6 +30,8 @@
  *                                                experiments/mle_sysid.py:89-136, neural_ode/node_training.py:31-61   myr_fit_grad
  *   ... of many independent models at once (study_scripts.py:28-43 trains one per noise level, one after the
  *                                                other; hp.num_experiments, seed sweeps)          myr_fit_grad_sets
+ *   many_steps_grad / the Lagrangian Hessian product of many independent networks at once (the reference's
+ *                                                node_e2e_sysid.py loop trains one)               myr_exgd_grad_node_sets, myr_hvp_node_sets
  *
  * Conventions
  *   - all floating point is IEEE fp64 (the reference sets jax_enable_x64, run.py:15);
@@ -484,6 +486,38 @@ int myr_hvp(myr_handle h, int32_t B, const double* z, const double* lam, const d
  */
 int myr_hvp_node(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params,
                  int32_t with_cost, double* out_z, double* out_p, int32_t p_stride, int32_t mem);
+
+/*
+ * myr_exgd_grad_node / myr_exgd_grad_node_shoot for E independent weight sets of R instances each in ONE call (an ensemble of networks that
+ * differ in seed, noise level or learning rate: E launches of one workgroup each become one launch of E R workgroups).  Served on a
+ * MYR_SYS_NODE_CARTPOLE handle under MYR_TR_HERMITE_SIMPSON and MYR_TR_SHOOTING alike: the call dispatches on the handle's transcription.
+ *   params [E][np]: the weight sets, required; every per-instance array is [E][R][...], instance (e, r) is row e R + r: z, lb, ub, seed_z,
+ *   dz0 [E][R][n]; lam, seed_lam, dlam0 [E][R][m]; grad [E][R][np] if grad_stride == np, [E][np] if grad_stride == 0: row e is the fixed-order sum
+ *   over the R rows of set e.  seed_lam, dz0, dlam0 may be NULL.  Inputs are not modified; E == 0 writes nothing.
+ * For every set e the outputs of set e have the BITS of the single-set call on that set alone (B = R, params + e np, the same stride and
+ * mem): for MYR_MEM_HOST and MYR_MEM_DEVICE, on every call, whatever E is and whatever ran on the handle before, with the history in one chunk
+ * or in many (a chunk of instances may begin and end inside a set).  The two single-set calls are the E = 1, R = B case of this one.
+ * MYR_E_ARG: null h / z / lam / lb / ub / seed_z / grad / params, E < 0, R < 1, E R past the int range, negative nsteps, a grad_stride other
+ * than 0 and np, a bad mem; MYR_E_UNSUPPORTED (before the size checks): a handle whose system is not MYR_SYS_NODE_CARTPOLE, MYR_TR_TRAPEZOIDAL;
+ * MYR_E_CAPACITY: the LDS bounds of the single-set call of the handle's transcription, unchanged.
+ */
+int myr_exgd_grad_node_sets(myr_handle h, int32_t E, int32_t R, const double* z, const double* lam, const double* lb, const double* ub,
+                            const double* params, double eta_x, double eta_v, int32_t nsteps,
+                            const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
+                            double* dz0, double* dlam0, int32_t mem);
+
+/*
+ * myr_hvp_node for E independent weight sets of R instances each in one call, under MYR_TR_HERMITE_SIMPSON or MYR_TR_SHOOTING.
+ *   params [E][np], required; z, v, out_z [E][R][n]; lam [E][R][m] or NULL (= 0); out_p [E][R][np] if p_stride == np, [E][np] if p_stride == 0
+ *   (row e: the fixed-order sum over the R rows of set e), or NULL -- out_z and out_p not both NULL.  E == 0 writes nothing.
+ * For every set e the outputs of set e have the bits of myr_hvp_node on that set alone (B = R, params + e np, the same stride and mem), for
+ * MYR_MEM_HOST and MYR_MEM_DEVICE, on every call.  myr_hvp_node is the E = 1, R = B case of this call.
+ * MYR_E_ARG: null h / z / v / params, both outputs NULL, E < 0, R < 1, E R past the int range, a p_stride other than 0 and np, a bad mem;
+ * MYR_E_UNSUPPORTED (before the size checks): a handle whose system is not MYR_SYS_NODE_CARTPOLE, MYR_TR_TRAPEZOIDAL;
+ * MYR_E_CAPACITY (SHOOTING only): myr_hvp_node's LDS bound, unchanged.
+ */
+int myr_hvp_node_sets(myr_handle h, int32_t E, int32_t R, const double* z, const double* lam, const double* v, const double* params,
+                      int32_t with_cost, double* out_z, double* out_p, int32_t p_stride, int32_t mem);
 
 /* Average device time (HIP events on the handle's stream) of the launches of one kernel since the last reset. */
 int myr_kernel_time(myr_handle h, int32_t kernel_id, double* avg_ms, int32_t* launches);

@@ -31,7 +31,8 @@ STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr
 EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
            "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
            "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp",
-           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot", "myr_hvp_node", "myr_fit_grad_sets"]
+           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot", "myr_hvp_node", "myr_fit_grad_sets",
+           "myr_exgd_grad_node_sets", "myr_hvp_node_sets"]
 
 
 class ProblemDesc(C.Structure):
@@ -123,6 +124,11 @@ def load() -> C.CDLL:
   lib.myr_hvp.restype = C.c_int
   lib.myr_hvp_node.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
   lib.myr_hvp_node.restype = C.c_int
+  lib.myr_exgd_grad_node_sets.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp,
+                                          C.c_int32]
+  lib.myr_exgd_grad_node_sets.restype = C.c_int
+  lib.myr_hvp_node_sets.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
+  lib.myr_hvp_node_sets.restype = C.c_int
   lib.myr_fbsm.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_double, C.c_double, C.c_int32,
                            dp, dp, dp, ip, C.c_int32]
   lib.myr_fbsm.restype = C.c_int
@@ -532,6 +538,92 @@ class Engine:
                                   dlam0=None):
     self.exgd_grad_node_device(B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam, dz0, dlam0,
                                _call="myr_exgd_grad_node_shoot")
+
+  # ---- E weight sets of R instances each in one call (myr_exgd_grad_node_sets, myr_hvp_node_sets) --------------------------
+  def _sets3(self, a, E, R, width, name):
+    a = _f64(a)
+    if a.shape != (E, R, width):
+      raise ValueError(f"{name} must be [E = {E}, R = {R}, {width}]")
+    return a
+
+  def _weight_sets(self, params):
+    p = np.ascontiguousarray(_f64(params))
+    if p.ndim != 2 or p.shape[1] != self.np:
+      raise ValueError(f"params must be [E,{self.np}]: a weight set per row")
+    return p
+
+  def exgd_grad_node_sets(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
+    """myr_exgd_grad_node_sets: exgd_grad_node (exgd_grad_node_shoot on a SHOOTING handle) for E weight sets of R instances each in one call.
+    params [E,np]; z [E,R,n], lam [E,R,m]; lb, ub, seed_z broadcast to z, seed_lam (None: zero) to lam.  Returns {"grad" [E,R,np], or [E,np] =
+    per set the sum over its instances with reduce=True, "dz0" [E,R,n], "dlam0" [E,R,m]} (the last two with want_start).  Set e has the bits of
+    the single-set call on that set alone."""
+    p = self._weight_sets(params)
+    E = p.shape[0]
+    z = _f64(z)
+    if z.ndim != 3 or z.shape[0] != E or z.shape[1] < 1 or z.shape[2] != self.n:
+      raise ValueError(f"z must be [E = {E}, R, {self.n}] with R >= 1")
+    R = z.shape[1]
+    lam = self._sets3(lam, E, R, self.m, "lam")
+    lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), z.shape))
+    ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), z.shape))
+    sz = np.ascontiguousarray(np.broadcast_to(_f64(seed_z), z.shape))
+    sl = None if seed_lam is None else np.ascontiguousarray(np.broadcast_to(_f64(seed_lam), lam.shape))
+    grad = np.empty((E, self.np)) if reduce else np.empty((E, R, self.np))
+    dz0 = np.empty((E, R, self.n)) if want_start else None
+    dlam0 = np.empty((E, R, self.m)) if want_start else None
+    _chk(self.lib.myr_exgd_grad_node_sets(self._h, E, R, _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(p), float(eta_x), float(eta_v), int(nsteps),
+                                          _addr(sz), _addr(sl), _addr(grad), 0 if reduce else self.np, _addr(dz0), _addr(dlam0), MEM_HOST),
+         "myr_exgd_grad_node_sets")
+    out = {"grad": grad}
+    if want_start:
+      out["dz0"] = dz0; out["dlam0"] = dlam0
+    return out
+
+  def exgd_grad_node_sets_device(self, E, R, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None,
+                                 dlam0=None):
+    """Zero-copy variant of exgd_grad_node_sets: every array is a device tensor on this handle's device."""
+    _chk(self.lib.myr_exgd_grad_node_sets(self._h, int(E), int(R), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), float(eta_x), float(eta_v),
+                                          int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
+                                          MEM_DEVICE), "myr_exgd_grad_node_sets")
+
+  def exgd_grad_node_sets_probe(self):
+    """Raises the library's error when myr_exgd_grad_node_sets is not built for this handle (no sets: the checks run, nothing else)."""
+    d = np.zeros(1)
+    _chk(self.lib.myr_exgd_grad_node_sets(self._h, 0, 1, _addr(d), _addr(d), _addr(d), _addr(d), _addr(d), 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None,
+                                          None, MEM_HOST), "myr_exgd_grad_node_sets")
+
+  def hvp_node_sets(self, z, lam, v, params, with_cost=True, want_z=True, want_p=False, reduce=False):
+    """myr_hvp_node_sets: hvp_node for E weight sets of R instances each in one call.  params [E,np]; z, v [E,R,n]; lam [E,R,m] or None (zero
+    multipliers).  Returns {"hz" [E,R,n] (with want_z), "hp" [E,R,np], or [E,np] = per set the sum over its instances with reduce=True (with
+    want_p)}.  Set e has the bits of hvp_node on that set alone."""
+    p = self._weight_sets(params)
+    E = p.shape[0]
+    z = _f64(z)
+    if z.ndim != 3 or z.shape[0] != E or z.shape[1] < 1 or z.shape[2] != self.n:
+      raise ValueError(f"z must be [E = {E}, R, {self.n}] with R >= 1")
+    R = z.shape[1]
+    v = self._sets3(v, E, R, self.n, "v")
+    lam = None if lam is None else self._sets3(lam, E, R, self.m, "lam")
+    hz = np.empty((E, R, self.n)) if want_z else None
+    hp = (np.empty((E, self.np)) if reduce else np.empty((E, R, self.np))) if want_p else None
+    _chk(self.lib.myr_hvp_node_sets(self._h, E, R, _addr(z), _addr(lam), _addr(v), _addr(p), int(bool(with_cost)), _addr(hz), _addr(hp),
+                                    0 if reduce else self.np, MEM_HOST), "myr_hvp_node_sets")
+    out = {}
+    if want_z:
+      out["hz"] = hz
+    if want_p:
+      out["hp"] = hp
+    return out
+
+  def hvp_node_sets_device(self, E, R, z, lam, v, params, out_z=None, out_p=None, p_stride=0, with_cost=True):
+    """Zero-copy variant of hvp_node_sets: every array is a device tensor on this handle's device (lam, out_z, out_p may be None)."""
+    _chk(self.lib.myr_hvp_node_sets(self._h, int(E), int(R), _addr(z), _addr(lam), _addr(v), _addr(params), int(bool(with_cost)), _addr(out_z),
+                                    _addr(out_p), int(p_stride), MEM_DEVICE), "myr_hvp_node_sets")
+
+  def hvp_node_sets_probe(self):
+    """Raises the library's error when myr_hvp_node_sets is not built for this handle (no sets: the checks run, nothing else)."""
+    d = np.zeros(1)
+    _chk(self.lib.myr_hvp_node_sets(self._h, 0, 1, _addr(d), None, _addr(d), _addr(d), 1, _addr(d), None, 0, MEM_HOST), "myr_hvp_node_sets")
 
   def hvp(self, z, lam, v, params=None, with_cost=True, want_z=True, want_p=False, reduce=False):
     """myr_hvp: Lagrangian Hessian-vector product.  With L = f + lam^T c (f dropped when with_cost is false) and psi = <grad_z L, v>:

@@ -334,9 +334,11 @@ struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of 
   int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
   double *rows, *dz0, *dlam0, *hist; int chunk;
   double* work; long Pp;      // SHOOTING (closed form) only: the scratch of one chunk (launch_shoot_exgd_grad carves it) and its pair columns
+  int R, inst0;               // R: instances to a weight set (the network routes: params [B / R][NP], pstride 0; else B); inst0: the chunk's first instance
 };
 struct HvpArgs {      // lam, out_z, rows ([B][NP] parameter rows) may be null; hist, side: shooting scratch, batch-minor with Pp columns (one per pair)
   int B; const double *z, *lam, *v, *params; int pstride, with_cost; double *out_z, *rows, *hist, *side; long Pp;
+  int R;                      // myr_hvp_node*: instances to a weight set (params [B / R][NP])
 };
 struct FbsmArgs {      // X, A [N+1][NS][Bp], U [N+1 | N][NU][Bp]: batch-minor
   int B; long Bp; int N; const double *x0, *adjT, *params; int pstride; VarScale lo, hi; double bang, delta; int max_sweeps;
@@ -1160,7 +1162,9 @@ int fit_for_system(myr_handle h, const FitArgs& a) {
 // derivative of the unrolled extragradient steps in the model parameters (exgd_grad.h: colloc_exgd_grad_kernel)
 // ------------------------------------------------------------------------------------------------
 // The batch in chunks of a.chunk instances that share one history buffer (launches on one stream: a chunk starts when the one before has ended).
-// `launch` gets the chunk's record: B its instances, every batch pointer at its first one (null stays null; params advances by pstride)
+// `launch` gets the chunk's record: B its instances, inst0 the number of its first one in the call, every batch pointer at that instance (null stays
+// null; params advances by pstride -- the network routes pass pstride 0 and find an instance's weight set from inst0 and R: blockIdx.x restarts at 0
+// in every chunk, and a chunk may begin and end inside a set)
 template <class F>
 static int for_exgd_grad_chunks(myr_handle h, const ExgdGradArgs& a, F launch) {
   const myr_dims& dm = h->dims;
@@ -1168,6 +1172,7 @@ static int for_exgd_grad_chunks(myr_handle h, const ExgdGradArgs& a, F launch) {
     auto at = [b0](auto* p, long stride) { return p ? p + b0 * stride : nullptr; };
     ExgdGradArgs c = a;
     c.B = (int)(a.B - b0 < a.chunk ? a.B - b0 : a.chunk);
+    c.inst0 = (int)b0;
     c.z = at(a.z, dm.n); c.lam = at(a.lam, dm.m); c.lb = at(a.lb, dm.n); c.ub = at(a.ub, dm.n); c.params = at(a.params, a.pstride);
     c.seed_z = at(a.seed_z, dm.n); c.seed_lam = at(a.seed_lam, dm.m);
     c.rows = at(a.rows, dm.np); c.dz0 = at(a.dz0, dm.n); c.dlam0 = at(a.dlam0, dm.m);
@@ -1208,9 +1213,9 @@ static int launch_node_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
   const size_t lds = node_exgd_grad_lds_bytes(N);
   auto kern = node_exgd_grad_kernel<WPI>;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  return for_exgd_grad_chunks(h, a, [&](const ExgdGradArgs& c) {      // (params: the one shared weight set, pstride 0)
+  return for_exgd_grad_chunks(h, a, [&](const ExgdGradArgs& c) {      // (params: the call's weight sets, pstride 0)
     hipLaunchKernelGGL(kern, dim3((unsigned)c.B), dim3(64 * WPI), lds, h->stream, c.B, N, h->d.T / N, c.z, c.lam, c.lb, c.ub, c.params, c.eta_x, c.eta_v,
-                       c.nsteps, c.seed_z, c.seed_lam, c.hist, c.rows, c.dz0, c.dlam0);
+                       c.nsteps, c.seed_z, c.seed_lam, c.hist, c.rows, c.dz0, c.dlam0, c.inst0, c.R);
     return (int)MYR_OK;
   });
 }
@@ -1333,7 +1338,7 @@ static int launch_node_shoot_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   return for_exgd_grad_chunks(h, a, [&](const ExgdGradArgs& c) {
     NseArgs k{};
-    k.B = c.B; k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.nsteps = c.nsteps;
+    k.B = c.B; k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.nsteps = c.nsteps; k.inst0 = c.inst0; k.R = c.R;
     k.T = h->d.T; k.eta_x = c.eta_x; k.eta_v = c.eta_v;
     k.z = c.z; k.lam = c.lam; k.lb = c.lb; k.ub = c.ub; k.params = c.params; k.seed_z = c.seed_z; k.seed_lam = c.seed_lam;
     k.hist = c.hist; k.grad = c.rows; k.dz0 = c.dz0; k.dlam0 = c.dlam0;
@@ -1351,7 +1356,7 @@ int exgd_grad_node_shoot_for_system(myr_handle h, const ExgdGradArgs& a) {
 
 // ------------------------------------------------------------------------------------------------
 // Lagrangian Hessian-vector product of the network system (node_hvp.h: node_hvp_colloc_kernel, node_hvp_shoot_kernel; myr_hvp_node has checked
-// system, transcription and that the SHOOTING carve fits).  One weight set: a.params [np], a.pstride is not read
+// system, transcription and that the SHOOTING carve fits).  a.params [B / R][np]: a weight set for every R instances; a.pstride is not read
 // ------------------------------------------------------------------------------------------------
 template <class Sys>
 int hvp_node_colloc_for_system(myr_handle h, const HvpArgs& a) {
@@ -1359,7 +1364,7 @@ int hvp_node_colloc_for_system(myr_handle h, const HvpArgs& a) {
     constexpr int WPI = 4;
     const int N = h->d.intervals;
     hipLaunchKernelGGL(node_hvp_colloc_kernel<WPI>, dim3((unsigned)a.B), dim3(64 * WPI), node_hvp_colloc_lds_bytes(), h->stream, a.B, N, h->d.T / N, a.z,
-                       a.lam, a.v, a.params, a.with_cost, a.out_z, a.rows);
+                       a.lam, a.v, a.params, a.with_cost, a.out_z, a.rows, a.R);
     return MYR_OK;
   }
   return fail(MYR_E_UNSUPPORTED, "myr_hvp_node: the network system only; use myr_hvp");
@@ -1372,7 +1377,7 @@ static int launch_node_hvp_shoot(myr_handle h, const HvpArgs& a) {
   auto kern = node_hvp_shoot_kernel<M>;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   NodeHvpArgs k{};
-  k.B = a.B; k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.with_cost = a.with_cost; k.T = h->d.T;
+  k.B = a.B; k.I = I; k.cpi = cpi; k.method = (int)h->d.integration_method; k.with_cost = a.with_cost; k.R = a.R; k.T = h->d.T;
   k.z = a.z; k.lam = a.lam; k.v = a.v; k.params = a.params; k.out_z = a.out_z; k.rows = a.rows;
   hipLaunchKernelGGL(kern, dim3((unsigned)k.B), dim3(64 * node_hvp_shoot_wpi(I)), lds, h->stream, k);
   return MYR_OK;
@@ -2468,7 +2473,8 @@ static int exgd_grad_chunk(myr_handle h, int B, int nsteps, size_t* per) {
 }
 
 // device pointers throughout (a.hist, a.chunk, under EXGD_GRAD_SHOOT a.work and a.Pp and, for the batch sum, a.rows are set here); grad: [B][np] rows
-// (grad_stride == np) or their sum
+// (grad_stride == np) or, per weight set of a.R instances, the sum of its rows in fit_reduce_sets_kernel's fixed order: [B / R][np] (the closed-form
+// routes and the single-set network calls have R = B: one row, the bits of fit_reduce_kernel)
 enum { EXGD_GRAD_CLOSED_FORM = 0, EXGD_GRAD_NODE = 1, EXGD_GRAD_NODE_SHOOT = 2, EXGD_GRAD_SHOOT = 3 };      // which kernel family runs the sweep
 static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, int route) {
   const myr_dims& dm = h->dims;
@@ -2493,14 +2499,16 @@ static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int gr
                  : route == EXGD_GRAD_SHOOT
                      ? for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_shoot_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; })
                      : for_system(h->d.system_id, true, [&](auto t) { return exgd_grad_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
-  if (!rc && !grad_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, grad);
+  if (!rc && !grad_stride)
+    hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)dm.np * (unsigned)(a.B / a.R)), dim3(256), 0, h->stream, a.R, (int)dm.np, (const double*)a.rows,
+                       grad);
   const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
   return rc ? rc : rc_end;
 }
 
 // what the four myr_exgd_grad* entry points share behind their own checks: the staging, the sweep of `route`, the copies back.
-// n_param_doubles: what `params` holds (a row per instance, or one shared set)
-static int run_exgd_grad(myr_handle h, int route, int mem, int B, const double* z, const double* lam, const double* lb, const double* ub,
+// n_param_doubles: what `params` holds (a row per instance, or one shared set; the network routes: a set for every R instances, B / R sets)
+static int run_exgd_grad(myr_handle h, int route, int mem, int B, int R, const double* z, const double* lam, const double* lb, const double* ub,
                          const double* params, size_t n_param_doubles, int pstride, double eta_x, double eta_v, int nsteps, const double* seed_z,
                          const double* seed_lam, double* grad, int grad_stride, double* dz0, double* dlam0) {
   if (B == 0) return MYR_OK;                          // (nothing is written)
@@ -2508,7 +2516,7 @@ static int run_exgd_grad(myr_handle h, int route, int mem, int B, const double* 
   const myr_dims& dm = h->dims;
   const size_t nz = (size_t)B * dm.n, nl = (size_t)B * dm.m;
   ExgdGradArgs a{};
-  a.B = B; a.pstride = pstride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
+  a.B = B; a.R = R; a.pstride = pstride; a.eta_x = eta_x; a.eta_v = eta_v; a.nsteps = nsteps;
   double* g = nullptr;
   DevStage st = call_stage(h, mem);
   st.in(a.z, z, nz);
@@ -2518,7 +2526,7 @@ static int run_exgd_grad(myr_handle h, int route, int mem, int B, const double* 
   st.in(a.params, params, n_param_doubles);
   st.in(a.seed_z, seed_z, nz);
   st.in(a.seed_lam, seed_lam, nl);
-  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
+  st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)(B / R) * dm.np);
   st.out(a.dz0, dz0, nz);
   st.out(a.dlam0, dlam0, nl);
   if (int rc = st.commit()) return rc;
@@ -2542,7 +2550,7 @@ extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const dou
   if (h->d.transcription == MYR_TR_SHOOTING)
     return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: SHOOTING is not built (it needs the second-order adjoint of the rollout); use a collocation transcription");
   if (int rc = check_mem(who, mem)) return rc;
-  return run_exgd_grad(h, EXGD_GRAD_CLOSED_FORM, mem, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps,
+  return run_exgd_grad(h, EXGD_GRAD_CLOSED_FORM, mem, B, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps,
                        seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
 }
 
@@ -2566,7 +2574,7 @@ extern "C" int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, cons
   if (int rc = check_mem(who, mem)) return rc;
   if (node_exgd_grad_lds_bytes(h->d.intervals) > 160 * 1024)
     return fail(MYR_E_CAPACITY, "myr_exgd_grad_node: intervals too large for the LDS-resident reverse sweep beside the weight copy");
-  return run_exgd_grad(h, EXGD_GRAD_NODE, mem, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
+  return run_exgd_grad(h, EXGD_GRAD_NODE, mem, B, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
                        dz0, dlam0);
 }
 
@@ -2596,8 +2604,40 @@ extern "C" int myr_exgd_grad_node_shoot(myr_handle h, int32_t B, const double* z
     if (lds > 160 * 1024)
       return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_shoot: intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy");
   }
-  return run_exgd_grad(h, EXGD_GRAD_NODE_SHOOT, mem, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad,
+  return run_exgd_grad(h, EXGD_GRAD_NODE_SHOOT, mem, B, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad,
                        grad_stride, dz0, dlam0);
+}
+
+// ... and for E weight sets of R instances each in one call, under either transcription of the network system: the two calls above are its E = 1,
+// R = B case (run_exgd_grad with R = B).  Set e has the bits of the single-set call on that set alone
+extern "C" int myr_exgd_grad_node_sets(myr_handle h, int32_t E, int32_t R, const double* z, const double* lam, const double* lb, const double* ub,
+                                       const double* params, double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam,
+                                       double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
+  const char* who = "myr_exgd_grad_node_sets";
+  if (!h || !z || !lam || !lb) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null handle or array");
+  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null ub");
+  if (E < 0 || R < 1 || (long)E * R > 0x7fffffffL) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: bad sizes (E >= 0 sets of R >= 1 instances, E * R an int)");
+  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: negative nsteps");
+  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null seed_z or grad");
+  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_sets: this handle's system is not the network system; use myr_exgd_grad or myr_exgd_grad_shoot");
+  if (h->d.transcription != MYR_TR_HERMITE_SIMPSON && h->d.transcription != MYR_TR_SHOOTING)
+    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_sets: TRAPEZOIDAL is not built for the network system; HERMITE_SIMPSON and SHOOTING only");
+  if (!params) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null params (the [E][np] weight sets)");
+  if (grad_stride != 0 && grad_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: grad_stride must be 0 (a row per set: the sum over its instances) or np (a row per instance)");
+  if (int rc = check_mem(who, mem)) return rc;
+  const bool shoot = h->d.transcription == MYR_TR_SHOOTING;
+  if (shoot) {
+    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_shoot_exgd_grad_lds_bytes<2>(I, cpi) : node_shoot_exgd_grad_lds_bytes<1>(I, cpi);
+    if (lds > 160 * 1024)
+      return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_sets: intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy");
+  } else if (node_exgd_grad_lds_bytes(h->d.intervals) > 160 * 1024) {
+    return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_sets: intervals too large for the LDS-resident reverse sweep beside the weight copy");
+  }
+  return run_exgd_grad(h, shoot ? EXGD_GRAD_NODE_SHOOT : EXGD_GRAD_NODE, mem, E * R, R, z, lam, lb, ub, params, (size_t)E * h->dims.np, 0, eta_x, eta_v, nsteps,
+                       seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
 }
 
 // the same derivative under SHOOTING (shoot_exgd_grad.h)
@@ -2618,7 +2658,7 @@ extern "C" int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, con
   if (h->d.transcription != MYR_TR_SHOOTING)
     return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: this handle's transcription is not SHOOTING; use myr_exgd_grad");
   if (int rc = check_mem(who, mem)) return rc;
-  return run_exgd_grad(h, EXGD_GRAD_SHOOT, mem, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps,
+  return run_exgd_grad(h, EXGD_GRAD_SHOOT, mem, B, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps,
                        seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
 }
 
@@ -2691,9 +2731,33 @@ static int dispatch_hvp_node(myr_handle h, HvpArgs a, double* out_p, int p_strid
   if (int rc = st.commit()) return rc;
   if (int rc = timed_begin(h, kt)) return rc;
   const int rc = shoot ? hvp_node_shoot_for_system<SysNODE_CARTPOLE>(h, a) : hvp_node_colloc_for_system<SysNODE_CARTPOLE>(h, a);
-  if (!rc && out_p && !p_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, out_p);
+  if (!rc && out_p && !p_stride)      // per weight set the sum of its a.R rows, [B / R][np] (one set: the bits of fit_reduce_kernel)
+    hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)dm.np * (unsigned)(a.B / a.R)), dim3(256), 0, h->stream, a.R, (int)dm.np, (const double*)a.rows,
+                       out_p);
   const int rc_end = timed_end(h, kt);          // on every path
   return rc ? rc : rc_end;
+}
+
+// what myr_hvp_node and myr_hvp_node_sets share behind their own checks: B instances, a weight set for every R of them (params [B / R][np])
+static int run_hvp_node(myr_handle h, int mem, int B, int R, const double* z, const double* lam, const double* v, const double* params, int with_cost,
+                        double* out_z, double* out_p, int p_stride) {
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n;
+  HvpArgs a{};
+  a.B = B; a.R = R; a.with_cost = with_cost != 0;
+  double* gp = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lam, lam, (size_t)B * dm.m);
+  st.in(a.v, v, nz);
+  st.in(a.params, params, (size_t)(B / R) * dm.np);
+  st.out(a.out_z, out_z, nz);
+  st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)(B / R) * dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_hvp_node(h, a, gp, p_stride)) return rc;
+  return st.finish();
 }
 
 extern "C" int myr_hvp_node(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params, int32_t with_cost,
@@ -2716,23 +2780,31 @@ extern "C" int myr_hvp_node(myr_handle h, int32_t B, const double* z, const doub
     if (lds > 160 * 1024)
       return fail(MYR_E_CAPACITY, "myr_hvp_node: intervals x controls_per_interval too large for the LDS-resident pair records beside the weight copy");
   }
-  if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t nz = (size_t)B * dm.n;
-  HvpArgs a{};
-  a.B = B; a.with_cost = with_cost != 0;
-  double* gp = nullptr;
-  DevStage st = call_stage(h, mem);
-  st.in(a.z, z, nz);
-  st.in(a.lam, lam, (size_t)B * dm.m);
-  st.in(a.v, v, nz);
-  st.in(a.params, params, (size_t)dm.np);
-  st.out(a.out_z, out_z, nz);
-  st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)dm.np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_hvp_node(h, a, gp, p_stride)) return rc;
-  return st.finish();
+  return run_hvp_node(h, mem, B, B, z, lam, v, params, with_cost, out_z, out_p, p_stride);
+}
+
+// ... and for E weight sets of R instances each in one call: myr_hvp_node is its E = 1, R = B case.  Set e has the bits of myr_hvp_node on that set alone
+extern "C" int myr_hvp_node_sets(myr_handle h, int32_t E, int32_t R, const double* z, const double* lam, const double* v, const double* params,
+                                 int32_t with_cost, double* out_z, double* out_p, int32_t p_stride, int32_t mem) {
+  const char* who = "myr_hvp_node_sets";
+  if (!h || !z || !v) return fail(MYR_E_ARG, "myr_hvp_node_sets: null handle, z or v");
+  if (!out_z && !out_p) return fail(MYR_E_ARG, "myr_hvp_node_sets: both outputs are null");
+  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
+    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node_sets: this handle's system is not the network system; use myr_hvp");
+  if (h->d.transcription != MYR_TR_HERMITE_SIMPSON && h->d.transcription != MYR_TR_SHOOTING)
+    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node_sets: TRAPEZOIDAL is not built for the network system; HERMITE_SIMPSON and SHOOTING only");
+  if (!params) return fail(MYR_E_ARG, "myr_hvp_node_sets: null params (the [E][np] weight sets)");
+  if (E < 0 || R < 1 || (long)E * R > 0x7fffffffL) return fail(MYR_E_ARG, "myr_hvp_node_sets: bad sizes (E >= 0 sets of R >= 1 instances, E * R an int)");
+  if (p_stride != 0 && p_stride != h->dims.np)
+    return fail(MYR_E_ARG, "myr_hvp_node_sets: p_stride must be 0 (a row per set: the sum over its instances) or np (a row per instance)");
+  if (int rc = check_mem(who, mem)) return rc;
+  if (h->d.transcription == MYR_TR_SHOOTING) {
+    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_hvp_shoot_lds_bytes<2>(I, cpi) : node_hvp_shoot_lds_bytes<1>(I, cpi);
+    if (lds > 160 * 1024)
+      return fail(MYR_E_CAPACITY, "myr_hvp_node_sets: intervals x controls_per_interval too large for the LDS-resident pair records beside the weight copy");
+  }
+  return run_hvp_node(h, mem, E * R, R, z, lam, v, params, with_cost, out_z, out_p, p_stride);
 }
 
 extern "C" int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, const double* adj_T, const double* params,

@@ -17,6 +17,7 @@
 // NodeExgdWave: the same on one wavefront, lane j = hidden unit j of both layers, weights from the LDS copy of NodeMfma64::load_weights,
 // activations broadcast by v_readlane (NodeFit::fwd / bcast / wsum, fit.h); the weight gradient in NodeFit::Acc.
 // node_exgd_grad_kernel<WPI>: one workgroup of WPI wavefronts per instance.
+// Weight sets (myr_exgd_grad_node_sets): params [E][NP], R instances to a set; a workgroup is one instance and takes the row of its set.
 #pragma once
 #include "exgd_grad.h"
 #include "node_system.h"
@@ -258,7 +259,9 @@ inline size_t node_exgd_grad_lds_bytes(int N) {
   return (size_t)(NodeMfma64::L_N + 3 * n + 2 * m + K * NodeExgdHost::NS) * 8 + 16;
 }
 
-// One workgroup of WPI wavefronts per instance (blockIdx.x: the instance within this launch's chunk; every pointer is the chunk's).  Dynamic LDS:
+// One workgroup of WPI wavefronts per instance (blockIdx.x: the instance within this launch's chunk; every batch pointer is the chunk's).  params is
+// the CALL's [E][NP]: it does not advance with the chunk; the chunk's first instance is number inst0 of the call, and instance i reads the row of set
+// i / R (a chunk may begin and end inside a set; one shared set: R = the call's batch, set 0 throughout).  Dynamic LDS:
 // the weight copy, then colloc_exgd_grad_kernel's buffers.  In a point pass wavefront w takes the points j = w, w + WPI, ... one after the other and
 // writes only their entries (wave-uniform values: every lane stores); an idle wavefront of the last round skips the point's work behind a
 // wave-uniform test and reaches every barrier.  The interval passes and the copies run with all 64 WPI lanes.  The weight gradient stays in
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(64 * WPI)
 void node_exgd_grad_kernel(int B, int N, double h, const double* __restrict__ z, const double* __restrict__ lam, const double* __restrict__ lb,
                            const double* __restrict__ ub, const double* __restrict__ params, double eta_x, double eta_v, int nsteps,
                            const double* __restrict__ seed_z, const double* __restrict__ seed_lam, double* __restrict__ hist,
-                           double* __restrict__ grad, double* __restrict__ dz0, double* __restrict__ dlam0) {
+                           double* __restrict__ grad, double* __restrict__ dz0, double* __restrict__ dlam0, int inst0, int R) {
   using P = NodeExgdHost;
   using W = NodeExgdWave;
   using G = P::G;
@@ -293,6 +296,7 @@ void node_exgd_grad_kernel(int B, int N, double h, const double* __restrict__ z,
   const double* lo = lb + b * n;
   const double* hi = ub + b * n;
   double* hb = hist + b * G::hist_doubles(N, nsteps);
+  params += (size_t)(((unsigned)inst0 + blockIdx.x) / (unsigned)R) * NP;      // this instance's weight set: every use of params below
   NodeMfma64::load_weights(params, wl, tid, NT);
   for (int i = tid; i < n; i += NT) sx[i] = zb[i];
   for (int i = tid; i < m; i += NT) sl[i] = lamb[i];

@@ -159,12 +159,12 @@ __device__ static __forceinline__ void node_hvp_store_row(const NodeFit::Acc& ac
 
 inline size_t node_hvp_colloc_lds_bytes() { return (size_t)NodeMfma64::L_N * 8 + 16; }
 
-// One workgroup of WPI wavefronts per instance (blockIdx.x).  lam, out_z, rows may be null (kernel arguments: the tests on them are uniform over
-// the workgroup).  An idle wavefront of the last round leaves the point loop by its wave-uniform bound; no barrier inside it.
+// One workgroup of WPI wavefronts per instance (blockIdx.x).  params [E][NP], R instances to a set: instance b reads the row of set b / R (one
+// shared set: R = B).  lam, out_z, rows may be null (kernel arguments: the tests on them are uniform over the workgroup).  An idle wavefront of the last round leaves the point loop by its wave-uniform bound; no barrier inside it.
 template <int WPI>
 __global__ __launch_bounds__(64 * WPI)
 void node_hvp_colloc_kernel(int B, int N, double h, const double* __restrict__ z, const double* __restrict__ lam, const double* __restrict__ v,
-                            const double* __restrict__ params, int with_cost, double* __restrict__ out_z, double* __restrict__ rows) {
+                            const double* __restrict__ params, int with_cost, double* __restrict__ out_z, double* __restrict__ rows, int R) {
   using C = NodeHvp;
   using W = NodeExgdWave;
   constexpr int NS = C::NS, NW = C::NW, NP = C::NP, NT = 64 * WPI;
@@ -179,6 +179,7 @@ void node_hvp_colloc_kernel(int B, int N, double h, const double* __restrict__ z
   const double* zb = z + b * n;
   const double* vb = v + b * n;
   const double* lamb = lam ? lam + b * m : nullptr;
+  params += (long)((int)blockIdx.x / R) * NP;                     // this instance's weight set
   NodeMfma64::load_weights(params, wl, tid, NT);
   __syncthreads();
   typename W::Acc acc;
@@ -202,6 +203,7 @@ void node_hvp_colloc_kernel(int B, int N, double h, const double* __restrict__ z
 
 struct NodeHvpArgs {
   int B, I, cpi, method, with_cost;
+  int R;                                   // weight sets: R instances to a set, params [B / R][NP]
   double T;
   const double *z, *lam, *v, *params;      // lam may be null
   double *out_z, *rows;                    // either may be null
@@ -238,7 +240,8 @@ void node_hvp_shoot_kernel(NodeHvpArgs a) {
   double* side = phist + A::pair_hist_doubles(cpi) * I;
   const double* zb = a.z + b * n;
   const double* vb = a.v + b * n;
-  NodeMfma64::load_weights(a.params, wl, tid, NT);
+  const double* params = a.params + (long)((int)blockIdx.x / a.R) * NP;      // this instance's weight set: every use below
+  NodeMfma64::load_weights(params, wl, tid, NT);
   for (long i = tid; i < m; i += NT) {
     const long k = i / NS, q = i - k * NS;
     lc[k + q * I] = a.lam ? a.lam[b * m + i] : 0.0;
@@ -251,7 +254,7 @@ void node_hvp_shoot_kernel(NodeHvpArgs a) {
   NseWaveNet net{wl, lane, &acc};
   const double cw = a.with_cost ? 1.0 : 0.0;
   for (int k = wave; k < I; k += WPI)                              // (wave-uniform bounds; no barrier inside)
-    A::template interval<true>(net, R, I, cpi, k, h, zb, vb, lc + k, a.params, cw, phist + k, side + k, I, al + k, 0.0);
+    A::template interval<true>(net, R, I, cpi, k, h, zb, vb, lc + k, params, cw, phist + k, side + k, I, al + k, 0.0);
   __syncthreads();                                                 // every side record is written; the weight copy is idle from here
   if (a.out_z)
     for (long i = tid; i < n; i += NT) a.out_z[b * n + i] = S::HV::gather_z(I, cpi, i, side, I);

@@ -360,8 +360,10 @@ struct NseWaveNet {
 
 struct NseArgs {
   int B, I, cpi, method, nsteps;
+  int inst0, R;      // weight sets: the chunk's first instance is number inst0 of the call; R instances to a set
   double T, eta_x, eta_v;
-  const double *z, *lam, *lb, *ub, *params, *seed_z, *seed_lam;      // the chunk's
+  const double *z, *lam, *lb, *ub, *seed_z, *seed_lam;      // the chunk's
+  const double* params;                                      // the call's [E][NP]: does not advance with the chunk
   double *hist, *grad, *dz0, *dlam0;
 };
 
@@ -373,7 +375,7 @@ inline size_t node_shoot_exgd_grad_lds_bytes(int I, int cpi) {
 inline int node_shoot_exgd_grad_wpi(int I) { return I >= 4 ? 4 : (I >= 2 ? 2 : 1); }
 
 // One workgroup of WPI = blockDim.x / 64 wavefronts per instance (blockIdx.x: the instance within this launch's chunk; every pointer is the
-// chunk's).  In a pair pass wavefront w takes the intervals k = w, w + WPI, ... one after the other and writes only their columns (wave-uniform
+// chunk's, but params: instance i of the call reads the row of set i / R, as node_exgd_grad_kernel).  In a pair pass wavefront w takes the intervals k = w, w + WPI, ... one after the other and writes only their columns (wave-uniform
 // values: every lane stores); an idle wavefront of the last round skips the pair's work behind a wave-uniform test and reaches every barrier.
 template <int M>
 __global__ __launch_bounds__(256)
@@ -402,7 +404,8 @@ void node_shoot_exgd_grad_kernel(NseArgs a) {
   const double* lo = a.lb + b * n;
   const double* hi = a.ub + b * n;
   double* hb = a.hist + b * A::hist_doubles(I, cpi, nsteps);
-  NodeMfma64::load_weights(a.params, wl, tid, NT);
+  const double* params = a.params + (long)((a.inst0 + (int)blockIdx.x) / a.R) * NP;      // this instance's weight set: every use below
+  NodeMfma64::load_weights(params, wl, tid, NT);
   for (long i = tid; i < n; i += NT) zx[i] = a.z[b * n + i];
   for (long i = tid; i < m; i += NT) { const long k = i / NS, q = i - k * NS; lc[k + q * I] = a.lam[b * m + i]; }
   __syncthreads();
@@ -419,7 +422,7 @@ void node_shoot_exgd_grad_kernel(NseArgs a) {
       const double* src = half == 0 ? zx : zb;
       double* dst = half == 0 ? zb : zx;
       for (int k = wave; k < I; k += WPI)                          // (wave-uniform bounds; no barrier inside)
-        A::template interval<false>(net, R, I, cpi, k, h, src, nullptr, lc + k, a.params, 1.0, phist + k, side + k, I, nullptr, 0.0);
+        A::template interval<false>(net, R, I, cpi, k, h, src, nullptr, lc + k, params, 1.0, phist + k, side + k, I, nullptr, 0.0);
       __syncthreads();
       for (long i = tid; i < n; i += NT) {
         const double v = A::P::clip_step(zx[i], G::out_z(I, cpi, i, side, lc, 1.0, I), a.eta_x, lo[i], hi[i]);
@@ -452,7 +455,7 @@ void node_shoot_exgd_grad_kernel(NseArgs a) {
       for (long i = tid; i < m; i += NT) { const long k = i / NS, r = i - k * NS; lc[k + r * I] = Hh[2 * n + i]; }
     __syncthreads();
     for (int k = wave; k < I; k += WPI)
-      A::template interval<true>(net, R, I, cpi, k, h, zx, zb, has_lam ? lc + k : nullptr, a.params, 1.0, phist + k, side + k, I, al + k, q.scale);
+      A::template interval<true>(net, R, I, cpi, k, h, zx, zb, has_lam ? lc + k : nullptr, params, 1.0, phist + k, side + k, I, al + k, q.scale);
     __syncthreads();
     for (long i = tid; i < n; i += NT) {
       double av = ax[i], dv;

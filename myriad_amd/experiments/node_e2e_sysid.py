@@ -7,6 +7,10 @@ that same point (`lookahead_update`, :187-196), and optax.adam(1e-4) -- hard-cod
 (myr_exgd) and the contracted derivative another (myr_exgd_grad_node: one reverse sweep, csrc/node_exgd_grad.h; under SHOOTING
 myr_exgd_grad_node_shoot, csrc/node_shoot_exgd_grad.h); loss and Adam run in numpy.
 
+`run_node_endtoend_sets` trains E networks at once -- seeds, noise levels, learning rates --: an epoch of all of them is one myr_exgd call with a
+weight row per instance and one myr_exgd_grad_node_sets call (E R workgroups in one launch where E runs launch E times one), with
+node_training.AdamSets; entry e of its result is run_node_endtoend on network e alone, to the bit.
+
 `run_node_endtoend(..., shooting=True)` with a SHOOTING optimizer -- the reference's default hyperparameters -- runs the same loop on
 myr_exgd_grad_node_shoot.  Without it myr_exgd_grad_node is asked, which refuses every transcription but Hermite-Simpson before anything is solved.
 
@@ -125,3 +129,88 @@ def run_node_endtoend(hp: HParams, cfg: Config, num_epochs: int = 10_000, node: 
   saved[num_epochs] = mapping_from_flat(flat)
   return {"params": node.params, "saved_params": saved, "ts": ts, "imitation_losses": imitation_losses, "primal_guesses": primal_guesses,
           "dual_guesses": dual_guesses, "true_opt_us": true_opt_us}
+
+
+def advance_sets(engine, Z, L, lb, ub, eta_x, eta_v, nsteps, P):
+  """`nsteps` extragradient steps of all E R iterates Z [E,R,n], L [E,R,m], set e under the weights P[e] of P [E,np]: ONE myr_exgd call with each
+  set's row repeated R times (params_stride == np).  Under SHOOTING that stride takes the one-instance-per-pass route of
+  csrc/node_shoot_products.h where a single run's shared-weights call takes the batched one; both give the same bits
+  (tests/test_gpu_node_sets.py: the driver under SHOOTING).  Returns the new (Z, L)."""
+  E, R = Z.shape[:2]
+  wide = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), Z.shape)).reshape(E * R, -1)
+  z, lam = engine.exgd(Z.reshape(E * R, -1), L.reshape(E * R, -1), wide(lb), wide(ub), eta_x, eta_v, nsteps, params=np.repeat(P, R, axis=0))
+  return z.reshape(Z.shape), lam.reshape(L.shape)
+
+
+def run_node_endtoend_sets(hp: HParams, cfg: Config, nodes, num_epochs: int = 10_000, start_states=None, save_and_reset_time: int = 1_000,
+                           shooting: bool = False, lrs=None) -> Optional[list]:
+  """run_node_endtoend for E networks at once (`nodes`: E NeuralODE of the (64, 64) architecture -- different seeds, noise levels, learning
+  rates): every epoch is ONE advance of all E R iterates (myr_exgd with a weight row per instance) and ONE myr_exgd_grad_node_sets call with the
+  per-set sums, where E separate runs launch E workgroups one after the other; Adam is node_training.AdamSets, a row per network, with the
+  learning rate lrs[e] (default ADAM_LR for all).  R = the number of start states (1 without them); the true optimum, the guess and the bounds
+  are the same for every network.  Returns a list of E dicts with run_node_endtoend's keys; entry e equals run_node_endtoend on nodes[e] alone
+  (with ADAM_LR = lrs[e]), to the bit.  None for a system without parameter guesses."""
+  from myriad_amd.neural_ode.node_training import AdamSets
+  if hp.system not in param_guesses:
+    print("We do not currently support that kind of system for sysid. Exiting...")
+    return None
+  nodes = list(nodes)
+  E = len(nodes)
+  if E == 0:
+    return []
+  true_system = hp.system()
+  true_optimizer = get_optimizer(hp, cfg, true_system)
+  node_optimizer = get_optimizer(hp, cfg, NodeSystem(node=nodes[0], true_system=true_system))      # one handle serves every set: the weights go in per call
+  engine = node_optimizer.engine
+  is_shoot = node_optimizer.transcription == "SHOOTING"
+  if is_shoot and not shooting:      # (as run_node_endtoend: without the opt-in the single-set Hermite-Simpson call is asked, which refuses)
+    engine.exgd_grad_node_probe()
+  engine.exgd_grad_node_sets_probe()      # the library's own refusals, before the true optimum is solved for
+  batched = start_states is not None
+  if batched:
+    x0s = np.asarray(start_states, dtype=np.float64)
+    B = x0s.shape[0]
+    true_opt_us = true_optimizer.solve_batch(x0s=x0s)['u']
+    guess, lb, ub = true_optimizer.batch_inputs(x0s, true_system.device_params())
+  else:
+    B = 1
+    true_opt_us = true_optimizer.solve()['u']
+    guess, lb, ub = true_optimizer.guess, true_optimizer.bounds[:, 0], true_optimizer.bounds[:, 1]
+  guess = np.array(guess, dtype=np.float64).reshape(B, -1)
+  own = (lambda a: a) if batched else (lambda a: a[0])           # a set's iterate in the shape run_node_endtoend keeps it: [B][n], or [n]
+  P = np.stack([flat_from_mapping(node.params) for node in nodes])
+  Z0 = np.ascontiguousarray(np.broadcast_to(guess, (E,) + guess.shape))
+  L0 = np.zeros((E, B, engine.m))
+  Z, L = Z0.copy(), L0.copy()
+  opt = AdamSets(P.shape, ADAM_LR if lrs is None else np.asarray(lrs, dtype=np.float64))
+  every = list(range(E))
+  eta_x, eta_v = true_optimizer.step_sizes()
+  runs = [{"ts": [], "primal_guesses": [], "dual_guesses": [], "imitation_losses": [], "saved_params": {}} for _ in range(E)]
+  record_things_time = 10
+  for epoch in range(num_epochs):
+    if epoch % save_and_reset_time == 0:
+      record_things_time = 1
+      for e in every:
+        runs[e]["saved_params"][epoch] = mapping_from_flat(P[e])
+      Z, L = Z0.copy(), L0.copy()
+    if epoch % record_things_time == 0:
+      if epoch >= 10:
+        record_things_time = 10
+      for e in every:
+        r = runs[e]
+        r["ts"].append(epoch); r["primal_guesses"].append(own(Z[e]).copy()); r["dual_guesses"].append(own(L[e]).copy())
+        cur_loss, _ = simple_imitation_loss(true_optimizer, own(Z[e]), true_opt_us)
+        r["imitation_losses"].append(cur_loss)
+        if cfg.verbose:
+          print(e, epoch, "loss", cur_loss)
+    Z, L = advance_sets(engine, Z, L, lb, ub, eta_x, eta_v, hp.num_unrolled, P)
+    dJ = np.stack([simple_imitation_loss(true_optimizer, own(Z[e]), true_opt_us)[1].reshape(B, -1) for e in every])
+    g = engine.exgd_grad_node_sets(Z, L, lb, ub, eta_x, eta_v, hp.num_unrolled, dJ, P, reduce=True, want_start=False)["grad"] / B
+    P = opt.update(every, P, g)
+  out = []
+  for e, node in enumerate(nodes):
+    node.params = mapping_from_flat(P[e])
+    runs[e]["saved_params"][num_epochs] = mapping_from_flat(P[e])
+    out.append({"params": node.params, "saved_params": runs[e]["saved_params"], "ts": runs[e]["ts"], "imitation_losses": runs[e]["imitation_losses"],
+                "primal_guesses": runs[e]["primal_guesses"], "dual_guesses": runs[e]["dual_guesses"], "true_opt_us": true_opt_us})
+  return out

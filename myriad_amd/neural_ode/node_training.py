@@ -93,10 +93,10 @@ def train(hp, T, params, train_data, val_data, rng=None, verbose=False, fit=None
 
 class AdamSets:
   """mle_sysid.Adam on the rows of an [E, np] array: every row is an optimiser of its own -- its moments and its step count --, in the elementwise
-  arithmetic of Adam.update.  Rows left out of a step keep both."""
+  arithmetic of Adam.update.  Rows left out of a step keep both.  lr: one learning rate, or one per row ([E])."""
 
   def __init__(self, shape, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
-    self.lr, self.b1, self.b2, self.eps = lr, b1, b2, eps
+    self.lr, self.b1, self.b2, self.eps = (lr if np.ndim(lr) == 0 else np.asarray(lr, dtype=np.float64).reshape(shape[0])), b1, b2, eps
     self.m, self.v, self.t = np.zeros(shape), np.zeros(shape), [0] * shape[0]
 
   def update(self, rows, params, grads):
@@ -110,7 +110,8 @@ class AdamSets:
     c2 = np.array([1.0 - self.b2 ** self.t[r] for r in rows])[:, None]
     m_hat = self.m[rows] / c1
     v_hat = self.v[rows] / c2
-    return params - self.lr * m_hat / (np.sqrt(v_hat) + self.eps)
+    lr = self.lr if np.ndim(self.lr) == 0 else self.lr[rows][:, None]      # (a row's own rate times its row: the product Adam.update takes)
+    return params - lr * m_hat / (np.sqrt(v_hat) + self.eps)
 
 
 def train_ensemble(hp, T, params_sets, train_data, val_data, rngs=None, fit=None, verbose=False):

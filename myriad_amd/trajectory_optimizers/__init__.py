@@ -198,9 +198,12 @@ class TrajectoryOptimizer(object):
   def lagrangian_hessp(self, xs_and_us, lmbdas, v, params=None, with_cost=True):
     """(d2 lagrangian / dx dx) v, matrix-free and exact on the device (myr_hvp), for every transcription.  with_cost=False drops the objective:
     sum_i lmbda_i (d2 c_i / dx dx) v, the `hess(x, v)` a SciPy NonlinearConstraint takes; lmbdas None with with_cost=True: the objective's Hessian.
-    Over a NodeSystem `params` is the Haiku mapping of the weights (None: the system's own) and the product is myr_hvp_node's."""
+    Over a NodeSystem `params` is the Haiku mapping of the weights (None: the system's own) and the product is myr_hvp_node's; `params` an array [E, np] of flat weight rows with
+    xs_and_us, v [E, R, n] (lmbdas [E, R, m] or None) gives all E R products in one myr_hvp_node_sets call, [E, R, n]."""
     if self.system.name == "NODE_CARTPOLE":
       from myriad_amd.systems.neural_ode import flat_from_mapping
+      if isinstance(params, np.ndarray) and params.ndim == 2:      # E weight sets [E, np] as flat rows, variables [E, R, n]: one myr_hvp_node_sets call, [E, R, n]
+        return self.engine.hvp_node_sets(xs_and_us, lmbdas, v, params, with_cost=with_cost)["hz"]
       flat = self.system.device_params() if params is None else flat_from_mapping(params)
       return self.engine.hvp_node(xs_and_us, lmbdas, v, flat, with_cost=with_cost)["hz"][0]
     p = self.system.device_params() if params is None else self.system.params_from_mapping(params)
@@ -224,11 +227,19 @@ class TrajectoryOptimizer(object):
     (myr_exgd_grad; myr_exgd_grad_shoot on a SHOOTING optimizer).  variables [n] or [B,n], seed likewise (dJ/dx); params: a parameter mapping (None: the system's own).  Returns the
     gradient in the device order of system.param_names, [np] ([B,np] for a batch; its sum over the batch with reduce).  lb / ub: bounds per
     instance (default: this optimizer's).  Over a NodeSystem `params` is the Haiku mapping of the weights and the gradient comes back as
-    such a mapping (a list of them for a batch without reduce), through myr_exgd_grad_node (myr_exgd_grad_node_shoot on a SHOOTING optimizer)."""
+    such a mapping (a list of them for a batch without reduce), through myr_exgd_grad_node (myr_exgd_grad_node_shoot on a SHOOTING optimizer).  `params` an array [E, np] of flat weight
+    rows with variables [E, R, n] and lmbdas [E, R, m]: E networks in one myr_exgd_grad_node_sets call, the gradient as flat rows [E, R, np]
+    ([E, np] with reduce: per network the sum over its R instances)."""
     ex, ev = self.step_sizes()
     single = np.ndim(variables) == 1
     if self.system.name == "NODE_CARTPOLE":      # a Haiku mapping in, the gradient as a mapping out (myr_exgd_grad_node; a batch: the sum with reduce)
       from myriad_amd.systems.neural_ode import flat_from_mapping, mapping_from_flat
+      if isinstance(params, np.ndarray) and params.ndim == 2:
+        # E weight sets [E, np] as flat rows, variables [E, R, n]: one myr_exgd_grad_node_sets call under either transcription; the gradient as flat
+        # rows too, [E, R, np], or [E, np] = per set the sum over its instances with reduce
+        return self.engine.exgd_grad_node_sets(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
+                                               ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, seed, params, reduce=reduce,
+                                               want_start=False)["grad"]
       flat = self.system.device_params() if params is None else flat_from_mapping(params)
       node_call = self.engine.exgd_grad_node_shoot if self.transcription == "SHOOTING" else self.engine.exgd_grad_node
       out = node_call(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
