@@ -28,12 +28,6 @@ K_EVAL, K_SOLVE, K_ROLLOUT, K_RESID, K_PROD, K_FBSM, K_FIT, K_HVP_NODE, K_HVP_NO
 STATUS_NAMES = {0: "CONVERGED", 1: "MAXITER", 2: "NAN", 3: "STALLED", 4: "INFEASIBLE"}
 STATUS_INFEASIBLE = 4   # assigned by the library's restoration phase inside myr_solve (csrc/myriad_hip.hip: solve_restored), never by a kernel
 
-EXPORTS = ["myr_create", "myr_destroy", "myr_get_dims", "myr_default_solve_opts", "myr_eval", "myr_solve", "myr_solve_x0",
-           "myr_set_var_scale", "myr_rollout", "myr_vjp", "myr_jvp", "myr_exgd", "myr_fbsm", "myr_kernel_time", "myr_kernel_time_reset", "myr_last_error",
-           "myr_version", "myr_device_count", "myr_solve_info", "myr_abi_sizeof", "myr_solve_plan", "myr_fit_grad", "myr_exgd_grad", "myr_hvp",
-           "myr_exgd_grad_node", "myr_exgd_grad_shoot", "myr_exgd_grad_node_shoot", "myr_hvp_node", "myr_fit_grad_sets",
-           "myr_exgd_grad_node_sets", "myr_hvp_node_sets"]
-
 
 class ProblemDesc(C.Structure):
   _fields_ = [("system_id", C.c_int32), ("transcription", C.c_int32), ("integration_method", C.c_int32),
@@ -57,6 +51,48 @@ class MyriadHipError(RuntimeError):
   pass
 
 
+# The C-ABI (include/myriad_hip.h): exported function -> (argument types, return type).  load() declares every function from this table, and
+# __graft_entry__.build() checks the built library against its names (EXPORTS).
+_i, _f, _p = C.c_int32, C.c_double, C.c_void_p      # _p: the handle, and raw addresses (host numpy or device pointers)
+_opts = C.POINTER(SolveOpts)
+_EXGD_GRAD_TAIL = [_f, _f, _i, _p, _p, _p, _i, _p, _p, _i]      # eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride, dz0, dlam0, mem
+_HVP_TAIL = [_i, _p, _p, _i, _i]                                # with_cost, out_z, out_p, p_stride, mem
+_SIGNATURES = {
+  "myr_create": ([C.POINTER(ProblemDesc), C.POINTER(C.c_void_p)], C.c_int),
+  "myr_destroy": ([_p], C.c_int),
+  "myr_get_dims": ([_p, C.POINTER(Dims)], C.c_int),
+  "myr_default_solve_opts": ([_opts], None),
+  "myr_device_count": ([], C.c_int),
+  "myr_eval": ([_p, _i, _p, _p, _i, _p, _p, _p, _p, _i], C.c_int),
+  "myr_solve": ([_p, _i, _p, _p, _p, _p, _i, _opts, _p, _p, _p, _p, _p, _i], C.c_int),
+  "myr_solve_x0": ([_p, _i, _p, _p, _p, _p, _p, _p, _i, _opts, _p, _p, _p, _p, _p, _p, _i], C.c_int),
+  "myr_solve_info": ([_p, _i, _p, _p, _p], C.c_int),
+  "myr_solve_plan": ([_p, _p], C.c_int),
+  "myr_rollout": ([_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _i], C.c_int),
+  "myr_fit_grad": ([_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i], C.c_int),
+  "myr_fit_grad_sets": ([_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _i], C.c_int),
+  "myr_set_var_scale": ([_p, _p], C.c_int),
+  "myr_vjp": ([_p, _i, _p, _p, _p, _i, _p, _i, _i], C.c_int),
+  "myr_jvp": ([_p, _i, _p, _p, _p, _i, _p, _i], C.c_int),
+  "myr_exgd": ([_p, _i, _p, _p, _p, _p, _p, _i, _f, _f, _i, _i], C.c_int),
+  "myr_exgd_grad": ([_p, _i, _p, _p, _p, _p, _p, _i] + _EXGD_GRAD_TAIL, C.c_int),
+  "myr_exgd_grad_shoot": ([_p, _i, _p, _p, _p, _p, _p, _i] + _EXGD_GRAD_TAIL, C.c_int),
+  "myr_exgd_grad_node": ([_p, _i, _p, _p, _p, _p, _p] + _EXGD_GRAD_TAIL, C.c_int),
+  "myr_exgd_grad_node_shoot": ([_p, _i, _p, _p, _p, _p, _p] + _EXGD_GRAD_TAIL, C.c_int),
+  "myr_exgd_grad_node_sets": ([_p, _i, _i, _p, _p, _p, _p, _p] + _EXGD_GRAD_TAIL, C.c_int),
+  "myr_hvp": ([_p, _i, _p, _p, _p, _p, _i] + _HVP_TAIL, C.c_int),
+  "myr_hvp_node": ([_p, _i, _p, _p, _p, _p] + _HVP_TAIL, C.c_int),
+  "myr_hvp_node_sets": ([_p, _i, _i, _p, _p, _p, _p] + _HVP_TAIL, C.c_int),
+  "myr_fbsm": ([_p, _i, _i, _p, _p, _p, _i, _p, _p, _f, _f, _i, _p, _p, _p, _p, _i], C.c_int),
+  "myr_kernel_time": ([_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_int32)], C.c_int),
+  "myr_kernel_time_reset": ([_p], C.c_int),
+  "myr_last_error": ([], C.c_char_p),
+  "myr_version": ([], C.c_char_p),
+  "myr_abi_sizeof": ([_i], C.c_int32),
+}
+EXPORTS = list(_SIGNATURES)
+
+
 _lib = None
 
 
@@ -77,72 +113,13 @@ def load() -> C.CDLL:
     except Exception:
       pass
   lib = C.CDLL(LIB_PATH)
-  vp, dp, ip = C.c_void_p, C.c_void_p, C.c_void_p   # raw addresses (host numpy or device pointers)
-  lib.myr_create.argtypes = [C.POINTER(ProblemDesc), C.POINTER(C.c_void_p)]
-  lib.myr_create.restype = C.c_int
-  lib.myr_destroy.argtypes = [C.c_void_p]
-  lib.myr_destroy.restype = C.c_int
-  lib.myr_get_dims.argtypes = [C.c_void_p, C.POINTER(Dims)]
-  lib.myr_get_dims.restype = C.c_int
-  lib.myr_default_solve_opts.argtypes = [C.POINTER(SolveOpts)]
-  lib.myr_default_solve_opts.restype = None
-  lib.myr_device_count.argtypes = []
-  lib.myr_device_count.restype = C.c_int
-  lib.myr_eval.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, dp, dp, dp, dp, C.c_int32]
-  lib.myr_eval.restype = C.c_int
-  lib.myr_solve.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.POINTER(SolveOpts), dp, dp, ip, ip, dp, C.c_int32]
-  lib.myr_solve.restype = C.c_int
-  lib.myr_solve_x0.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, C.POINTER(SolveOpts), dp, dp, dp, ip, ip, dp, C.c_int32]
-  lib.myr_solve_x0.restype = C.c_int
-  lib.myr_solve_info.argtypes = [vp, C.c_int32, ip, ip, ip]
-  lib.myr_solve_info.restype = C.c_int
-  lib.myr_solve_plan.argtypes = [vp, ip]
-  lib.myr_solve_plan.restype = C.c_int
-  lib.myr_rollout.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
-  lib.myr_rollout.restype = C.c_int
-  lib.myr_fit_grad.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
-  lib.myr_fit_grad.restype = C.c_int
-  lib.myr_fit_grad_sets.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32]
-  lib.myr_fit_grad_sets.restype = C.c_int
-  lib.myr_set_var_scale.argtypes = [vp, dp]
-  lib.myr_set_var_scale.restype = C.c_int
-  lib.myr_vjp.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32]
-  lib.myr_vjp.restype = C.c_int
-  lib.myr_jvp.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32, dp, C.c_int32]
-  lib.myr_jvp.restype = C.c_int
-  lib.myr_exgd.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32]
-  lib.myr_exgd.restype = C.c_int
-  lib.myr_exgd_grad.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
-  lib.myr_exgd_grad.restype = C.c_int
-  lib.myr_exgd_grad_shoot.argtypes = lib.myr_exgd_grad.argtypes
-  lib.myr_exgd_grad_shoot.restype = C.c_int
-  lib.myr_exgd_grad_node.argtypes = [vp, C.c_int32, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_int32]
-  lib.myr_exgd_grad_node.restype = C.c_int
-  lib.myr_exgd_grad_node_shoot.argtypes = lib.myr_exgd_grad_node.argtypes
-  lib.myr_exgd_grad_node_shoot.restype = C.c_int
-  lib.myr_hvp.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, C.c_int32, C.c_int32]
-  lib.myr_hvp.restype = C.c_int
-  lib.myr_hvp_node.argtypes = [vp, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
-  lib.myr_hvp_node.restype = C.c_int
-  lib.myr_exgd_grad_node_sets.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_int32, dp, dp, dp, C.c_int32, dp, dp,
-                                          C.c_int32]
-  lib.myr_exgd_grad_node_sets.restype = C.c_int
-  lib.myr_hvp_node_sets.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32]
-  lib.myr_hvp_node_sets.restype = C.c_int
-  lib.myr_fbsm.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, C.c_int32, dp, dp, C.c_double, C.c_double, C.c_int32,
-                           dp, dp, dp, ip, C.c_int32]
-  lib.myr_fbsm.restype = C.c_int
-  lib.myr_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-  lib.myr_kernel_time.restype = C.c_int
-  lib.myr_kernel_time_reset.argtypes = [vp]
-  lib.myr_kernel_time_reset.restype = C.c_int
-  lib.myr_last_error.restype = C.c_char_p
-  lib.myr_version.restype = C.c_char_p
   # ABI guard: the structs have no size field; a library built from another header would read past (or short of) ours
+  lib.myr_version.restype = C.c_char_p
   if not hasattr(lib, "myr_abi_sizeof"):
     raise MyriadHipError(f"{LIB_PATH} ({lib.myr_version().decode()}) predates myr_abi_sizeof: rebuild it (python __graft_entry__.py build)")
-  lib.myr_abi_sizeof.argtypes = [C.c_int32]
-  lib.myr_abi_sizeof.restype = C.c_int32
+  for name, (argtypes, restype) in _SIGNATURES.items():
+    fn = getattr(lib, name)
+    fn.argtypes, fn.restype = argtypes, restype
   for which, st in ((0, SolveOpts), (1, ProblemDesc), (2, Dims)):
     if lib.myr_abi_sizeof(which) != C.sizeof(st):
       raise MyriadHipError(f"{LIB_PATH} ({lib.myr_version().decode()}): {st.__name__} is {lib.myr_abi_sizeof(which)} bytes in the library, "
@@ -440,106 +417,15 @@ class Engine:
                            int(nsteps), MEM_HOST), "myr_exgd")
     return z, lam
 
-  def exgd_grad(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam=None, params=None, reduce=False, want_start=True, _call="myr_exgd_grad"):
-    """myr_exgd_grad: derivative of `nsteps` extragradient steps from (z, lam) in the model parameters, contracted with the seed.
-    Returns {"grad" [B,np], or [np] = the sum over the batch with reduce=True, "dz0" [B,n], "dlam0" [B,m]} (the last two with want_start)."""
-    z = self._batch2(z, self.n, "z"); lam = self._batch2(lam, self.m, "lam")
-    B = z.shape[0]
-    if lam.shape[0] != B:
-      raise ValueError("z and lam must have the same batch size")
-    lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), z.shape))
-    ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), z.shape))
-    sz = np.ascontiguousarray(np.broadcast_to(_f64(seed_z), z.shape))
-    sl = None if seed_lam is None else np.ascontiguousarray(np.broadcast_to(_f64(seed_lam), lam.shape))
-    p, ps = self._params(params, B)
-    grad = np.empty(self.np) if reduce else np.empty((B, self.np))
-    dz0 = np.empty((B, self.n)) if want_start else None
-    dlam0 = np.empty((B, self.m)) if want_start else None
-    _chk(getattr(self.lib, _call)(self._h, B, _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(p), ps, float(eta_x), float(eta_v), int(nsteps),
-                                  _addr(sz), _addr(sl), _addr(grad), 0 if reduce else self.np, _addr(dz0), _addr(dlam0), MEM_HOST), _call)
-    out = {"grad": grad}
-    if want_start:
-      out["dz0"] = dz0; out["dlam0"] = dlam0
-    return out
-
-  def exgd_grad_probe(self, _call="myr_exgd_grad"):
-    """Raises the library's error when myr_exgd_grad is not built for this handle (an empty batch: the checks run, nothing else)."""
-    d = np.zeros(1)
-    _chk(getattr(self.lib, _call)(self._h, 0, _addr(d), _addr(d), _addr(d), _addr(d), None, 0, 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None, None,
-                                  MEM_HOST), _call)
-
-  def exgd_grad_node_probe(self, _call="myr_exgd_grad_node"):
-    """Raises the library's error when myr_exgd_grad_node is not built for this handle (an empty batch: the checks run, nothing else)."""
-    d = np.zeros(1)
-    _chk(getattr(self.lib, _call)(self._h, 0, _addr(d), _addr(d), _addr(d), _addr(d), _addr(d), 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None, None,
-                                  MEM_HOST), _call)
-
-  def exgd_grad_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam=None, params=None, params_stride=0,
-                       dz0=None, dlam0=None, _call="myr_exgd_grad"):
-    """Zero-copy variant of exgd_grad: every array is a device tensor on this handle's device."""
-    _chk(getattr(self.lib, _call)(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), int(params_stride), float(eta_x),
-                                  float(eta_v), int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
-                                  MEM_DEVICE), _call)
-
-  # myr_exgd_grad_shoot: the same derivative on a SHOOTING handle (csrc/shoot_exgd_grad.h) -- the signatures, the return dict and the checks of the
-  # three methods above; myr_exgd_grad itself keeps refusing SHOOTING
-  def exgd_grad_shoot(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam=None, params=None, reduce=False, want_start=True):
-    return self.exgd_grad(z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam, params, reduce, want_start, _call="myr_exgd_grad_shoot")
-
-  def exgd_grad_shoot_probe(self):
-    self.exgd_grad_probe(_call="myr_exgd_grad_shoot")
-
-  def exgd_grad_shoot_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam=None, params=None, params_stride=0,
-                             dz0=None, dlam0=None):
-    self.exgd_grad_device(B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam, params, params_stride, dz0, dlam0,
-                          _call="myr_exgd_grad_shoot")
-
-  def exgd_grad_node(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True,
-                     _call="myr_exgd_grad_node"):
-    """myr_exgd_grad_node: exgd_grad in the 4 804 shared weights of the network system (`params`: the flat vector of csrc/node_system.h's order;
-    Hermite-Simpson).  Returns {"grad" [B,np], or [np] = the sum over the batch with reduce=True, "dz0" [B,n], "dlam0" [B,m]}."""
-    z = self._batch2(z, self.n, "z"); lam = self._batch2(lam, self.m, "lam")
-    B = z.shape[0]
-    if lam.shape[0] != B:
-      raise ValueError("z and lam must have the same batch size")
-    lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), z.shape))
-    ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), z.shape))
-    sz = np.ascontiguousarray(np.broadcast_to(_f64(seed_z), z.shape))
-    sl = None if seed_lam is None else np.ascontiguousarray(np.broadcast_to(_f64(seed_lam), lam.shape))
+  # ---- the derivative family (myr_exgd_grad*, myr_hvp*): one C call, one host body, one probe for each of the two ------------------------------
+  # `kind` says what `params` is: "rows" (a closed-form system: None, [np] or [B,np], passed with its stride), "shared" (the network system: its
+  # 4 804 weights, no stride) or "sets" ([E,np] weight sets of R instances each: the arrays are [E,R,.] and the call takes E, R where the others take B)
+  def _weights(self, params):
     p = None if params is None else np.ascontiguousarray(_f64(params))
     if p is not None and p.shape != (self.np,):
       raise ValueError(f"params must be the {self.np} shared weights")
-    grad = np.empty(self.np) if reduce else np.empty((B, self.np))
-    dz0 = np.empty((B, self.n)) if want_start else None
-    dlam0 = np.empty((B, self.m)) if want_start else None
-    _chk(getattr(self.lib, _call)(self._h, B, _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(p), float(eta_x), float(eta_v), int(nsteps),
-                                  _addr(sz), _addr(sl), _addr(grad), 0 if reduce else self.np, _addr(dz0), _addr(dlam0), MEM_HOST), _call)
-    out = {"grad": grad}
-    if want_start:
-      out["dz0"] = dz0; out["dlam0"] = dlam0
-    return out
+    return p
 
-  def exgd_grad_node_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None, dlam0=None,
-                            _call="myr_exgd_grad_node"):
-    """Zero-copy variant of exgd_grad_node: every array is a device tensor on this handle's device."""
-    _chk(getattr(self.lib, _call)(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), float(eta_x), float(eta_v),
-                                  int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
-                                  MEM_DEVICE), _call)
-
-  # myr_exgd_grad_node_shoot: the same derivative in the weights on a SHOOTING handle (csrc/node_shoot_exgd_grad.h) -- the signatures, the return
-  # dict and the checks of the three methods above; myr_exgd_grad_node itself keeps refusing SHOOTING
-  def exgd_grad_node_shoot(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
-    return self.exgd_grad_node(z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam, reduce, want_start, _call="myr_exgd_grad_node_shoot")
-
-  def exgd_grad_node_shoot_probe(self):
-    self.exgd_grad_node_probe(_call="myr_exgd_grad_node_shoot")
-
-  def exgd_grad_node_shoot_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None,
-                                  dlam0=None):
-    self.exgd_grad_node_device(B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam, dz0, dlam0,
-                               _call="myr_exgd_grad_node_shoot")
-
-  # ---- E weight sets of R instances each in one call (myr_exgd_grad_node_sets, myr_hvp_node_sets) --------------------------
   def _sets3(self, a, E, R, width, name):
     a = _f64(a)
     if a.shape != (E, R, width):
@@ -552,136 +438,187 @@ class Engine:
       raise ValueError(f"params must be [E,{self.np}]: a weight set per row")
     return p
 
+  def _sets_z(self, z, E):
+    z = _f64(z)
+    if z.ndim != 3 or z.shape[0] != E or z.shape[1] < 1 or z.shape[2] != self.n:
+      raise ValueError(f"z must be [E = {E}, R, {self.n}] with R >= 1")
+    return z
+
+  def _param_args(self, kind, params, B):
+    """what the C call takes for `params`: (array, stride), or (array,) for the network calls"""
+    return self._params(params, B) if kind == "rows" else (self._weights(params),)
+
+  @staticmethod
+  def _present(**arrays):
+    return {k: v for k, v in arrays.items() if v is not None}
+
+  def _exgd_grad_call(self, call, mem, sizes, z, lam, lb, ub, pargs, eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride, dz0, dlam0):
+    """the C call: `sizes` (B,) or (E, R), `pargs` as _param_args gives them; the arrays are host or device ones, as `mem` says"""
+    _chk(getattr(self.lib, call)(self._h, *map(int, sizes), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(pargs[0]), *map(int, pargs[1:]), float(eta_x),
+                                 float(eta_v), int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0), mem), call)
+
+  def _exgd_grad(self, call, kind, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam, params, reduce, want_start):
+    if kind == "sets":
+      pargs = (self._weight_sets(params),)
+      z = self._sets_z(z, pargs[0].shape[0])
+      lead = z.shape[:2]
+      lam = self._sets3(lam, *lead, self.m, "lam")
+    else:
+      z = self._batch2(z, self.n, "z"); lam = self._batch2(lam, self.m, "lam")
+      lead = z.shape[:1]
+      if lam.shape[0] != lead[0]:
+        raise ValueError("z and lam must have the same batch size")
+    lb, ub, sz = (np.ascontiguousarray(np.broadcast_to(_f64(a), z.shape)) for a in (lb, ub, seed_z))
+    sl = None if seed_lam is None else np.ascontiguousarray(np.broadcast_to(_f64(seed_lam), lam.shape))
+    if kind != "sets":
+      pargs = self._param_args(kind, params, lead[0])
+    grad = np.empty((lead[:-1] if reduce else lead) + (self.np,))      # reduce: a row for the batch, or a row per set
+    dz0 = np.empty(lead + (self.n,)) if want_start else None
+    dlam0 = np.empty(lead + (self.m,)) if want_start else None
+    self._exgd_grad_call(call, MEM_HOST, lead, z, lam, lb, ub, pargs, eta_x, eta_v, nsteps, sz, sl, grad, 0 if reduce else self.np, dz0, dlam0)
+    return self._present(grad=grad, dz0=dz0, dlam0=dlam0)
+
+  def _exgd_grad_probe(self, call, kind):
+    """an empty batch: the library's checks run, nothing else"""
+    d = np.zeros(1)
+    self._exgd_grad_call(call, MEM_HOST, (0, 1) if kind == "sets" else (0,), d, d, d, d, (None, 0) if kind == "rows" else (d,), 0.0, 0.0, 0, d, None, d, 0,
+                         None, None)
+
+  def _hvp_call(self, call, mem, sizes, z, lam, v, pargs, with_cost, out_z, out_p, p_stride):
+    _chk(getattr(self.lib, call)(self._h, *map(int, sizes), _addr(z), _addr(lam), _addr(v), _addr(pargs[0]), *map(int, pargs[1:]), int(bool(with_cost)),
+                                 _addr(out_z), _addr(out_p), int(p_stride), mem), call)
+
+  def _hvp(self, call, kind, z, lam, v, params, with_cost, want_z, want_p, reduce):
+    if kind == "sets":
+      pargs = (self._weight_sets(params),)
+      z = self._sets_z(z, pargs[0].shape[0])
+      lead = z.shape[:2]
+      v = self._sets3(v, *lead, self.n, "v")
+      lam = None if lam is None else self._sets3(lam, *lead, self.m, "lam")
+    else:
+      z = self._batch2(z, self.n, "z"); v = self._batch2(v, self.n, "v")
+      lead = z.shape[:1]
+      lam = None if lam is None else self._batch2(lam, self.m, "lam")
+      if v.shape[0] != lead[0] or (lam is not None and lam.shape[0] != lead[0]):
+        raise ValueError("z, lam and v must have the same batch size")
+      pargs = self._param_args(kind, params, lead[0])
+    hz = np.empty(lead + (self.n,)) if want_z else None
+    hp = np.empty((lead[:-1] if reduce else lead) + (self.np,)) if want_p else None
+    self._hvp_call(call, MEM_HOST, lead, z, lam, v, pargs, with_cost, hz, hp, 0 if reduce else self.np)
+    return self._present(hz=hz, hp=hp)
+
+  def _hvp_probe(self, call, kind):
+    d = np.zeros(1)
+    self._hvp_call(call, MEM_HOST, (0, 1) if kind == "sets" else (0,), d, None, d, (d,), 1, d, None, 0)
+
+  def exgd_grad(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam=None, params=None, reduce=False, want_start=True):
+    """myr_exgd_grad: derivative of `nsteps` extragradient steps from (z, lam) in the model parameters, contracted with the seed.
+    Returns {"grad" [B,np], or [np] = the sum over the batch with reduce=True, "dz0" [B,n], "dlam0" [B,m]} (the last two with want_start)."""
+    return self._exgd_grad("myr_exgd_grad", "rows", z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam, params, reduce, want_start)
+
+  def exgd_grad_probe(self):
+    """Raises the library's error when myr_exgd_grad is not built for this handle (an empty batch: the checks run, nothing else)."""
+    self._exgd_grad_probe("myr_exgd_grad", "rows")
+
+  def exgd_grad_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam=None, params=None, params_stride=0,
+                       dz0=None, dlam0=None):
+    """Zero-copy variant of exgd_grad: every array is a device tensor on this handle's device."""
+    self._exgd_grad_call("myr_exgd_grad", MEM_DEVICE, (B,), z, lam, lb, ub, (params, params_stride), eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
+                         dz0, dlam0)
+
+  # myr_exgd_grad_shoot: the same derivative on a SHOOTING handle (csrc/shoot_exgd_grad.h) -- the signatures, the return dict and the checks of the
+  # three methods above; myr_exgd_grad itself keeps refusing SHOOTING
+  def exgd_grad_shoot(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam=None, params=None, reduce=False, want_start=True):
+    return self._exgd_grad("myr_exgd_grad_shoot", "rows", z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam, params, reduce, want_start)
+
+  def exgd_grad_shoot_probe(self):
+    self._exgd_grad_probe("myr_exgd_grad_shoot", "rows")
+
+  def exgd_grad_shoot_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, seed_lam=None, params=None, params_stride=0,
+                             dz0=None, dlam0=None):
+    self._exgd_grad_call("myr_exgd_grad_shoot", MEM_DEVICE, (B,), z, lam, lb, ub, (params, params_stride), eta_x, eta_v, nsteps, seed_z, seed_lam, grad,
+                         grad_stride, dz0, dlam0)
+
+  def exgd_grad_node(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
+    """myr_exgd_grad_node: exgd_grad in the 4 804 shared weights of the network system (`params`: the flat vector of csrc/node_system.h's order;
+    Hermite-Simpson).  Returns {"grad" [B,np], or [np] = the sum over the batch with reduce=True, "dz0" [B,n], "dlam0" [B,m]}."""
+    return self._exgd_grad("myr_exgd_grad_node", "shared", z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam, params, reduce, want_start)
+
+  def exgd_grad_node_probe(self):
+    """Raises the library's error when myr_exgd_grad_node is not built for this handle (an empty batch: the checks run, nothing else)."""
+    self._exgd_grad_probe("myr_exgd_grad_node", "shared")
+
+  def exgd_grad_node_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None, dlam0=None):
+    """Zero-copy variant of exgd_grad_node: every array is a device tensor on this handle's device."""
+    self._exgd_grad_call("myr_exgd_grad_node", MEM_DEVICE, (B,), z, lam, lb, ub, (params,), eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride, dz0, dlam0)
+
+  # myr_exgd_grad_node_shoot: the same derivative in the weights on a SHOOTING handle (csrc/node_shoot_exgd_grad.h) -- the signatures, the return
+  # dict and the checks of the three methods above; myr_exgd_grad_node itself keeps refusing SHOOTING
+  def exgd_grad_node_shoot(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
+    return self._exgd_grad("myr_exgd_grad_node_shoot", "shared", z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam, params, reduce, want_start)
+
+  def exgd_grad_node_shoot_probe(self):
+    self._exgd_grad_probe("myr_exgd_grad_node_shoot", "shared")
+
+  def exgd_grad_node_shoot_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None,
+                                  dlam0=None):
+    self._exgd_grad_call("myr_exgd_grad_node_shoot", MEM_DEVICE, (B,), z, lam, lb, ub, (params,), eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
+                         dz0, dlam0)
+
+  # ---- E weight sets of R instances each in one call (myr_exgd_grad_node_sets, myr_hvp_node_sets) --------------------------
   def exgd_grad_node_sets(self, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, params, seed_lam=None, reduce=False, want_start=True):
     """myr_exgd_grad_node_sets: exgd_grad_node (exgd_grad_node_shoot on a SHOOTING handle) for E weight sets of R instances each in one call.
     params [E,np]; z [E,R,n], lam [E,R,m]; lb, ub, seed_z broadcast to z, seed_lam (None: zero) to lam.  Returns {"grad" [E,R,np], or [E,np] =
     per set the sum over its instances with reduce=True, "dz0" [E,R,n], "dlam0" [E,R,m]} (the last two with want_start).  Set e has the bits of
     the single-set call on that set alone."""
-    p = self._weight_sets(params)
-    E = p.shape[0]
-    z = _f64(z)
-    if z.ndim != 3 or z.shape[0] != E or z.shape[1] < 1 or z.shape[2] != self.n:
-      raise ValueError(f"z must be [E = {E}, R, {self.n}] with R >= 1")
-    R = z.shape[1]
-    lam = self._sets3(lam, E, R, self.m, "lam")
-    lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), z.shape))
-    ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), z.shape))
-    sz = np.ascontiguousarray(np.broadcast_to(_f64(seed_z), z.shape))
-    sl = None if seed_lam is None else np.ascontiguousarray(np.broadcast_to(_f64(seed_lam), lam.shape))
-    grad = np.empty((E, self.np)) if reduce else np.empty((E, R, self.np))
-    dz0 = np.empty((E, R, self.n)) if want_start else None
-    dlam0 = np.empty((E, R, self.m)) if want_start else None
-    _chk(self.lib.myr_exgd_grad_node_sets(self._h, E, R, _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(p), float(eta_x), float(eta_v), int(nsteps),
-                                          _addr(sz), _addr(sl), _addr(grad), 0 if reduce else self.np, _addr(dz0), _addr(dlam0), MEM_HOST),
-         "myr_exgd_grad_node_sets")
-    out = {"grad": grad}
-    if want_start:
-      out["dz0"] = dz0; out["dlam0"] = dlam0
-    return out
+    return self._exgd_grad("myr_exgd_grad_node_sets", "sets", z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, seed_lam, params, reduce, want_start)
 
   def exgd_grad_node_sets_device(self, E, R, z, lam, lb, ub, eta_x, eta_v, nsteps, seed_z, grad, grad_stride, params, seed_lam=None, dz0=None,
                                  dlam0=None):
     """Zero-copy variant of exgd_grad_node_sets: every array is a device tensor on this handle's device."""
-    _chk(self.lib.myr_exgd_grad_node_sets(self._h, int(E), int(R), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), float(eta_x), float(eta_v),
-                                          int(nsteps), _addr(seed_z), _addr(seed_lam), _addr(grad), int(grad_stride), _addr(dz0), _addr(dlam0),
-                                          MEM_DEVICE), "myr_exgd_grad_node_sets")
+    self._exgd_grad_call("myr_exgd_grad_node_sets", MEM_DEVICE, (E, R), z, lam, lb, ub, (params,), eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
+                         dz0, dlam0)
 
   def exgd_grad_node_sets_probe(self):
     """Raises the library's error when myr_exgd_grad_node_sets is not built for this handle (no sets: the checks run, nothing else)."""
-    d = np.zeros(1)
-    _chk(self.lib.myr_exgd_grad_node_sets(self._h, 0, 1, _addr(d), _addr(d), _addr(d), _addr(d), _addr(d), 0.0, 0.0, 0, _addr(d), None, _addr(d), 0, None,
-                                          None, MEM_HOST), "myr_exgd_grad_node_sets")
+    self._exgd_grad_probe("myr_exgd_grad_node_sets", "sets")
 
   def hvp_node_sets(self, z, lam, v, params, with_cost=True, want_z=True, want_p=False, reduce=False):
     """myr_hvp_node_sets: hvp_node for E weight sets of R instances each in one call.  params [E,np]; z, v [E,R,n]; lam [E,R,m] or None (zero
     multipliers).  Returns {"hz" [E,R,n] (with want_z), "hp" [E,R,np], or [E,np] = per set the sum over its instances with reduce=True (with
     want_p)}.  Set e has the bits of hvp_node on that set alone."""
-    p = self._weight_sets(params)
-    E = p.shape[0]
-    z = _f64(z)
-    if z.ndim != 3 or z.shape[0] != E or z.shape[1] < 1 or z.shape[2] != self.n:
-      raise ValueError(f"z must be [E = {E}, R, {self.n}] with R >= 1")
-    R = z.shape[1]
-    v = self._sets3(v, E, R, self.n, "v")
-    lam = None if lam is None else self._sets3(lam, E, R, self.m, "lam")
-    hz = np.empty((E, R, self.n)) if want_z else None
-    hp = (np.empty((E, self.np)) if reduce else np.empty((E, R, self.np))) if want_p else None
-    _chk(self.lib.myr_hvp_node_sets(self._h, E, R, _addr(z), _addr(lam), _addr(v), _addr(p), int(bool(with_cost)), _addr(hz), _addr(hp),
-                                    0 if reduce else self.np, MEM_HOST), "myr_hvp_node_sets")
-    out = {}
-    if want_z:
-      out["hz"] = hz
-    if want_p:
-      out["hp"] = hp
-    return out
+    return self._hvp("myr_hvp_node_sets", "sets", z, lam, v, params, with_cost, want_z, want_p, reduce)
 
   def hvp_node_sets_device(self, E, R, z, lam, v, params, out_z=None, out_p=None, p_stride=0, with_cost=True):
     """Zero-copy variant of hvp_node_sets: every array is a device tensor on this handle's device (lam, out_z, out_p may be None)."""
-    _chk(self.lib.myr_hvp_node_sets(self._h, int(E), int(R), _addr(z), _addr(lam), _addr(v), _addr(params), int(bool(with_cost)), _addr(out_z),
-                                    _addr(out_p), int(p_stride), MEM_DEVICE), "myr_hvp_node_sets")
+    self._hvp_call("myr_hvp_node_sets", MEM_DEVICE, (E, R), z, lam, v, (params,), with_cost, out_z, out_p, p_stride)
 
   def hvp_node_sets_probe(self):
     """Raises the library's error when myr_hvp_node_sets is not built for this handle (no sets: the checks run, nothing else)."""
-    d = np.zeros(1)
-    _chk(self.lib.myr_hvp_node_sets(self._h, 0, 1, _addr(d), None, _addr(d), _addr(d), 1, _addr(d), None, 0, MEM_HOST), "myr_hvp_node_sets")
+    self._hvp_probe("myr_hvp_node_sets", "sets")
 
   def hvp(self, z, lam, v, params=None, with_cost=True, want_z=True, want_p=False, reduce=False):
     """myr_hvp: Lagrangian Hessian-vector product.  With L = f + lam^T c (f dropped when with_cost is false) and psi = <grad_z L, v>:
     {"hz" [B,n] = grad_z psi = (d2L/dz dz) v (with want_z), "hp" [B,np] = grad_p psi = (d2L/dp dz) v, or [np] = the sum over the batch with
     reduce=True (with want_p)}.  lam None: zero multipliers."""
-    z = self._batch2(z, self.n, "z"); v = self._batch2(v, self.n, "v")
-    B = z.shape[0]
-    lam = None if lam is None else self._batch2(lam, self.m, "lam")
-    if v.shape[0] != B or (lam is not None and lam.shape[0] != B):
-      raise ValueError("z, lam and v must have the same batch size")
-    p, ps = self._params(params, B)
-    hz = np.empty((B, self.n)) if want_z else None
-    hp = (np.empty(self.np) if reduce else np.empty((B, self.np))) if want_p else None
-    _chk(self.lib.myr_hvp(self._h, B, _addr(z), _addr(lam), _addr(v), _addr(p), ps, int(bool(with_cost)), _addr(hz), _addr(hp),
-                          0 if reduce else self.np, MEM_HOST), "myr_hvp")
-    out = {}
-    if want_z:
-      out["hz"] = hz
-    if want_p:
-      out["hp"] = hp
-    return out
+    return self._hvp("myr_hvp", "rows", z, lam, v, params, with_cost, want_z, want_p, reduce)
 
   def hvp_device(self, B, z, lam, v, out_z=None, out_p=None, p_stride=0, params=None, params_stride=0, with_cost=True):
     """Zero-copy variant of hvp: every array is a device tensor on this handle's device (lam, out_z, out_p may be None); nothing is copied."""
-    _chk(self.lib.myr_hvp(self._h, int(B), _addr(z), _addr(lam), _addr(v), _addr(params), int(params_stride), int(bool(with_cost)), _addr(out_z),
-                          _addr(out_p), int(p_stride), MEM_DEVICE), "myr_hvp")
+    self._hvp_call("myr_hvp", MEM_DEVICE, (B,), z, lam, v, (params, params_stride), with_cost, out_z, out_p, p_stride)
 
   def hvp_node(self, z, lam, v, params, with_cost=True, want_z=True, want_p=False, reduce=False):
     """myr_hvp_node: hvp on a handle of the network system (HERMITE_SIMPSON or SHOOTING); `params`: the 4 804 shared weights, the flat vector of
     csrc/node_system.h's order.  Returns {"hz" [B,n] (with want_z), "hp" [B,np], or [np] = the sum over the batch with reduce=True (with want_p)}."""
-    z = self._batch2(z, self.n, "z"); v = self._batch2(v, self.n, "v")
-    B = z.shape[0]
-    lam = None if lam is None else self._batch2(lam, self.m, "lam")
-    if v.shape[0] != B or (lam is not None and lam.shape[0] != B):
-      raise ValueError("z, lam and v must have the same batch size")
-    p = None if params is None else np.ascontiguousarray(_f64(params))
-    if p is not None and p.shape != (self.np,):
-      raise ValueError(f"params must be the {self.np} shared weights")
-    hz = np.empty((B, self.n)) if want_z else None
-    hp = (np.empty(self.np) if reduce else np.empty((B, self.np))) if want_p else None
-    _chk(self.lib.myr_hvp_node(self._h, B, _addr(z), _addr(lam), _addr(v), _addr(p), int(bool(with_cost)), _addr(hz), _addr(hp),
-                               0 if reduce else self.np, MEM_HOST), "myr_hvp_node")
-    out = {}
-    if want_z:
-      out["hz"] = hz
-    if want_p:
-      out["hp"] = hp
-    return out
+    return self._hvp("myr_hvp_node", "shared", z, lam, v, params, with_cost, want_z, want_p, reduce)
 
   def hvp_node_device(self, B, z, lam, v, params, out_z=None, out_p=None, p_stride=0, with_cost=True):
     """Zero-copy variant of hvp_node: every array is a device tensor on this handle's device (lam, out_z, out_p may be None); nothing is copied."""
-    _chk(self.lib.myr_hvp_node(self._h, int(B), _addr(z), _addr(lam), _addr(v), _addr(params), int(bool(with_cost)), _addr(out_z), _addr(out_p),
-                               int(p_stride), MEM_DEVICE), "myr_hvp_node")
+    self._hvp_call("myr_hvp_node", MEM_DEVICE, (B,), z, lam, v, (params,), with_cost, out_z, out_p, p_stride)
 
   def hvp_node_probe(self):
     """Raises the library's error when myr_hvp_node is not built for this handle (an empty batch: the checks run, nothing else)."""
-    d = np.zeros(1)
-    _chk(self.lib.myr_hvp_node(self._h, 0, _addr(d), None, _addr(d), _addr(d), 1, _addr(d), None, 0, MEM_HOST), "myr_hvp_node")
+    self._hvp_probe("myr_hvp_node", "shared")
 
   def products_device(self, op, B, z, w, out, params=None, params_stride=0, add_gradf=0):
     """Zero-copy vjp ('vjp') / jvp ('jvp') on device tensors."""

@@ -1617,6 +1617,56 @@ static int check_node_weights(myr_handle h, const char* who, const double* param
   return !params && h->d.system_id == MYR_SYS_NODE_CARTPOLE ? arg_fail(who, MYR_E_ARG, "a NODE system needs its weights in `params`") : MYR_OK;
 }
 static int check_mem(const char* who, int mem) { return mem != MYR_MEM_HOST && mem != MYR_MEM_DEVICE ? arg_fail(who, MYR_E_ARG, "bad mem kind") : MYR_OK; }
+// ... and those of the derivative family (myr_exgd_grad*, myr_hvp*, myr_fit_grad*)
+static int check_handle_and_arrays(const char* who, myr_handle h, const void* p0, const void* p1, const void* p2) {
+  return !h || !p0 || !p1 || !p2 ? arg_fail(who, MYR_E_ARG, "null handle or array") : MYR_OK;
+}
+static int check_ub(const char* who, const void* ub) { return !ub ? arg_fail(who, MYR_E_ARG, "null ub") : MYR_OK; }
+static int check_steps_and_seed(const char* who, int nsteps, const void* seed_z, const void* grad) {
+  if (nsteps < 0) return arg_fail(who, MYR_E_ARG, "negative nsteps");
+  return !seed_z || !grad ? arg_fail(who, MYR_E_ARG, "null seed_z or grad") : MYR_OK;
+}
+// the stride of a result with np entries to a row (`name`: grad_stride, p_stride): np, a row per `unit`, or 0 -- `zero` says what the rows are summed to
+static int check_row_stride(myr_handle h, const char* who, const char* name, int stride, const char* zero, const char* unit) {
+  if (stride == 0 || stride == h->dims.np) return MYR_OK;
+  return arg_fail(who, MYR_E_ARG, (std::string(name) + " must be 0 (" + zero + ") or np (a row per " + unit + ")").c_str());
+}
+static const char *const ROW_SUM_BATCH = "one row: the sum over the batch", *const ROW_SUM_SETS = "a row per set: the sum over its instances";
+static int check_sets(const char* who, int E, int R) {
+  return E < 0 || R < 1 || (long)E * R > 0x7fffffffL ? arg_fail(who, MYR_E_ARG, "bad sizes (E >= 0 sets of R >= 1 instances, E * R an int)") : MYR_OK;
+}
+static int check_weight_sets(const char* who, const double* params) {
+  return !params ? arg_fail(who, MYR_E_ARG, "null params (the [E][np] weight sets)") : MYR_OK;
+}
+// the network calls: another system is sent to `use`; the transcriptions they have are named in `built`
+static int check_is_node(myr_handle h, const char* who, const char* use) {
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE) return MYR_OK;
+  return arg_fail(who, MYR_E_UNSUPPORTED, (std::string("this handle's system is not the network system; use ") + use).c_str());
+}
+static int check_node_not_trapezoidal(myr_handle h, const char* who, const char* built) {
+  if (h->d.transcription == MYR_TR_HERMITE_SIMPSON || h->d.transcription == MYR_TR_SHOOTING) return MYR_OK;
+  return arg_fail(who, MYR_E_UNSUPPORTED, (std::string("TRAPEZOIDAL is not built for the network system; ") + built + " only").c_str());
+}
+// does the LDS carve of the network kernel this handle would run fit?  The SHOOTING kernels come in two forms, <2> for RK4 (two control rows a step)
+// and <1>; Hermite-Simpson has a bound for the reverse sweep only
+enum { NODE_LDS_EXGD_GRAD = 0, NODE_LDS_HVP = 1 };
+static int check_node_lds(myr_handle h, const char* who, int which) {
+  const int I = h->d.intervals, cpi = h->d.controls_per_interval;
+  const bool shoot = h->d.transcription == MYR_TR_SHOOTING, rk4 = h->d.integration_method == MYR_INT_RK4;
+  size_t lds = 0;
+  const char* what = "";
+  if (which == NODE_LDS_HVP && shoot) {
+    lds = rk4 ? node_hvp_shoot_lds_bytes<2>(I, cpi) : node_hvp_shoot_lds_bytes<1>(I, cpi);
+    what = "intervals x controls_per_interval too large for the LDS-resident pair records beside the weight copy";
+  } else if (which == NODE_LDS_EXGD_GRAD && shoot) {
+    lds = rk4 ? node_shoot_exgd_grad_lds_bytes<2>(I, cpi) : node_shoot_exgd_grad_lds_bytes<1>(I, cpi);
+    what = "intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy";
+  } else if (which == NODE_LDS_EXGD_GRAD) {
+    lds = node_exgd_grad_lds_bytes(I);
+    what = "intervals too large for the LDS-resident reverse sweep beside the weight copy";
+  }
+  return lds > 160 * 1024 ? arg_fail(who, MYR_E_CAPACITY, what) : MYR_OK;
+}
 // doubles behind `params`: none, one shared set, or a set per instance
 static size_t n_params(myr_handle h, const double* params, int stride, int B) { return params ? (stride ? (size_t)B * h->dims.np : (size_t)h->dims.np) : 0; }
 
@@ -1656,7 +1706,7 @@ static int dispatch_products(myr_handle h, const ProdArgs& a) {
 
 static int check_products_args(myr_handle h, const char* who, int32_t B, const void* p0, const void* p1, const void* p2,
                                const double* params, int32_t params_stride) {
-  if (!h || !p0 || !p1 || !p2) return arg_fail(who, MYR_E_ARG, "null handle or array");
+  if (int rc = check_handle_and_arrays(who, h, p0, p1, p2)) return rc;
   if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
   if (int rc = check_batch(who, B)) return rc;
   if (int rc = check_stride(h, who, params, params_stride)) return rc;
@@ -2306,25 +2356,12 @@ extern "C" int myr_rollout(myr_handle h, int32_t B, int32_t num_steps, int32_t u
   return st.finish();
 }
 
-// Sum of the per-trajectory gradient rows in a fixed order: block k owns entry k; thread t adds rows t, t + 256, ... in ascending order, then the
-// 256 partial sums meet in a fixed tree.  No atomics: the same bits on every call.  (Neighbouring threads read rows np apart -- not coalesced: the
-// kernel reads B * np doubles once, and the rows keep the layout the caller gets with grad_stride == np.)
-static __global__ __launch_bounds__(256) void fit_reduce_kernel(int B, int np, const double* __restrict__ rows, double* __restrict__ out) {
-  __shared__ double part[256];
-  const int k = blockIdx.x, t = threadIdx.x;
-  double a = 0.0;
-  for (long b = t; b < B; b += 256) a += rows[b * np + k];
-  part[t] = a;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) part[t] += part[t + w];
-    __syncthreads();
-  }
-  if (t == 0) out[k] = part[0];
-}
-
-// the same sum for each of E parameter sets of R rows (rows [E][R][np] -> out [E][np]): block (k, e) is fit_reduce_kernel's block k on the rows of set e
-// alone -- thread t adds rows t, t + 256, ... of that set, then the same tree --, so a set's sums have the bits of a call on that set alone.  Grid: np * E.
+// Sum of the per-trajectory gradient rows in a fixed order, for each of E parameter sets of R rows (rows [E][R][np] -> out [E][np]; grid np * E): block
+// (k, e) owns entry k of set e; thread t adds rows t, t + 256, ... of that set in ascending order, then the 256 partial sums meet in a fixed tree.  No
+// atomics: the same bits on every call, and a set's sums have the bits of a call on that set alone.  The sum over a whole batch is the call with one set
+// (E = 1, R = B): block k then runs the additions of the one-set kernel this replaces (out[k] = sum over b of rows[b * np + k], thread t taking b = t,
+// t + 256, ..., the same tree) in the same order, so those bits are unchanged.  (Neighbouring threads read rows np apart -- not coalesced: the kernel
+// reads E * R * np doubles once, and the rows keep the layout the caller gets with grad_stride == np.)
 static __global__ __launch_bounds__(256) void fit_reduce_sets_kernel(int R, int np, const double* __restrict__ rows, double* __restrict__ out) {
   __shared__ double part[256];
   const int k = (int)(blockIdx.x % (unsigned)np), t = threadIdx.x;
@@ -2405,8 +2442,7 @@ extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t 
   if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
   if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
   if (B < 0 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_grad: bad sizes");
-  if (grad_stride != 0 && grad_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_fit_grad: grad_stride must be 0 (one row: the sum over the batch) or np (a row per trajectory)");
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_BATCH, "trajectory")) return rc;
   if (int rc = check_stride(h, who, params, params_stride)) return rc;
   if (int rc = check_node_weights(h, who, params)) return rc;
   if (h->d.system_id == MYR_SYS_NODE_CARTPOLE && params_stride != 0)
@@ -2435,8 +2471,7 @@ extern "C" int myr_fit_grad_sets(myr_handle h, int32_t E, int32_t R, int32_t num
   if (!h || !xs_obs || !us || !params) return fail(MYR_E_ARG, "myr_fit_grad_sets: null handle, xs_obs, us or params");
   if (!loss && !grad) return fail(MYR_E_ARG, "myr_fit_grad_sets: loss and grad are both null");
   if (E < 0 || R < 1 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_grad_sets: bad sizes");
-  if (grad_stride != 0 && grad_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_fit_grad_sets: grad_stride must be 0 (a row per set: the sum over its trajectories) or np (a row per trajectory)");
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, "a row per set: the sum over its trajectories", "trajectory")) return rc;
   if (data_shared != 0 && data_shared != 1) return fail(MYR_E_ARG, "myr_fit_grad_sets: data_shared must be 0 (data per set) or 1 (one set of data, read by every set)");
   if (int rc = check_mem(who, mem)) return rc;
   if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
@@ -2474,7 +2509,7 @@ static int exgd_grad_chunk(myr_handle h, int B, int nsteps, size_t* per) {
 
 // device pointers throughout (a.hist, a.chunk, under EXGD_GRAD_SHOOT a.work and a.Pp and, for the batch sum, a.rows are set here); grad: [B][np] rows
 // (grad_stride == np) or, per weight set of a.R instances, the sum of its rows in fit_reduce_sets_kernel's fixed order: [B / R][np] (the closed-form
-// routes and the single-set network calls have R = B: one row, the bits of fit_reduce_kernel)
+// routes and the single-set network calls have R = B: one row, the sum over the batch)
 enum { EXGD_GRAD_CLOSED_FORM = 0, EXGD_GRAD_NODE = 1, EXGD_GRAD_NODE_SHOOT = 2, EXGD_GRAD_SHOOT = 3 };      // which kernel family runs the sweep
 static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, int route) {
   const myr_dims& dm = h->dims;
@@ -2506,7 +2541,7 @@ static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int gr
   return rc ? rc : rc_end;
 }
 
-// what the four myr_exgd_grad* entry points share behind their own checks: the staging, the sweep of `route`, the copies back.
+// what the five myr_exgd_grad* entry points share behind their own checks: the staging, the sweep of `route`, the copies back.
 // n_param_doubles: what `params` holds (a row per instance, or one shared set; the network routes: a set for every R instances, B / R sets)
 static int run_exgd_grad(myr_handle h, int route, int mem, int B, int R, const double* z, const double* lam, const double* lb, const double* ub,
                          const double* params, size_t n_param_doubles, int pstride, double eta_x, double eta_v, int nsteps, const double* seed_z,
@@ -2539,11 +2574,9 @@ extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const dou
                              double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
   const char* who = "myr_exgd_grad";
   if (int rc = check_products_args(h, who, B, z, lam, lb, params, params_stride)) return rc;
-  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad: null ub");
-  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad: negative nsteps");
-  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad: null seed_z or grad");
-  if (grad_stride != 0 && grad_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_exgd_grad: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_ub(who, ub)) return rc;
+  if (int rc = check_steps_and_seed(who, nsteps, seed_z, grad)) return rc;
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_BATCH, "instance")) return rc;
   if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: an elastic twin has no model of its own to differentiate; use the handle of its system");
   if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
     return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: the network system is not built (second derivatives in 4 804 weights)");
@@ -2559,21 +2592,17 @@ extern "C" int myr_exgd_grad_node(myr_handle h, int32_t B, const double* z, cons
                                   double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam, double* grad,
                                   int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
   const char* who = "myr_exgd_grad_node";
-  if (!h || !z || !lam || !lb) return fail(MYR_E_ARG, "myr_exgd_grad_node: null handle or array");
-  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_node: null ub");
+  if (int rc = check_handle_and_arrays(who, h, z, lam, lb)) return rc;
+  if (int rc = check_ub(who, ub)) return rc;
   if (int rc = check_batch(who, B)) return rc;
-  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_node: negative nsteps");
-  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_node: null seed_z or grad");
-  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
-    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node: this handle's system is not the network system; use myr_exgd_grad");
+  if (int rc = check_steps_and_seed(who, nsteps, seed_z, grad)) return rc;
+  if (int rc = check_is_node(h, who, "myr_exgd_grad")) return rc;
   if (h->d.transcription != MYR_TR_HERMITE_SIMPSON)
-    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node: HERMITE_SIMPSON only, the one transcription myr_vjp / myr_exgd build for the network system");
+    return arg_fail(who, MYR_E_UNSUPPORTED, "HERMITE_SIMPSON only, the one transcription myr_vjp / myr_exgd build for the network system");
   if (int rc = check_node_weights(h, who, params)) return rc;
-  if (grad_stride != 0 && grad_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_exgd_grad_node: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_BATCH, "instance")) return rc;
   if (int rc = check_mem(who, mem)) return rc;
-  if (node_exgd_grad_lds_bytes(h->d.intervals) > 160 * 1024)
-    return fail(MYR_E_CAPACITY, "myr_exgd_grad_node: intervals too large for the LDS-resident reverse sweep beside the weight copy");
+  if (int rc = check_node_lds(h, who, NODE_LDS_EXGD_GRAD)) return rc;
   return run_exgd_grad(h, EXGD_GRAD_NODE, mem, B, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
                        dz0, dlam0);
 }
@@ -2583,27 +2612,18 @@ extern "C" int myr_exgd_grad_node_shoot(myr_handle h, int32_t B, const double* z
                                         const double* params, double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam,
                                         double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
   const char* who = "myr_exgd_grad_node_shoot";
-  if (!h || !z || !lam || !lb) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: null handle or array");
-  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: null ub");
+  if (int rc = check_handle_and_arrays(who, h, z, lam, lb)) return rc;
+  if (int rc = check_ub(who, ub)) return rc;
   if (int rc = check_batch(who, B)) return rc;
-  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: negative nsteps");
-  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: null seed_z or grad");
-  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
-    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: this handle's system is not the network system; use myr_exgd_grad_shoot");
+  if (int rc = check_steps_and_seed(who, nsteps, seed_z, grad)) return rc;
+  if (int rc = check_is_node(h, who, "myr_exgd_grad_shoot")) return rc;
   if (h->d.transcription == MYR_TR_HERMITE_SIMPSON)
-    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: this handle's transcription is HERMITE_SIMPSON, not SHOOTING; use myr_exgd_grad_node");
-  if (h->d.transcription != MYR_TR_SHOOTING)
-    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_shoot: TRAPEZOIDAL is not built for the network system; SHOOTING only");
+    return arg_fail(who, MYR_E_UNSUPPORTED, "this handle's transcription is HERMITE_SIMPSON, not SHOOTING; use myr_exgd_grad_node");
+  if (int rc = check_node_not_trapezoidal(h, who, "SHOOTING")) return rc;
   if (int rc = check_node_weights(h, who, params)) return rc;
-  if (grad_stride != 0 && grad_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_exgd_grad_node_shoot: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_BATCH, "instance")) return rc;
   if (int rc = check_mem(who, mem)) return rc;
-  {
-    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
-    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_shoot_exgd_grad_lds_bytes<2>(I, cpi) : node_shoot_exgd_grad_lds_bytes<1>(I, cpi);
-    if (lds > 160 * 1024)
-      return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_shoot: intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy");
-  }
+  if (int rc = check_node_lds(h, who, NODE_LDS_EXGD_GRAD)) return rc;
   return run_exgd_grad(h, EXGD_GRAD_NODE_SHOOT, mem, B, B, z, lam, lb, ub, params, (size_t)h->dims.np, 0, eta_x, eta_v, nsteps, seed_z, seed_lam, grad,
                        grad_stride, dz0, dlam0);
 }
@@ -2614,29 +2634,17 @@ extern "C" int myr_exgd_grad_node_sets(myr_handle h, int32_t E, int32_t R, const
                                        const double* params, double eta_x, double eta_v, int32_t nsteps, const double* seed_z, const double* seed_lam,
                                        double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
   const char* who = "myr_exgd_grad_node_sets";
-  if (!h || !z || !lam || !lb) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null handle or array");
-  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null ub");
-  if (E < 0 || R < 1 || (long)E * R > 0x7fffffffL) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: bad sizes (E >= 0 sets of R >= 1 instances, E * R an int)");
-  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: negative nsteps");
-  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null seed_z or grad");
-  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
-    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_sets: this handle's system is not the network system; use myr_exgd_grad or myr_exgd_grad_shoot");
-  if (h->d.transcription != MYR_TR_HERMITE_SIMPSON && h->d.transcription != MYR_TR_SHOOTING)
-    return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_node_sets: TRAPEZOIDAL is not built for the network system; HERMITE_SIMPSON and SHOOTING only");
-  if (!params) return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: null params (the [E][np] weight sets)");
-  if (grad_stride != 0 && grad_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_exgd_grad_node_sets: grad_stride must be 0 (a row per set: the sum over its instances) or np (a row per instance)");
+  if (int rc = check_handle_and_arrays(who, h, z, lam, lb)) return rc;
+  if (int rc = check_ub(who, ub)) return rc;
+  if (int rc = check_sets(who, E, R)) return rc;
+  if (int rc = check_steps_and_seed(who, nsteps, seed_z, grad)) return rc;
+  if (int rc = check_is_node(h, who, "myr_exgd_grad or myr_exgd_grad_shoot")) return rc;
+  if (int rc = check_node_not_trapezoidal(h, who, "HERMITE_SIMPSON and SHOOTING")) return rc;
+  if (int rc = check_weight_sets(who, params)) return rc;
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_SETS, "instance")) return rc;
   if (int rc = check_mem(who, mem)) return rc;
-  const bool shoot = h->d.transcription == MYR_TR_SHOOTING;
-  if (shoot) {
-    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
-    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_shoot_exgd_grad_lds_bytes<2>(I, cpi) : node_shoot_exgd_grad_lds_bytes<1>(I, cpi);
-    if (lds > 160 * 1024)
-      return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_sets: intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy");
-  } else if (node_exgd_grad_lds_bytes(h->d.intervals) > 160 * 1024) {
-    return fail(MYR_E_CAPACITY, "myr_exgd_grad_node_sets: intervals too large for the LDS-resident reverse sweep beside the weight copy");
-  }
-  return run_exgd_grad(h, shoot ? EXGD_GRAD_NODE_SHOOT : EXGD_GRAD_NODE, mem, E * R, R, z, lam, lb, ub, params, (size_t)E * h->dims.np, 0, eta_x, eta_v, nsteps,
+  if (int rc = check_node_lds(h, who, NODE_LDS_EXGD_GRAD)) return rc;
+  return run_exgd_grad(h, h->d.transcription == MYR_TR_SHOOTING ? EXGD_GRAD_NODE_SHOOT : EXGD_GRAD_NODE, mem, E * R, R, z, lam, lb, ub, params, (size_t)E * h->dims.np, 0, eta_x, eta_v, nsteps,
                        seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
 }
 
@@ -2646,11 +2654,9 @@ extern "C" int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, con
                                    double* grad, int32_t grad_stride, double* dz0, double* dlam0, int32_t mem) {
   const char* who = "myr_exgd_grad_shoot";
   if (int rc = check_products_args(h, who, B, z, lam, lb, params, params_stride)) return rc;
-  if (!ub) return fail(MYR_E_ARG, "myr_exgd_grad_shoot: null ub");
-  if (nsteps < 0) return fail(MYR_E_ARG, "myr_exgd_grad_shoot: negative nsteps");
-  if (!seed_z || !grad) return fail(MYR_E_ARG, "myr_exgd_grad_shoot: null seed_z or grad");
-  if (grad_stride != 0 && grad_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_exgd_grad_shoot: grad_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_ub(who, ub)) return rc;
+  if (int rc = check_steps_and_seed(who, nsteps, seed_z, grad)) return rc;
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_BATCH, "instance")) return rc;
   if (h->d.system_id >= 100)
     return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad_shoot: an elastic twin has no model of its own to differentiate; use the handle of its system");
   if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
@@ -2662,12 +2668,15 @@ extern "C" int myr_exgd_grad_shoot(myr_handle h, int32_t B, const double* z, con
                        seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
 }
 
-// device pointers throughout (a.hist, a.side, a.Pp and, for the batch sum, a.rows are set here); out_p: [B][np] rows (p_stride == np), their sum, or null
-static int dispatch_hvp(myr_handle h, HvpArgs a, double* out_p, int p_stride) {
+// device pointers throughout (a.hist, a.side, a.Pp and, for the sums, a.rows are set here); out_p: [B][np] rows (p_stride == np), per weight set of a.R
+// instances the sum of its rows in fit_reduce_sets_kernel's fixed order, [B / R][np] (myr_hvp and myr_hvp_node have R = B: one row), or null
+enum { HVP_CLOSED_FORM = 0, HVP_NODE = 1 };      // which kernel family runs the product (node_hvp.h for the network system)
+static int dispatch_hvp(myr_handle h, HvpArgs a, double* out_p, int p_stride, int route) {
   const myr_dims& dm = h->dims;
-  const bool shoot = h->d.transcription == MYR_TR_SHOOTING;
+  const bool shoot = h->d.transcription == MYR_TR_SHOOTING, node = route == HVP_NODE;
+  const int kt = !node ? MYR_K_PROD : shoot ? MYR_K_HVP_NODE_SHOOT : MYR_K_HVP_NODE;
   DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
-  if (shoot) {      // per (instance, interval) pair: the history of its steps and its side record (ShootHvp::hist_doubles, side_doubles), a column per lane
+  if (shoot && !node) {      // per (instance, interval) pair: the history of its steps and its side record (ShootHvp::hist_doubles, side_doubles), a column per lane
     const long I = h->d.intervals, cpi = h->d.controls_per_interval, M = h->d.integration_method == MYR_INT_RK4 ? 2 : 1;
     const long P = (long)a.B * I;
     if (P > (1L << 30)) return fail(MYR_E_CAPACITY, "myr_hvp: more than 2^30 (instance, interval) pairs in one call");
@@ -2679,12 +2688,38 @@ static int dispatch_hvp(myr_handle h, HvpArgs a, double* out_p, int p_stride) {
   if (out_p && p_stride) a.rows = out_p;
   else if (out_p) st.scratch(a.rows, (size_t)a.B * dm.np);
   if (int rc = st.commit()) return rc;
-  if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
-  const int rc = shoot ? for_system(h->d.system_id, true, [&](auto t) { return hvp_shoot_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; })
-                       : for_system(h->d.system_id, true, [&](auto t) { return hvp_colloc_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
-  if (!rc && out_p && !p_stride) hipLaunchKernelGGL(fit_reduce_kernel, dim3((unsigned)dm.np), dim3(256), 0, h->stream, a.B, (int)dm.np, (const double*)a.rows, out_p);
-  const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
+  if (int rc = timed_begin(h, kt)) return rc;
+  const int rc = node ? (shoot ? hvp_node_shoot_for_system<SysNODE_CARTPOLE>(h, a) : hvp_node_colloc_for_system<SysNODE_CARTPOLE>(h, a))
+                 : shoot ? for_system(h->d.system_id, true, [&](auto t) { return hvp_shoot_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; })
+                         : for_system(h->d.system_id, true, [&](auto t) { return hvp_colloc_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+  if (!rc && out_p && !p_stride)
+    hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)dm.np * (unsigned)(a.B / a.R)), dim3(256), 0, h->stream, a.R, (int)dm.np, (const double*)a.rows,
+                       out_p);
+  const int rc_end = timed_end(h, kt);          // on every path
   return rc ? rc : rc_end;
+}
+
+// what myr_hvp, myr_hvp_node and myr_hvp_node_sets share behind their own checks: the staging, the product of `route`, the copies back.  B instances;
+// n_param_doubles: what `params` holds (a row per instance or one shared set; the network route: a weight set for every R instances, B / R sets)
+static int run_hvp(myr_handle h, int route, int mem, int B, int R, const double* z, const double* lam, const double* v, const double* params,
+                   size_t n_param_doubles, int pstride, int with_cost, double* out_z, double* out_p, int p_stride) {
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t nz = (size_t)B * dm.n;
+  HvpArgs a{};
+  a.B = B; a.R = R; a.pstride = pstride; a.with_cost = with_cost != 0;
+  double* gp = nullptr;
+  DevStage st = call_stage(h, mem);
+  st.in(a.z, z, nz);
+  st.in(a.lam, lam, (size_t)B * dm.m);
+  st.in(a.v, v, nz);
+  st.in(a.params, params, n_param_doubles);
+  st.out(a.out_z, out_z, nz);
+  st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)(B / R) * dm.np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_hvp(h, a, gp, p_stride, route)) return rc;
+  return st.finish();
 }
 
 extern "C" int myr_hvp(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params, int32_t params_stride,
@@ -2697,90 +2732,27 @@ extern "C" int myr_hvp(myr_handle h, int32_t B, const double* z, const double* l
   if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
     return fail(MYR_E_UNSUPPORTED, "myr_hvp: the network system is not built (second derivatives in 4 804 weights)");
   if (int rc = check_batch(who, B)) return rc;
-  if (p_stride != 0 && p_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_hvp: p_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_row_stride(h, who, "p_stride", p_stride, ROW_SUM_BATCH, "instance")) return rc;
   if (int rc = check_stride(h, who, params, params_stride)) return rc;
   if (int rc = check_mem(who, mem)) return rc;
-  if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t nz = (size_t)B * dm.n;
-  HvpArgs a{};
-  a.B = B; a.pstride = params_stride; a.with_cost = with_cost != 0;
-  double* gp = nullptr;
-  DevStage st = call_stage(h, mem);
-  st.in(a.z, z, nz);
-  st.in(a.lam, lam, (size_t)B * dm.m);
-  st.in(a.v, v, nz);
-  st.in(a.params, params, n_params(h, params, params_stride, B));
-  st.out(a.out_z, out_z, nz);
-  st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)dm.np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_hvp(h, a, gp, p_stride)) return rc;
-  return st.finish();
+  return run_hvp(h, HVP_CLOSED_FORM, mem, B, B, z, lam, v, params, n_params(h, params, params_stride, B), params_stride, with_cost, out_z, out_p, p_stride);
 }
 
-// the product for the network system (node_hvp.h): device pointers throughout (for the batch sum a.rows is set here); out_p as in dispatch_hvp
-static int dispatch_hvp_node(myr_handle h, HvpArgs a, double* out_p, int p_stride) {
-  const myr_dims& dm = h->dims;
-  const bool shoot = h->d.transcription == MYR_TR_SHOOTING;
-  const int kt = shoot ? MYR_K_HVP_NODE_SHOOT : MYR_K_HVP_NODE;
-  DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
-  if (out_p && p_stride) a.rows = out_p;
-  else if (out_p) st.scratch(a.rows, (size_t)a.B * dm.np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = timed_begin(h, kt)) return rc;
-  const int rc = shoot ? hvp_node_shoot_for_system<SysNODE_CARTPOLE>(h, a) : hvp_node_colloc_for_system<SysNODE_CARTPOLE>(h, a);
-  if (!rc && out_p && !p_stride)      // per weight set the sum of its a.R rows, [B / R][np] (one set: the bits of fit_reduce_kernel)
-    hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)dm.np * (unsigned)(a.B / a.R)), dim3(256), 0, h->stream, a.R, (int)dm.np, (const double*)a.rows,
-                       out_p);
-  const int rc_end = timed_end(h, kt);          // on every path
-  return rc ? rc : rc_end;
-}
-
-// what myr_hvp_node and myr_hvp_node_sets share behind their own checks: B instances, a weight set for every R of them (params [B / R][np])
-static int run_hvp_node(myr_handle h, int mem, int B, int R, const double* z, const double* lam, const double* v, const double* params, int with_cost,
-                        double* out_z, double* out_p, int p_stride) {
-  if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t nz = (size_t)B * dm.n;
-  HvpArgs a{};
-  a.B = B; a.R = R; a.with_cost = with_cost != 0;
-  double* gp = nullptr;
-  DevStage st = call_stage(h, mem);
-  st.in(a.z, z, nz);
-  st.in(a.lam, lam, (size_t)B * dm.m);
-  st.in(a.v, v, nz);
-  st.in(a.params, params, (size_t)(B / R) * dm.np);
-  st.out(a.out_z, out_z, nz);
-  st.out(gp, out_p, p_stride ? (size_t)B * dm.np : (size_t)(B / R) * dm.np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_hvp_node(h, a, gp, p_stride)) return rc;
-  return st.finish();
-}
+// the product for the network system (node_hvp.h): one shared weight set (no params_stride), HERMITE_SIMPSON or SHOOTING
 
 extern "C" int myr_hvp_node(myr_handle h, int32_t B, const double* z, const double* lam, const double* v, const double* params, int32_t with_cost,
                             double* out_z, double* out_p, int32_t p_stride, int32_t mem) {
   const char* who = "myr_hvp_node";
   if (!h || !z || !v) return fail(MYR_E_ARG, "myr_hvp_node: null handle, z or v");
   if (!out_z && !out_p) return fail(MYR_E_ARG, "myr_hvp_node: both outputs are null");
-  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
-    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node: this handle's system is not the network system; use myr_hvp");
-  if (h->d.transcription != MYR_TR_HERMITE_SIMPSON && h->d.transcription != MYR_TR_SHOOTING)
-    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node: TRAPEZOIDAL is not built for the network system; HERMITE_SIMPSON and SHOOTING only");
+  if (int rc = check_is_node(h, who, "myr_hvp")) return rc;
+  if (int rc = check_node_not_trapezoidal(h, who, "HERMITE_SIMPSON and SHOOTING")) return rc;
   if (int rc = check_node_weights(h, who, params)) return rc;
   if (int rc = check_batch(who, B)) return rc;
-  if (p_stride != 0 && p_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_hvp_node: p_stride must be 0 (one row: the sum over the batch) or np (a row per instance)");
+  if (int rc = check_row_stride(h, who, "p_stride", p_stride, ROW_SUM_BATCH, "instance")) return rc;
   if (int rc = check_mem(who, mem)) return rc;
-  if (h->d.transcription == MYR_TR_SHOOTING) {
-    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
-    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_hvp_shoot_lds_bytes<2>(I, cpi) : node_hvp_shoot_lds_bytes<1>(I, cpi);
-    if (lds > 160 * 1024)
-      return fail(MYR_E_CAPACITY, "myr_hvp_node: intervals x controls_per_interval too large for the LDS-resident pair records beside the weight copy");
-  }
-  return run_hvp_node(h, mem, B, B, z, lam, v, params, with_cost, out_z, out_p, p_stride);
+  if (int rc = check_node_lds(h, who, NODE_LDS_HVP)) return rc;
+  return run_hvp(h, HVP_NODE, mem, B, B, z, lam, v, params, (size_t)h->dims.np, 0, with_cost, out_z, out_p, p_stride);
 }
 
 // ... and for E weight sets of R instances each in one call: myr_hvp_node is its E = 1, R = B case.  Set e has the bits of myr_hvp_node on that set alone
@@ -2789,22 +2761,14 @@ extern "C" int myr_hvp_node_sets(myr_handle h, int32_t E, int32_t R, const doubl
   const char* who = "myr_hvp_node_sets";
   if (!h || !z || !v) return fail(MYR_E_ARG, "myr_hvp_node_sets: null handle, z or v");
   if (!out_z && !out_p) return fail(MYR_E_ARG, "myr_hvp_node_sets: both outputs are null");
-  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
-    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node_sets: this handle's system is not the network system; use myr_hvp");
-  if (h->d.transcription != MYR_TR_HERMITE_SIMPSON && h->d.transcription != MYR_TR_SHOOTING)
-    return fail(MYR_E_UNSUPPORTED, "myr_hvp_node_sets: TRAPEZOIDAL is not built for the network system; HERMITE_SIMPSON and SHOOTING only");
-  if (!params) return fail(MYR_E_ARG, "myr_hvp_node_sets: null params (the [E][np] weight sets)");
-  if (E < 0 || R < 1 || (long)E * R > 0x7fffffffL) return fail(MYR_E_ARG, "myr_hvp_node_sets: bad sizes (E >= 0 sets of R >= 1 instances, E * R an int)");
-  if (p_stride != 0 && p_stride != h->dims.np)
-    return fail(MYR_E_ARG, "myr_hvp_node_sets: p_stride must be 0 (a row per set: the sum over its instances) or np (a row per instance)");
+  if (int rc = check_is_node(h, who, "myr_hvp")) return rc;
+  if (int rc = check_node_not_trapezoidal(h, who, "HERMITE_SIMPSON and SHOOTING")) return rc;
+  if (int rc = check_weight_sets(who, params)) return rc;
+  if (int rc = check_sets(who, E, R)) return rc;
+  if (int rc = check_row_stride(h, who, "p_stride", p_stride, ROW_SUM_SETS, "instance")) return rc;
   if (int rc = check_mem(who, mem)) return rc;
-  if (h->d.transcription == MYR_TR_SHOOTING) {
-    const int I = h->d.intervals, cpi = h->d.controls_per_interval;
-    const size_t lds = h->d.integration_method == MYR_INT_RK4 ? node_hvp_shoot_lds_bytes<2>(I, cpi) : node_hvp_shoot_lds_bytes<1>(I, cpi);
-    if (lds > 160 * 1024)
-      return fail(MYR_E_CAPACITY, "myr_hvp_node_sets: intervals x controls_per_interval too large for the LDS-resident pair records beside the weight copy");
-  }
-  return run_hvp_node(h, mem, E * R, R, z, lam, v, params, with_cost, out_z, out_p, p_stride);
+  if (int rc = check_node_lds(h, who, NODE_LDS_HVP)) return rc;
+  return run_hvp(h, HVP_NODE, mem, E * R, R, z, lam, v, params, (size_t)E * h->dims.np, 0, with_cost, out_z, out_p, p_stride);
 }
 
 extern "C" int myr_fbsm(myr_handle h, int32_t B, int32_t N, const double* x0, const double* adj_T, const double* params,

@@ -208,9 +208,28 @@ _ORDER = {
   "myr_fit_grad": ("B", "num_steps", "u_rows", "xs_obs", "us", "wt", "params", "stride", "loss", "grad", "grad_stride", "mem"),
   "myr_fbsm": ("B", "N", "x0", "adj_T", "params", "stride", "clip_lo", "clip_hi", "bang", "delta", "max_sweeps", "xs", "us", "adjs", "sweeps", "mem"),
 }
+# the derivative family: the sets calls take E, R where the others take B
+_EXGD_GRAD_TAIL = ("eta_x", "eta_v", "nsteps", "seed_z", "seed_lam", "grad", "grad_stride", "dz0", "dlam0", "mem")
+_HVP_TAIL = ("with_cost", "out_z", "out_p", "p_stride", "mem")
+_ORDER.update({
+  "myr_exgd_grad": ("B", "z", "lam", "lb", "ub", "params", "stride") + _EXGD_GRAD_TAIL,
+  "myr_exgd_grad_shoot": ("B", "z", "lam", "lb", "ub", "params", "stride") + _EXGD_GRAD_TAIL,
+  "myr_exgd_grad_node": ("B", "z", "lam", "lb", "ub", "params") + _EXGD_GRAD_TAIL,
+  "myr_exgd_grad_node_shoot": ("B", "z", "lam", "lb", "ub", "params") + _EXGD_GRAD_TAIL,
+  "myr_exgd_grad_node_sets": ("E", "R", "z", "lam", "lb", "ub", "params") + _EXGD_GRAD_TAIL,
+  "myr_hvp": ("B", "z", "lam", "v", "params", "stride") + _HVP_TAIL,
+  "myr_hvp_node": ("B", "z", "lam", "v", "params") + _HVP_TAIL,
+  "myr_hvp_node_sets": ("E", "R", "z", "lam", "v", "params") + _HVP_TAIL,
+  "myr_fit_grad_sets": ("E", "R", "num_steps", "u_rows", "xs_obs", "us", "data_shared", "wt", "params", "loss", "grad", "grad_stride", "mem"),
+})
+_EXGD_GRAD_EPS = ("myr_exgd_grad", "myr_exgd_grad_shoot", "myr_exgd_grad_node", "myr_exgd_grad_node_shoot", "myr_exgd_grad_node_sets")
+_HVP_EPS = ("myr_hvp", "myr_hvp_node", "myr_hvp_node_sets")
+_SETS_EPS = ("myr_exgd_grad_node_sets", "myr_hvp_node_sets", "myr_fit_grad_sets")
 _OUTPUTS = {"myr_eval": ("f", "g", "c", "j"), "myr_vjp": ("out",), "myr_jvp": ("out",), "myr_exgd": ("z", "lam"), "myr_rollout": ("xs", "cost"),
             "myr_solve": ("z", "lam", "cost", "status", "iters", "kkt"), "myr_solve_x0": ("z", "lam", "cost", "status", "iters", "kkt"),
-            "myr_fit_grad": ("loss", "grad"), "myr_fbsm": ("xs", "us", "adjs", "sweeps")}
+            "myr_fit_grad": ("loss", "grad"), "myr_fbsm": ("xs", "us", "adjs", "sweeps"), "myr_fit_grad_sets": ("loss", "grad")}
+_OUTPUTS.update({ep: ("grad", "dz0", "dlam0") for ep in _EXGD_GRAD_EPS})
+_OUTPUTS.update({ep: ("out_z", "out_p") for ep in _HVP_EPS})
 
 
 def _abi_call(ep, eng, a, handle=True):
@@ -328,6 +347,49 @@ def test_host_and_device_arrays_give_the_same_bits():
         _same_bits("myr_solve_x0", eng, cart(N), dict(common, x0s=x0, g0=g0, g1=g1, lb=tr.bounds[:, 0].copy(), ub=tr.bounds[:, 1].copy(), z=_nan(B, n)),
                    must_converge=True)
   eng.close()
+  # the derivative family at the smallest shapes that go through every staging item: B = 1 and 3 (E = 2 sets of R = 2), two extragradient steps, the row
+  # stride 0 and np, every optional array present and absent, the three params forms where the entry point has a stride
+  node = lambda: _lib.Engine("NODE_CARTPOLE", "HERMITE_SIMPSON", 3, 2.0)
+  node_sh = lambda: _lib.Engine("NODE_CARTPOLE", "SHOOTING", 2, 2.0, controls_per_interval=2)
+  for make, default, grads, hvps in ((cart(3), [9.81, 1.0, 0.3, 0.5], ("myr_exgd_grad",), ("myr_hvp",)), (vdp, None, ("myr_exgd_grad_shoot",), ("myr_hvp",)),
+                                     (node, None, ("myr_exgd_grad_node", "myr_exgd_grad_node_sets"), ("myr_hvp_node", "myr_hvp_node_sets")),
+                                     (node_sh, None, ("myr_exgd_grad_node_shoot", "myr_exgd_grad_node_sets"), ("myr_hvp_node", "myr_hvp_node_sets"))):
+    eng = make()
+    n, m, ns, nu, npar = eng.n, eng.m, eng.ns, eng.nu, eng.np
+    is_node = eng.desc.system_id == _lib.SYS_IDS["NODE_CARTPOLE"]
+    if default is None:
+      default = 0.1 * rng.standard_normal(npar) if is_node else np.ones(npar)
+    for ep in grads + hvps + ("myr_fit_grad_sets",):
+      sets = ep in _SETS_EPS
+      for lead in (((2, 2),) if sets else ((1,), (3,))):
+        B = int(np.prod(lead))
+        arr = lambda w, scale=1.0: scale * rng.standard_normal(lead + (w,))
+        if sets:
+          sizes, forms = dict(E=2, R=2), [(np.stack([np.asarray(default, dtype=np.float64) * (1.0 + 0.01 * e) for e in range(2)]), 0)]
+        else:
+          sizes, forms = dict(B=B), ([(np.asarray(default, dtype=np.float64), 0)] if is_node else _params_forms(default, B))
+        for p, ps in forms:
+          for stride in (0, npar):
+            rows = (lead if stride else lead[:-1]) + (npar,)
+            common = dict(sizes, params=p, stride=ps)
+            if ep in grads:
+              for full in (True, False):
+                _same_bits(ep, eng, make, dict(common, z=arr(n, 0.3), lam=arr(m), lb=np.full(lead + (n,), -5.0), ub=np.full(lead + (n,), 5.0), eta_x=1e-3,
+                                               eta_v=1e-3, nsteps=2, seed_z=arr(n), seed_lam=arr(m) if full else None, grad=_nan(*rows), grad_stride=stride,
+                                               dz0=_nan(*lead, n) if full else None, dlam0=_nan(*lead, m) if full else None))
+            elif ep in hvps:
+              for with_lam, with_z, with_p, with_cost in ((True, True, True, 1), (False, False, True, 1), (True, True, False, 0)):
+                _same_bits(ep, eng, make, dict(common, z=arr(n, 0.3), lam=arr(m) if with_lam else None, v=arr(n), with_cost=with_cost,
+                                               out_z=_nan(*lead, n) if with_z else None, out_p=_nan(*rows) if with_p else None, p_stride=stride))
+            elif eng.desc.transcription != _lib.TR_IDS["SHOOTING"]:      # (a rollout: the transcription plays no part, one handle per system is enough)
+              S = 4
+              for with_wt, with_loss, with_grad, shared in ((True, True, True, 0), (False, False, True, 1), (False, True, False, 0)):
+                dlead = lead[1:] if shared else lead
+                xs_obs = 0.1 * rng.standard_normal(dlead + (S + 1, ns)); us = 0.2 * rng.standard_normal(dlead + (S + 1, nu))
+                _same_bits(ep, eng, make, dict(common, num_steps=S, u_rows=S + 1, xs_obs=xs_obs, us=us, data_shared=shared,
+                                               wt=np.linspace(0.5, 1.5, S + 1) if with_wt else None, loss=_nan(*lead) if with_loss else None,
+                                               grad=_nan(*rows) if with_grad else None, grad_stride=stride))
+    eng.close()
 
 
 def _abi_defaults(ep, eng, B):
@@ -354,6 +416,20 @@ def _abi_defaults(ep, eng, B):
   elif ep == "myr_fbsm":
     a.update(N=4, x0=np.ones((R, ns)), adj_T=None, clip_lo=np.zeros(nu), clip_hi=np.ones(nu), bang=0.0, delta=1e-3, max_sweeps=5,
              xs=s(R, 5, ns), us=s(R, 5, nu), adjs=s(R, 5, ns), sweeps=i32(R))
+  elif ep in _EXGD_GRAD_EPS + _HVP_EPS + ("myr_fit_grad_sets",):      # (a sets call: B is its E, of two instances each)
+    sets, npar = ep in _SETS_EPS, max(eng.np, 1)
+    lead = (R, 2) if sets else (R,)
+    a.update(E=B, R=2)
+    if "_node" in ep:
+      a.update(params=np.zeros((R, npar) if sets else npar))
+    if ep in _EXGD_GRAD_EPS:
+      a.update(z=np.zeros(lead + (n,)), lam=np.zeros(lead + (m,)), lb=np.full(lead + (n,), -10.0), ub=np.full(lead + (n,), 10.0), eta_x=1e-3, eta_v=1e-3,
+               nsteps=1, seed_z=np.ones(lead + (n,)), seed_lam=None, grad=s(*lead, npar), grad_stride=eng.np, dz0=s(*lead, n), dlam0=s(*lead, m))
+    elif ep in _HVP_EPS:
+      a.update(z=np.zeros(lead + (n,)), lam=np.zeros(lead + (m,)), v=np.ones(lead + (n,)), with_cost=1, out_z=s(*lead, n), out_p=s(*lead, npar), p_stride=eng.np)
+    else:
+      a.update(num_steps=4, u_rows=5, xs_obs=np.zeros(lead + (5, ns)), us=np.zeros(lead + (5, nu)), data_shared=0, wt=None, params=np.ones((R, npar)),
+               loss=s(*lead), grad=s(*lead, npar), grad_stride=eng.np)
   return a
 
 
@@ -364,13 +440,175 @@ def _bad_opts(eng, **kw):
   return o
 
 
+def _derivative_rows():
+  """The rows of the derivative family (myr_exgd_grad*, myr_hvp*, myr_fit_grad_sets), written check by check from the entry points: every refusal they
+  can give with its full text, the empty call, and two faults at once wherever two siblings look in a different order.  For a sets call the
+  batch column is E (R = 2)."""
+  ARG, UNSUP, CAP = -1, -2, -4
+  home = {"myr_exgd_grad": "cart", "myr_exgd_grad_shoot": "vdp_sh", "myr_exgd_grad_node": "node", "myr_exgd_grad_node_shoot": "node_sh",
+          "myr_exgd_grad_node_sets": "node", "myr_hvp": "cart", "myr_hvp_node": "node", "myr_hvp_node_sets": "node_sh", "myr_fit_grad_sets": "cart"}
+  off = lambda key: (lambda e: {key: e.np + 1})      # a row stride that is neither 0 nor np
+  weights = lambda e: dict(params=np.zeros(e.np))
+  plant_text = "INVASIVEPLANT is a discrete-time system; only myr_fbsm is available for it"
+  twin_text = "an elastic twin has no model of its own to differentiate; use the handle of its system"
+  row_batch = "must be 0 (one row: the sum over the batch) or np (a row per instance)"
+  row_sets = "must be 0 (a row per set: the sum over its instances) or np (a row per instance)"
+  sizes_text = "bad sizes (E >= 0 sets of R >= 1 instances, E * R an int)"
+  tz_text = "TRAPEZOIDAL is not built for the network system; HERMITE_SIMPSON and SHOOTING only"
+  lds_hs = "intervals too large for the LDS-resident reverse sweep beside the weight copy"
+  lds_sh = "intervals x controls_per_interval too large for the LDS-resident sweep beside the weight copy"
+  lds_pairs = "intervals x controls_per_interval too large for the LDS-resident pair records beside the weight copy"
+  rows = []
+  add = lambda ep, which, B, change, code, text, null_handle=False: rows.append((ep, which, B, change, null_handle, code, f"{ep}: {text}" if text else ""))
+  for ep in _EXGD_GRAD_EPS:
+    h = home[ep]
+    add(ep, h, 2, {}, ARG, "null handle or array", null_handle=True)
+    for k in ("z", "lam", "lb"):
+      add(ep, h, 2, {k: None}, ARG, "null handle or array")
+    add(ep, h, 2, {"ub": None}, ARG, "null ub")
+    add(ep, h, 2, {"nsteps": -1}, ARG, "negative nsteps")
+    add(ep, h, 2, {"seed_z": None}, ARG, "null seed_z or grad")
+    add(ep, h, 2, {"grad": None}, ARG, "null seed_z or grad")
+    add(ep, h, 2, off("grad_stride"), ARG, "grad_stride " + (row_sets if ep in _SETS_EPS else row_batch))
+    add(ep, h, 2, {"mem": 2}, ARG, "bad mem kind")
+    add(ep, h, 0, {}, 0, "")
+    add(ep, h, 2, {"ub": None, "nsteps": -1, "seed_z": None}, ARG, "null ub")      # the run ub, nsteps, seed_z or grad: in this order everywhere
+    add(ep, h, 2, {"nsteps": -1, "grad": None}, ARG, "negative nsteps")
+  for ep in ("myr_exgd_grad", "myr_exgd_grad_shoot"):
+    add(ep, "plant", 2, {}, UNSUP, plant_text)
+    add(ep, "plant", -1, {}, UNSUP, plant_text)
+    add(ep, home[ep], -1, {}, ARG, "negative batch")
+    add(ep, home[ep], 2, lambda e: dict(params=np.ones((2, e.np)), stride=e.np + 2), ARG, "params_stride must be 0 (shared) or np")
+    add(ep, "node", 2, {}, ARG, "a NODE system needs its weights in `params`")
+    add(ep, "twin", 2, {}, UNSUP, twin_text)
+    add(ep, "twin", 2, off("grad_stride"), ARG, "grad_stride " + row_batch)      # the stride is looked at before the kind of system
+    add(ep, "twin", 2, {"mem": 2}, UNSUP, twin_text)
+  add("myr_exgd_grad", "node", 2, weights, UNSUP, "the network system is not built (second derivatives in 4 804 weights)")
+  add("myr_exgd_grad", "vdp_sh", 2, {}, UNSUP, "SHOOTING is not built (it needs the second-order adjoint of the rollout); use a collocation transcription")
+  add("myr_exgd_grad", "vdp_sh", 2, {"mem": 2}, UNSUP, "SHOOTING is not built (it needs the second-order adjoint of the rollout); use a collocation transcription")
+  add("myr_exgd_grad_shoot", "node", 2, weights, UNSUP, "the network system is not built (second derivatives in 4 804 weights); myr_exgd_grad_node has HERMITE_SIMPSON")
+  add("myr_exgd_grad_shoot", "cart", 2, {}, UNSUP, "this handle's transcription is not SHOOTING; use myr_exgd_grad")
+  add("myr_exgd_grad_shoot", "cart", 0, {}, UNSUP, "this handle's transcription is not SHOOTING; use myr_exgd_grad")
+  for ep, use in (("myr_exgd_grad_node", "myr_exgd_grad"), ("myr_exgd_grad_node_shoot", "myr_exgd_grad_shoot"),
+                  ("myr_exgd_grad_node_sets", "myr_exgd_grad or myr_exgd_grad_shoot"), ("myr_hvp_node", "myr_hvp"), ("myr_hvp_node_sets", "myr_hvp")):
+    for B in (2, 0):
+      add(ep, "cart", B, {}, UNSUP, f"this handle's system is not the network system; use {use}")
+    add(ep, "cart", 2, {"mem": 2}, UNSUP, f"this handle's system is not the network system; use {use}")
+    key = "grad_stride" if ep in _EXGD_GRAD_EPS else "p_stride"
+    add(ep, "cart", 2, off(key), UNSUP, f"this handle's system is not the network system; use {use}")      # (a stride that is wrong for it too)
+    if ep in ("myr_exgd_grad_node_sets", "myr_hvp_node", "myr_hvp_node_sets"):
+      add(ep, "node_tz", 2, off(key), UNSUP, tz_text)
+    if ep in _SETS_EPS:
+      add(ep, home[ep], 2, {"params": None}, ARG, "null params (the [E][np] weight sets)")
+      for change in ({"R": 0}, {"E": 65536, "R": 65536}):
+        add(ep, home[ep], 2, change, ARG, sizes_text)
+      add(ep, home[ep], -1, {}, ARG, sizes_text)
+      add(ep, home[ep], 2, lambda e, key=key: {"R": 0, key: e.np + 1, "mem": 2}, ARG, sizes_text)
+    else:
+      add(ep, home[ep], 2, {"params": None}, ARG, "a NODE system needs its weights in `params`")
+      add(ep, home[ep], -1, {}, ARG, "negative batch")
+      add(ep, home[ep], -1, lambda e, key=key: {key: e.np + 1, "mem": 2}, ARG, "negative batch")
+    add(ep, home[ep], 2, lambda e, key=key: {key: e.np + 1, "mem": 2}, ARG, f"{key} " + (row_sets if ep in _SETS_EPS else row_batch))
+  # myr_exgd_grad_node and its siblings look at the batch before the weights, myr_hvp_node and myr_hvp_node_sets at the weights first
+  add("myr_exgd_grad_node", "node", -1, {"params": None}, ARG, "negative batch")
+  add("myr_exgd_grad_node_shoot", "node_sh", -1, {"params": None}, ARG, "negative batch")
+  add("myr_exgd_grad_node_sets", "node", -1, {"params": None}, ARG, sizes_text)
+  add("myr_hvp_node", "node", -1, {"params": None}, ARG, "a NODE system needs its weights in `params`")
+  add("myr_hvp_node_sets", "node_sh", -1, {"params": None}, ARG, "null params (the [E][np] weight sets)")
+  # ... and the exgd_grad calls at the sizes before the system, the hvp calls at the system first
+  add("myr_exgd_grad_node", "cart", -1, {}, ARG, "negative batch")
+  add("myr_exgd_grad_node_sets", "cart", -1, {}, ARG, sizes_text)
+  add("myr_hvp_node", "cart", -1, {"params": None}, UNSUP, "this handle's system is not the network system; use myr_hvp")
+  add("myr_hvp_node_sets", "cart", -1, {"params": None}, UNSUP, "this handle's system is not the network system; use myr_hvp")
+  for ep in ("myr_hvp_node", "myr_hvp_node_sets"):      # ... whatever else is wrong with the call
+    add(ep, "cart", -1, lambda e: dict(p_stride=e.np + 1, mem=2), UNSUP, "this handle's system is not the network system; use myr_hvp")
+    add(ep, "node_tz", -1, lambda e: dict(p_stride=e.np + 1, mem=2), UNSUP, tz_text)
+    add(ep, "node_tz", 2, {"out_z": None, "out_p": None}, ARG, "both outputs are null")
+  add("myr_hvp_node", "node_sh", 0, {}, 0, "")
+  # the transcriptions of the network system
+  hs_only = "HERMITE_SIMPSON only, the one transcription myr_vjp / myr_exgd build for the network system"
+  add("myr_exgd_grad_node", "node_sh", 2, {}, UNSUP, hs_only)
+  add("myr_exgd_grad_node", "node_tz", 2, {"params": None}, UNSUP, hs_only)
+  add("myr_exgd_grad_node_shoot", "node", 2, {}, UNSUP, "this handle's transcription is HERMITE_SIMPSON, not SHOOTING; use myr_exgd_grad_node")
+  add("myr_exgd_grad_node_shoot", "node_tz", 2, {"params": None}, UNSUP, "TRAPEZOIDAL is not built for the network system; SHOOTING only")
+  for ep in ("myr_exgd_grad_node_sets", "myr_hvp_node", "myr_hvp_node_sets"):
+    add(ep, "node_tz", 2, {"params": None}, UNSUP, tz_text)
+    add(ep, "node_tz", 0, {"mem": 2}, UNSUP, tz_text)
+  # past the LDS bounds (an empty call is refused too: the bound belongs to the handle); the other checks come first
+  for ep, which, text in (("myr_exgd_grad_node", "node_hs_big", lds_hs), ("myr_exgd_grad_node_shoot", "node_sh_big", lds_sh),
+                          ("myr_exgd_grad_node_sets", "node_hs_big", lds_hs), ("myr_exgd_grad_node_sets", "node_sh_big", lds_sh),
+                          ("myr_hvp_node", "node_sh_big", lds_pairs), ("myr_hvp_node_sets", "node_sh_big", lds_pairs)):
+    add(ep, which, 0, {}, CAP, text)
+    add(ep, which, 0, {"mem": 2}, ARG, "bad mem kind")
+  for ep in ("myr_hvp_node", "myr_hvp_node_sets"):      # Hermite-Simpson has no bound here
+    add(ep, "node_hs_big", 0, {}, 0, "")
+  # the products
+  for ep in _HVP_EPS:
+    h = home[ep]
+    add(ep, h, 2, {}, ARG, "null handle, z or v", null_handle=True)
+    add(ep, h, 2, {"z": None}, ARG, "null handle, z or v")
+    add(ep, h, 2, {"v": None}, ARG, "null handle, z or v")
+    add(ep, h, 2, {"out_z": None, "out_p": None}, ARG, "both outputs are null")
+    add(ep, "plant" if ep == "myr_hvp" else "cart", -1, {"out_z": None, "out_p": None, "mem": 2}, ARG, "both outputs are null")
+    add(ep, h, 2, off("p_stride"), ARG, "p_stride " + (row_sets if ep in _SETS_EPS else row_batch))
+    add(ep, h, 2, {"mem": 2}, ARG, "bad mem kind")
+    add(ep, h, 0, {}, 0, "")
+  for ep in ("myr_hvp_node", "myr_hvp_node_sets"):
+    add(ep, "node", 0, {}, 0, "")
+  add("myr_exgd_grad_node_sets", "node_sh", 0, {}, 0, "")
+  add("myr_hvp", "plant", 2, {}, UNSUP, plant_text)
+  add("myr_hvp", "plant", -1, {}, UNSUP, plant_text)      # the kind of system before the batch
+  add("myr_hvp", "twin", -1, {}, UNSUP, twin_text)
+  add("myr_hvp", "node", -1, weights, UNSUP, "the network system is not built (second derivatives in 4 804 weights)")
+  add("myr_hvp", "node", 2, {}, UNSUP, "the network system is not built (second derivatives in 4 804 weights)")
+  add("myr_hvp", "cart", -1, {}, ARG, "negative batch")
+  add("myr_hvp", "cart", -1, off("p_stride"), ARG, "negative batch")
+  add("myr_hvp", "cart", 2, lambda e: dict(params=np.ones((2, e.np)), stride=e.np + 2), ARG, "params_stride must be 0 (shared) or np")
+  add("myr_hvp", "cart", 2, lambda e: dict(params=np.ones((2, e.np)), stride=e.np + 2, p_stride=e.np + 1), ARG, "p_stride " + row_batch)
+  add("myr_hvp", "cart", 0, lambda e: dict(params=np.ones((1, e.np)), stride=e.np + 2), ARG, "params_stride must be 0 (shared) or np")
+  add("myr_hvp", "cart", 2, lambda e: dict(params=np.ones((2, e.np)), stride=e.np + 2, mem=2), ARG, "params_stride must be 0 (shared) or np")
+  add("myr_hvp", "cart", 0, {"mem": 2}, ARG, "bad mem kind")      # the memory kind before the empty batch returns
+  add("myr_hvp", "cart", 2, {"z": None, "out_z": None, "out_p": None}, ARG, "null handle, z or v")
+  add("myr_hvp", "cart", -1, {"out_z": None, "out_p": None}, ARG, "both outputs are null")
+  for which, text in (("plant", plant_text), ("twin", twin_text), ("node", "the network system is not built (second derivatives in 4 804 weights)")):
+    add("myr_hvp", which, 0, weights, UNSUP, text)
+    add("myr_hvp", which, 2, {"out_z": None, "out_p": None}, ARG, "both outputs are null")      # ... behind the null checks
+  add("myr_exgd_grad_shoot", "node_sh", 2, weights, UNSUP, "the network system is not built (second derivatives in 4 804 weights); myr_exgd_grad_node has HERMITE_SIMPSON")
+  add("myr_hvp", "node_sh", 2, weights, UNSUP, "the network system is not built (second derivatives in 4 804 weights)")
+  # myr_fit_grad_sets: the arguments first, the system last; a twin and a system without derivatives are answered in myr_fit_grad's name
+  ep = "myr_fit_grad_sets"
+  add(ep, "cart", 2, {}, ARG, "null handle, xs_obs, us or params", null_handle=True)
+  for k in ("xs_obs", "us", "params"):
+    add(ep, "cart", 2, {k: None}, ARG, "null handle, xs_obs, us or params")
+  add(ep, "cart", 2, {"loss": None, "grad": None}, ARG, "loss and grad are both null")
+  for change in ({"E": -1}, {"R": 0}, {"num_steps": 0}, {"u_rows": 0}):
+    add(ep, "cart", 2, change, ARG, "bad sizes")
+  add(ep, "cart", 2, off("grad_stride"), ARG, "grad_stride must be 0 (a row per set: the sum over its trajectories) or np (a row per trajectory)")
+  add(ep, "cart", 2, {"data_shared": 2}, ARG, "data_shared must be 0 (data per set) or 1 (one set of data, read by every set)")
+  add(ep, "cart", 2, {"data_shared": -1, "mem": 2}, ARG, "data_shared must be 0 (data per set) or 1 (one set of data, read by every set)")
+  add(ep, "cart", 2, {"mem": 2}, ARG, "bad mem kind")
+  add(ep, "plant", 2, {}, UNSUP, plant_text)
+  add(ep, "plant", 2, {"mem": 2}, ARG, "bad mem kind")
+  add(ep, "plant", 0, {}, UNSUP, plant_text)
+  add(ep, "cart", 0, {}, 0, "")
+  add(ep, "node", 0, {}, 0, "")
+  rows.append((ep, "twin", 2, {}, False, UNSUP, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system"))
+  rows.append((ep, "twin", 0, {}, False, UNSUP, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system"))
+  return rows
+
+
 def test_argument_errors_keep_their_codes_and_texts():
   """(entry point, fault) -> (return code, text of myr_last_error), one call per row, as the entry points answer today -- the order of their checks included:
   myr_eval and myr_rollout return MYR_OK for an empty batch before they look at the stride, the products and myr_fit_grad look first.  No row reaches a kernel."""
   from myriad_amd import _lib
   ARG, UNSUP = -1, -2
   engines = {"cart": _lib.Engine("CARTPOLE", "HERMITE_SIMPSON", 3, 2.0), "node": _lib.Engine("NODE_CARTPOLE", "HERMITE_SIMPSON", 3, 2.0),
-             "plant": _lib.Engine("INVASIVEPLANT", "HERMITE_SIMPSON", 3, 2.0), "twin": _lib.Engine("CARTPOLE_ELASTIC", "HERMITE_SIMPSON", 3, 2.0)}
+             "plant": _lib.Engine("INVASIVEPLANT", "HERMITE_SIMPSON", 3, 2.0), "twin": _lib.Engine("CARTPOLE_ELASTIC", "HERMITE_SIMPSON", 3, 2.0),
+             # the derivative family's: the network system under its other transcriptions, a closed-form SHOOTING handle, and two past the LDS bounds
+             "node_sh": _lib.Engine("NODE_CARTPOLE", "SHOOTING", 2, 2.0, controls_per_interval=2), "node_tz": _lib.Engine("NODE_CARTPOLE", "TRAPEZOIDAL", 3, 2.0),
+             "vdp_sh": _lib.Engine("VANDERPOL", "SHOOTING", 2, 10.0, controls_per_interval=3, integration_method="HEUN"),
+             "node_sh_big": _lib.Engine("NODE_CARTPOLE", "SHOOTING", 1, 2.0, controls_per_interval=2000, integration_method="HEUN"),
+             "node_hs_big": _lib.Engine("NODE_CARTPOLE", "HERMITE_SIMPSON", 400, 2.0)}
   P = lambda eng, B=2: np.ones((B, eng.np))      # a set of parameters per instance
   direct = ("myr_eval", "myr_vjp", "myr_jvp", "myr_exgd", "myr_rollout", "myr_solve", "myr_solve_x0", "myr_fit_grad")
   nulls = {"myr_eval": ("z", "null handle or z"), "myr_vjp": ("out", "null handle or array"), "myr_jvp": ("w", "null handle or array"),
@@ -420,6 +658,7 @@ def test_argument_errors_keep_their_codes_and_texts():
   for ep in ("myr_solve", "myr_solve_x0"):
     for kw in (dict(max_iter=-1), dict(tol_feas=0.0), dict(tol_stat=-1.0), dict(tol_compl=0.0), dict(mu_init=0.0)):
       rows.append((ep, "cart", 2, lambda e, kw=kw: dict(opts=_bad_opts(e, **kw)), False, ARG, f"{ep}: bad options"))
+  rows += _derivative_rows()
   try:
     for ep, which, B, change, null_handle, code, text in rows:
       eng = engines[which]

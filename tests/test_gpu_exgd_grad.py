@@ -193,32 +193,14 @@ def test_errors():
     with pytest.raises(NotImplementedError, match=word):
       eng.exgd_grad_probe()
     eng.close()
-  eng = _lib.Engine("NODE_CARTPOLE", "HERMITE_SIMPSON", 3, 1.0)
-  d = np.zeros(4804)
-  rc = eng.lib.myr_exgd_grad(eng._h, 0, d.ctypes.data, d.ctypes.data, d.ctypes.data, d.ctypes.data, d.ctypes.data, 0, 0.0, 0.0, 0, d.ctypes.data, None,
-                             d.ctypes.data, 0, None, None, _lib.MEM_HOST)
-  assert rc == -2 and b"network system" in eng.lib.myr_last_error()
-  eng.close()
+  # (the argument checks of the C call, with their full texts and their order: tests/test_gpu_api.py)
   eng = _engine("CARTPOLE", "HERMITE_SIMPSON", 3, c["T"])
   grad = np.empty((2, 4))
-  ptr = {k: c[k].ctypes.data for k in ("z", "lam", "lb", "ub", "seed_z")}
-
-  def call(nsteps=2, grad_stride=4, pstride=0, g=grad.ctypes.data, **null):
-    a = dict(ptr); a.update(null)
-    return eng.lib.myr_exgd_grad(eng._h, 2, a["z"], a["lam"], a["lb"], a["ub"], c["params"].ctypes.data, pstride, 0.02, 0.02, nsteps, a["seed_z"], None, g,
-                                 grad_stride, None, None, _lib.MEM_HOST)
-
-  assert call() == 0
-  for k in ("z", "lam", "lb"):
-    assert call(**{k: None}) == -1 and b"null handle or array" in eng.lib.myr_last_error()
-  assert call(ub=None) == -1 and b"null ub" in eng.lib.myr_last_error()
-  assert call(seed_z=None) == -1 and b"null seed_z or grad" in eng.lib.myr_last_error()
-  assert call(g=None) == -1 and b"null seed_z or grad" in eng.lib.myr_last_error()
-  assert call(nsteps=-1) == -1 and b"negative nsteps" in eng.lib.myr_last_error()
-  assert call(grad_stride=3) == -1 and b"grad_stride must be 0" in eng.lib.myr_last_error()
-  assert call(pstride=3) == -1 and b"params_stride must be 0" in eng.lib.myr_last_error()
+  rc = eng.lib.myr_exgd_grad(eng._h, 2, *(c[k].ctypes.data for k in ("z", "lam", "lb", "ub", "params")), 0, 0.02, 0.02, 2, c["seed_z"].ctypes.data, None,
+                             grad.ctypes.data, 4, None, None, _lib.MEM_HOST)
+  assert rc == 0
   eng.close()
-  eng = _engine("CARTPOLE", "HERMITE_SIMPSON", 400, 2.0)      # (3 n + 2 m + K NS) doubles = 195 KB
+  eng = _engine("CARTPOLE", "HERMITE_SIMPSON", 400, 2.0)     # (3 n + 2 m + K NS) doubles = 195 KB
   with pytest.raises(_lib.MyriadHipError, match="too large for the LDS"):
     eng.exgd_grad(np.zeros((1, eng.n)), np.zeros((1, eng.m)), -np.ones(eng.n), np.ones(eng.n), 0.01, 0.01, 1, np.zeros((1, eng.n)))
   eng.close()

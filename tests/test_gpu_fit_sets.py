@@ -260,11 +260,8 @@ def test_errors():
   loss, grad = np.full((3, 1), 7.0), np.full((3, 1, 4), 7.0)
   call = lambda E, R, params, gs, shared: eng.lib.myr_fit_grad_sets(eng._h, E, R, 7, 8, xs_obs.ctypes.data, us.ctypes.data, shared, None, params,
                                                                    loss.ctypes.data, grad.ctypes.data, gs, _lib.MEM_HOST)
-  assert call(3, 1, None, 4, 0) == -1 and b"null" in eng.lib.myr_last_error()
-  assert call(3, 0, P.ctypes.data, 4, 0) == -1 and b"bad sizes" in eng.lib.myr_last_error()
-  assert call(3, 1, P.ctypes.data, 3, 0) == -1 and b"grad_stride must be 0" in eng.lib.myr_last_error()
-  assert call(3, 1, P.ctypes.data, 4, 2) == -1 and b"data_shared must be 0" in eng.lib.myr_last_error()
-  assert call(0, 1, P.ctypes.data, 4, 0) == 0                     # E = 0: nothing is written
+  # (the argument checks of the C call, with their full texts and their order: tests/test_gpu_api.py)
+  assert call(0, 1, P.ctypes.data, 4, 0) == 0                    # E = 0: nothing is written
   assert (loss == 7.0).all() and (grad == 7.0).all()
   assert call(3, 1, P.ctypes.data, 4, 0) == 0 and (loss != 7.0).all() and np.isfinite(grad).all()
   eng.close()

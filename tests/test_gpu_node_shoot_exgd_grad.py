@@ -169,30 +169,12 @@ def test_errors():
     return getattr(eng.lib, fn)(eng._h, B, a["z"], a["lam"], a["lb"], a["ub"], a["params"], c["eta_x"], c["eta_v"], nsteps, a["seed_z"], None,
                                 a["grad"], grad_stride, None, None, mem)
 
-  eng = _engine(c, system="CARTPOLE")                              # another system: the message points to myr_exgd_grad_shoot
-  assert call(eng, grad_stride=4) == -2 and b"use myr_exgd_grad_shoot" in eng.lib.myr_last_error()
-  eng.close()
-  eng = _lib.Engine("NODE_CARTPOLE", "HERMITE_SIMPSON", 3, c["T"])
-  assert call(eng) == -2 and b"use myr_exgd_grad_node" in eng.lib.myr_last_error() and b"HERMITE_SIMPSON" in eng.lib.myr_last_error()
-  eng.close()
-  eng = _lib.Engine("NODE_CARTPOLE", "TRAPEZOIDAL", 3, c["T"])
-  assert call(eng) == -2 and b"TRAPEZOIDAL" in eng.lib.myr_last_error()
-  eng.close()
+  # (the argument checks of the C call, with their full texts and their order, and the refusals that stay -- myr_exgd_grad_node on a shooting
+  # handle, myr_exgd_grad_shoot on the network: tests/test_gpu_api.py)
   eng = _engine(c)
   grad[:] = 7.0
   assert call(eng, B=0) == 0 and (grad == 7.0).all()             # an empty batch writes nothing
   assert call(eng) == 0 and np.isfinite(grad).all()
-  for k in ("z", "lam", "lb", "ub", "seed_z", "grad", "params"):
-    assert call(eng, **{k: None}) == -1, k
-  assert call(eng, nsteps=-1) == -1 and b"negative nsteps" in eng.lib.myr_last_error()
-  assert call(eng, B=-1) == -1 and b"negative batch" in eng.lib.myr_last_error()
-  assert call(eng, grad_stride=3) == -1 and b"grad_stride must be 0" in eng.lib.myr_last_error()
-  assert call(eng, mem=7) == -1 and b"bad mem kind" in eng.lib.myr_last_error()
-  # the refusals that stay: myr_exgd_grad_node on a shooting handle, myr_exgd_grad_shoot on the network
-  assert call(eng, fn="myr_exgd_grad_node") == -2 and b"HERMITE_SIMPSON only" in eng.lib.myr_last_error()
-  rc = eng.lib.myr_exgd_grad_shoot(eng._h, 2, ptr["z"], ptr["lam"], ptr["lb"], ptr["ub"], ptr["params"], 0, c["eta_x"], c["eta_v"], 3, ptr["seed_z"],
-                                   None, ptr["grad"], 4804, None, None, _lib.MEM_HOST)
-  assert rc == -2 and b"the network system is not built" in eng.lib.myr_last_error()
   eng.close()
   eng = _lib.Engine("NODE_CARTPOLE", "SHOOTING", 1, 2.0, controls_per_interval=2000, integration_method="HEUN")      # 5 064 + 24 035 doubles = 233 KB
   with pytest.raises(_lib.MyriadHipError, match="too large for the LDS"):

@@ -216,32 +216,13 @@ def test_errors():
     with pytest.raises(NotImplementedError, match=word):
       eng.exgd_grad_shoot_probe()
     eng.close()
-  eng = _lib.Engine("NODE_CARTPOLE", "HERMITE_SIMPSON", 3, 1.0)
-  d = np.zeros(4804)
-  rc = eng.lib.myr_exgd_grad_shoot(eng._h, 0, d.ctypes.data, d.ctypes.data, d.ctypes.data, d.ctypes.data, d.ctypes.data, 0, 0.0, 0.0, 0, d.ctypes.data,
-                                   None, d.ctypes.data, 0, None, None, _lib.MEM_HOST)
-  assert rc == -2 and b"network system" in eng.lib.myr_last_error()
-  eng.close()
+  # (the argument checks of the C call, with their full texts and their order: tests/test_gpu_api.py)
   eng = _engine(c)
   eng.exgd_grad_shoot_probe()
   grad = np.empty((2, 4))
-  ptr = {k: c[k].ctypes.data for k in ("z", "lam", "lb", "ub", "seed_z")}
-
-  def call(nsteps=2, grad_stride=4, pstride=0, g=grad.ctypes.data, mem=_lib.MEM_HOST, **null):
-    a = dict(ptr); a.update(null)
-    return eng.lib.myr_exgd_grad_shoot(eng._h, 2, a["z"], a["lam"], a["lb"], a["ub"], c["params"].ctypes.data, pstride, 0.02, 0.02, nsteps, a["seed_z"],
-                                       None, g, grad_stride, None, None, mem)
-
-  assert call() == 0
-  for k in ("z", "lam", "lb"):
-    assert call(**{k: None}) == -1 and b"null handle or array" in eng.lib.myr_last_error()
-  assert call(ub=None) == -1 and b"null ub" in eng.lib.myr_last_error()
-  assert call(seed_z=None) == -1 and b"null seed_z or grad" in eng.lib.myr_last_error()
-  assert call(g=None) == -1 and b"null seed_z or grad" in eng.lib.myr_last_error()
-  assert call(nsteps=-1) == -1 and b"negative nsteps" in eng.lib.myr_last_error()
-  assert call(grad_stride=3) == -1 and b"grad_stride must be 0" in eng.lib.myr_last_error()
-  assert call(pstride=3) == -1 and b"params_stride must be 0" in eng.lib.myr_last_error()
-  assert call(mem=7) == -1
+  rc = eng.lib.myr_exgd_grad_shoot(eng._h, 2, *(c[k].ctypes.data for k in ("z", "lam", "lb", "ub", "params")), 0, 0.02, 0.02, 2, c["seed_z"].ctypes.data,
+                                   None, grad.ctypes.data, 4, None, None, _lib.MEM_HOST)
+  assert rc == 0
   # myr_exgd_grad keeps its refusal of SHOOTING
   with pytest.raises(NotImplementedError, match="SHOOTING is not built"):
     eng.exgd_grad_probe()
