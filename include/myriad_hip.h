@@ -30,6 +30,8 @@
  *                                                experiments/mle_sysid.py:89-136, neural_ode/node_training.py:31-61   myr_fit_grad
  *   ... of many independent models at once (study_scripts.py:28-43 trains one per noise level, one after the
  *                                                other; hp.num_experiments, seed sweeps)          myr_fit_grad_sets
+ *   the Gauss-Newton matrix of that loss, 2 J^T W J (no call site in the reference: what a Levenberg-Marquardt fit and a
+ *                                                parameter covariance ask for)                    myr_fit_gn, myr_fit_gn_sets
  *   many_steps_grad / the Lagrangian Hessian product of many independent networks at once (the reference's
  *                                                node_e2e_sysid.py loop trains one)               myr_exgd_grad_node_sets, myr_hvp_node_sets
  *
@@ -367,6 +369,42 @@ int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, con
 int myr_fit_grad_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                       int32_t data_shared, const double* wt, const double* params, double* loss, double* grad, int32_t grad_stride,
                       int32_t mem);
+
+/*
+ * myr_fit_grad's loss and gradient together with the Gauss-Newton matrix of the fit, by forward sensitivities in one pass on the device
+ * (csrc/fit_gn.h; an extension with no call site in the reference -- what a Gauss-Newton / Levenberg-Marquardt fit solves with, and the
+ * Fisher information of the fit).  With r_b[t] = xh_b[t] - xs_obs_b[t] and S_b[t] = d xh_b[t] / d params [ns][np]:
+ *   loss[b] = sum_t wt[t] |r_b[t]|^2,   grad[b] = 2 sum_t wt[t] S_b[t]^T r_b[t],   gn[b] = 2 sum_t wt[t] S_b[t]^T S_b[t]
+ * so that loss(params + d) = loss + grad . d + d . gn d / 2 to second order in d (to first order in the residuals).  gn[b] is symmetric to the
+ * bit and positive semidefinite; a parameter that enters the running cost only has a 0 in grad and a row and column of 0 in gn.
+ *   xs_obs, us, wt, params, params_stride, loss: as in myr_fit_grad (closed-form systems; params NULL = the defaults);
+ *   out_stride == np: grad [B][np] (may be NULL), gn [B][np][np];
+ *   out_stride == 0:  grad [np] (may be NULL), gn [np][np]: the sums over the batch, in myr_fit_grad's fixed order, without atomics.
+ * gn is required.  Contract: the same bits for MYR_MEM_HOST and MYR_MEM_DEVICE, on every call, whatever ran on the handle before, with
+ * loss or grad NULL or not; row b of a batched call has the bits of the call on trajectory b alone.  Timed on MYR_K_FIT.  Detected by the export: myr_version() is unchanged.
+ * Errors, in this order: MYR_E_ARG -- a null h, xs_obs, us or gn; B < 0, num_steps < 1, u_rows < 1; an out_stride or params_stride other
+ * than 0 and np; a bad mem.  MYR_E_UNSUPPORTED -- the network system (its 4 804 x 4 804 matrix is not formed: use myr_fit_grad); then,
+ * with myr_fit_grad's messages, the elastic twins, INVASIVEPLANT, systems without generated parameter derivatives.  B == 0 writes
+ * nothing and returns MYR_OK.
+ */
+int myr_fit_gn(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+               const double* wt, const double* params, int32_t params_stride,
+               double* loss, double* grad, double* gn, int32_t out_stride, int32_t mem);
+
+/*
+ * myr_fit_gn for E independent parameter sets of R trajectories each, in one call: the lockstep iterations of many Levenberg-Marquardt fits.
+ *   inputs as in myr_fit_grad_sets (params [E][np] required; data_shared 0 / 1); loss [E][R] or NULL;
+ *   out_stride == np: grad [E][R][np] (may be NULL), gn [E][R][np][np];
+ *   out_stride == 0:  grad [E][np] (may be NULL), gn [E][np][np]: per set, the fixed-order sums over that set's R rows.
+ * Contract: the outputs of set e have the bits of myr_fit_gn on that set alone, as myr_fit_grad_sets' have myr_fit_grad's.  When the rows
+ * behind the per-set sums (E * R * (np + np^2) doubles of scratch) would pass 1 GiB the call runs in chunks of whole sets with the same bits;
+ * MYRIAD_FIT_ROWS_BYTES lowers that bound (tests).
+ * Errors, in this order: MYR_E_ARG -- a null h, xs_obs, us, gn or params; E < 0, R < 1, num_steps < 1, u_rows < 1; an out_stride other than
+ * 0 and np; a data_shared other than 0 and 1; a bad mem.  MYR_E_UNSUPPORTED as myr_fit_gn.  E == 0 writes nothing and returns MYR_OK.
+ */
+int myr_fit_gn_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                    int32_t data_shared, const double* wt, const double* params,
+                    double* loss, double* grad, double* gn, int32_t out_stride, int32_t mem);
 
 /*
  * Derivative of `nsteps` extragradient steps (myr_exgd) in the model parameters, by one reverse sweep through the steps on the device

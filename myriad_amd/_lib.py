@@ -71,6 +71,8 @@ _SIGNATURES = {
   "myr_rollout": ([_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _i], C.c_int),
   "myr_fit_grad": ([_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i], C.c_int),
   "myr_fit_grad_sets": ([_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _i], C.c_int),
+  "myr_fit_gn": ([_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i], C.c_int),
+  "myr_fit_gn_sets": ([_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i], C.c_int),
   "myr_set_var_scale": ([_p, _p], C.c_int),
   "myr_vjp": ([_p, _i, _p, _p, _p, _i, _p, _i, _i], C.c_int),
   "myr_jvp": ([_p, _i, _p, _p, _p, _i, _p, _i], C.c_int),
@@ -374,6 +376,63 @@ class Engine:
     """Zero-copy variant of fit_grad_sets: every array is a device tensor on this handle's device; grad=None: the loss only."""
     _chk(self.lib.myr_fit_grad_sets(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
                                     _addr(params), _addr(loss), _addr(grad), int(grad_stride), MEM_DEVICE), "myr_fit_grad_sets")
+
+  def fit_gn(self, xs_obs, us, params=None, wt=None, reduce=False):
+    """myr_fit_gn: fit_grad's loss and gradient with the Gauss-Newton matrix gn = 2 J^T W J of the fit (J: the sensitivity of the rolled-out
+    states in the parameters), by one forward pass.  Arguments as fit_grad.  Returns {"loss" [B], "grad" [B,np], "gn" [B,np,np]}; with
+    reduce=True "grad" [np] and "gn" [np,np] are the sums over the batch."""
+    xs_obs = _f64(xs_obs)
+    us = _f64(us)
+    if xs_obs.ndim == 2:
+      xs_obs = xs_obs[None]
+    if us.ndim == 2:
+      us = us[None]
+    B, S = xs_obs.shape[0], xs_obs.shape[1] - 1
+    if xs_obs.ndim != 3 or xs_obs.shape[2] != self.ns or S < 1:
+      raise ValueError(f"xs_obs must be [B,S+1,{self.ns}] with S >= 1")
+    if us.ndim != 3 or us.shape[0] != B or us.shape[2] != self.nu:
+      raise ValueError(f"us must be [B,u_rows,{self.nu}]")
+    p, ps = self._params(params, B)
+    w = None if wt is None else _f64(wt, (S + 1,))
+    lead = () if reduce else (B,)
+    loss, grad, gn = np.empty(B), np.empty(lead + (self.np,)), np.empty(lead + (self.np, self.np))
+    _chk(self.lib.myr_fit_gn(self._h, B, S, int(us.shape[1]), _addr(xs_obs), _addr(us), _addr(w), _addr(p), ps, _addr(loss), _addr(grad), _addr(gn),
+                             0 if reduce else self.np, MEM_HOST), "myr_fit_gn")
+    return {"loss": loss, "grad": grad, "gn": gn}
+
+  def fit_gn_device(self, B, num_steps, u_rows, xs_obs, us, gn, out_stride, params=None, params_stride=0, wt=None, loss=None, grad=None):
+    """Zero-copy variant of fit_gn: every array is a device tensor on this handle's device (loss, grad may be None)."""
+    _chk(self.lib.myr_fit_gn(self._h, int(B), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), _addr(wt), _addr(params), int(params_stride),
+                             _addr(loss), _addr(grad), _addr(gn), int(out_stride), MEM_DEVICE), "myr_fit_gn")
+
+  def fit_gn_sets(self, xs_obs, us, params, wt=None, reduce=False):
+    """myr_fit_gn_sets: fit_gn for E independent parameter sets of R trajectories each in one call; arguments as fit_grad_sets.  Returns
+    {"loss" [E,R], "grad" [E,R,np], "gn" [E,R,np,np]}; with reduce=True "grad" [E,np] and "gn" [E,np,np] are, per set, the sums over its
+    trajectories.  Set e has the bits of fit_gn on that set alone."""
+    xs_obs, us, params = _f64(xs_obs), _f64(us), _f64(params)
+    if params.ndim != 2 or params.shape[1] != self.np:
+      raise ValueError(f"params must be [E,{self.np}]")
+    E = params.shape[0]
+    if xs_obs.ndim not in (3, 4) or us.ndim != xs_obs.ndim:
+      raise ValueError("xs_obs and us must both be [E,R,...] (data per set) or both [R,...] (data shared by the sets)")
+    shared = xs_obs.ndim == 3
+    lead = () if shared else (E,)
+    R, S = xs_obs.shape[-3], xs_obs.shape[-2] - 1
+    if xs_obs.shape[:-3] != lead or xs_obs.shape[-1] != self.ns or S < 1 or R < 1:
+      raise ValueError(f"xs_obs must be [{'' if shared else 'E,'}R,S+1,{self.ns}] with R >= 1, S >= 1 and E = {E} as in params")
+    if us.shape[:-2] != lead + (R,) or us.shape[-1] != self.nu or us.shape[-2] < 1:
+      raise ValueError(f"us must be [{'' if shared else 'E,'}R,u_rows,{self.nu}]")
+    w = None if wt is None else _f64(wt, (S + 1,))
+    out = (E,) if reduce else (E, R)
+    loss, grad, gn = np.empty((E, R)), np.empty(out + (self.np,)), np.empty(out + (self.np, self.np))
+    _chk(self.lib.myr_fit_gn_sets(self._h, E, R, S, int(us.shape[-2]), _addr(xs_obs), _addr(us), int(shared), _addr(w), _addr(params), _addr(loss),
+                                  _addr(grad), _addr(gn), 0 if reduce else self.np, MEM_HOST), "myr_fit_gn_sets")
+    return {"loss": loss, "grad": grad, "gn": gn}
+
+  def fit_gn_sets_device(self, E, R, num_steps, u_rows, xs_obs, us, params, gn, out_stride=0, data_shared=False, wt=None, loss=None, grad=None):
+    """Zero-copy variant of fit_gn_sets: every array is a device tensor on this handle's device (loss, grad may be None)."""
+    _chk(self.lib.myr_fit_gn_sets(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
+                                  _addr(params), _addr(loss), _addr(grad), _addr(gn), int(out_stride), MEM_DEVICE), "myr_fit_gn_sets")
 
   # ---- Lagrangian products / extragradient (collocation transcriptions) ------------------------
   def _batch2(self, a, width, name):

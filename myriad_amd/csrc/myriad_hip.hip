@@ -25,6 +25,7 @@
 #include "shoot_eval.h"
 #include "rollout.h"
 #include "fit.h"
+#include "fit_gn.h"
 #include "exgd_grad.h"
 #include "node_exgd_grad.h"
 #include "colloc_hvp.h"
@@ -329,6 +330,9 @@ struct FitArgs {      // E parameter sets of R trajectories each (myr_fit_grad: 
   // grad [E][R][NP] rows or null (the loss only); data_shared: xs_obs, us are [R][...], read by every set; params: [E][NP] (a closed-form system: may be
   // null = the defaults), or with per_row -- myr_fit_grad with params_stride == np on a closed-form system, E = 1 -- [R][NP], a row per trajectory
   int E, R, data_shared; long Bp; int num_steps, u_rows; const double *xs_obs, *us, *wt, *params; int per_row; double *xh, *loss, *grad;
+  // myr_fit_gn*: gn non-null -- [E][R][NP][NP], the Gauss-Newton matrices; fit_gn_lane_kernel runs, without xh.  grad_ld, gn_ld: doubles from one
+  // trajectory's row to the next (dispatch_fit sets them)
+  double* gn; long grad_ld, gn_ld;
 };
 struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of one chunk of `chunk` instances; seed_lam, dz0, dlam0 may be null
   int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
@@ -1158,6 +1162,22 @@ int fit_for_system(myr_handle h, const FitArgs& a) {
   }
 }
 
+// ... and with the Gauss-Newton matrix, by forward sensitivities (fit_gn.h: fit_gn_lane_kernel).  myr_fit_gn* have refused the network system
+template <class Sys>
+int fit_gn_for_system(myr_handle h, const FitArgs& a) {
+  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {
+    return fail(MYR_E_UNSUPPORTED, "myr_fit_gn: the network system's 4 804 x 4 804 matrix is not formed; use myr_fit_grad");
+  } else if constexpr (!SysDp<Sys>::SUPPORTED) {
+    return fail(MYR_E_UNSUPPORTED, std::string("myr_fit_grad: no parameter derivatives are generated for ") + Sys::NAME);
+  } else {
+    const long B = (long)a.E * a.R;
+    hipLaunchKernelGGL(fit_gn_lane_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, (int)B, a.R, a.per_row ? 1 : a.R, a.data_shared,
+                       (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.loss, a.grad, a.grad_ld,
+                       a.gn, a.gn_ld);
+    return MYR_OK;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // derivative of the unrolled extragradient steps in the model parameters (exgd_grad.h: colloc_exgd_grad_kernel)
 // ------------------------------------------------------------------------------------------------
@@ -1397,6 +1417,7 @@ int hvp_node_shoot_for_system(myr_handle h, const HvpArgs& a) {
   LINK template int solve_for_system<S>(myr_handle, const SolveCall&);        \
   LINK template int rollout_for_system<S>(myr_handle, const RolloutArgs&);    \
   LINK template int fit_for_system<S>(myr_handle, const FitArgs&);            \
+  LINK template int fit_gn_for_system<S>(myr_handle, const FitArgs&);         \
   LINK template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
@@ -1430,6 +1451,7 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, 
   template int products_for_system<S>(myr_handle, const ProdArgs&);           \
   template int rollout_for_system<S>(myr_handle, const RolloutArgs&);         \
   template int fit_for_system<S>(myr_handle, const FitArgs&);                 \
+  template int fit_gn_for_system<S>(myr_handle, const FitArgs&);              \
   template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&);      \
   template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
   template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);          \
@@ -2385,35 +2407,57 @@ static bool sys_known(int id) { SysInfo si; return sys_info(id, &si); }
 
 // parameter sets one launch of dispatch_fit takes: all of them, unless the per-set sums are asked for and the row scratch (E R np doubles) would pass
 // 1 GiB -- then whole sets, at least one; and never more than 2^30 trajectories (the kernels count them in an int)
-static int fit_sets_chunk(myr_handle h, int E, int R, bool row_scratch) {
+static int fit_sets_chunk(int E, int R, bool row_scratch, size_t width) {      // width: doubles of one trajectory's row (np; myr_fit_gn*: np + np^2)
   size_t chunk = (size_t)E;
   if (row_scratch) {
     size_t bound = (size_t)1 << 30;
     if (const char* e = getenv("MYRIAD_FIT_ROWS_BYTES")) { const long long v = atoll(e); if (v > 0) bound = (size_t)v; }      // tests: force the chunked path
-    chunk = bound / ((size_t)R * (size_t)(h->dims.np > 0 ? h->dims.np : 1) * 8);
+    chunk = bound / ((size_t)R * (width > 0 ? width : 1) * 8);
   }
   const size_t cap = ((size_t)1 << 30) / (size_t)R;
   if (chunk > cap) chunk = cap;
   return (int)(chunk < 1 ? 1 : (chunk > (size_t)E ? (size_t)E : chunk));
 }
 
+// sums [E][np + np^2] (the packed per-set sums fit_reduce_sets_kernel leaves for myr_fit_gn*) -> grad [E][np] (or null) and gn [E][np][np]: a copy, one
+// thread per entry
+static __global__ __launch_bounds__(256) void fit_gn_unpack_kernel(long n, int np, const double* __restrict__ sums, double* __restrict__ grad,
+                                                                   double* __restrict__ gn) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int ng = np + np * np;
+  const long e = i / ng;
+  const int k = (int)(i - e * ng);
+  if (k < np) {
+    if (grad) grad[e * np + k] = sums[i];
+  } else {
+    gn[e * (long)np * np + (k - np)] = sums[i];
+  }
+}
+
 // device pointers throughout (a.Bp, a.xh are set here); a.grad: [E][R][np] rows (grad_stride == np), the [E][np] per-set sums (grad_stride == 0, rows in
 // sbuf) or null (the loss only).  The sets run in chunks of fit_sets_chunk (launches on one stream: a chunk starts when the one before has ended); a
-// trajectory's arithmetic does not depend on the chunk it runs in
+// trajectory's arithmetic does not depend on the chunk it runs in.
+// With a.gn (myr_fit_gn*) the forward-sensitivity kernel runs instead: no state scratch; a.gn is [E][R][np][np] beside a.grad (which may then be null
+// with either stride), or -- grad_stride == 0 -- [E][np][np] beside [E][np]: the lanes write packed rows [np + np^2], grad then gn, ONE reduction of
+// that width sums them per set in the same fixed order, and a copy takes the sums apart into the two arrays.
 static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
   const myr_dims& dm = h->dims;
+  const bool gnm = a.gn != nullptr;
   if (!fit_supported(h->d.system_id))                  // refused before anything is sized by the system's np, and before the timer starts: begin and end stay paired
     return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
-                                     : no_such_path(h, "myr_fit_grad");
-  const bool sums = a.grad && !grad_stride;
-  const int E = a.E, chunk = fit_sets_chunk(h, E, a.R, sums);
+                                     : no_such_path(h, gnm ? "myr_fit_gn" : "myr_fit_grad");
+  const size_t np = (size_t)dm.np, width = gnm ? np + np * np : np;
+  const bool sums = (a.grad || gnm) && !grad_stride;
+  const int E = a.E, chunk = fit_sets_chunk(E, a.R, sums, width);
   const size_t S1 = (size_t)a.num_steps + 1;
   const double *xs_obs = a.xs_obs, *us = a.us, *params = a.params;
-  double *const loss = a.loss, *const out = a.grad, *rows = nullptr;
+  double *const loss = a.loss, *const out = a.grad, *const out_gn = a.gn, *rows = nullptr, *packed = nullptr;
   a.Bp = padded_lanes((int)((long)chunk * a.R));
   DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
-  st.scratch(a.xh, S1 * dm.ns * (size_t)a.Bp);
-  if (sums) st.scratch(rows, (size_t)chunk * a.R * dm.np);
+  if (!gnm) st.scratch(a.xh, S1 * dm.ns * (size_t)a.Bp);
+  if (sums) st.scratch(rows, (size_t)chunk * a.R * width);
+  if (sums && gnm) st.scratch(packed, (size_t)chunk * width);
   if (int rc = st.commit()) return rc;
   if (int rc = timed_begin(h, MYR_K_FIT)) return rc;
   int rc = MYR_OK;
@@ -2425,6 +2469,19 @@ static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
     a.params = params ? params + (size_t)e0 * dm.np : nullptr;      // (per_row: one set, e0 = 0)
     a.loss = loss ? loss + r0 : nullptr;
     a.grad = sums ? rows : (out ? out + r0 * dm.np : nullptr);
+    if (gnm) {
+      a.gn = sums ? rows + np : out_gn + r0 * np * np;
+      a.grad_ld = (long)(sums ? width : np);
+      a.gn_ld = (long)(sums ? width : np * np);
+      rc = for_system(h->d.system_id, true, [&](auto t) { return fit_gn_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+      if (!rc && sums) {
+        const long n = (long)a.E * (long)width;
+        hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)width * (unsigned)a.E), dim3(256), 0, h->stream, a.R, (int)width, (const double*)rows, packed);
+        hipLaunchKernelGGL(fit_gn_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, (int)np, (const double*)packed,
+                           out ? out + (size_t)e0 * np : nullptr, out_gn + (size_t)e0 * np * np);
+      }
+      continue;
+    }
     rc = for_system(h->d.system_id, true, [&](auto t) { return fit_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
     if (!rc && sums)
       hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)dm.np * (unsigned)a.E), dim3(256), 0, h->stream, a.R, (int)dm.np, (const double*)rows,
@@ -2493,6 +2550,74 @@ extern "C" int myr_fit_grad_sets(myr_handle h, int32_t E, int32_t R, int32_t num
   st.out(a.grad, grad, grad_stride ? rows * dm.np : (size_t)E * dm.np);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_fit(h, a, grad_stride)) return rc;
+  return st.finish();
+}
+
+// the refusals myr_fit_gn and myr_fit_gn_sets share, behind their argument checks: the network system, then myr_fit_grad's
+static int check_fit_gn_system(myr_handle h, const char* who) {
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
+    return arg_fail(who, MYR_E_UNSUPPORTED, "the network system's 4 804 x 4 804 Gauss-Newton matrix is not formed; use myr_fit_grad for its loss and gradient");
+  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
+  if (!fit_supported(h->d.system_id))
+    return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
+                                     : no_such_path(h, who);
+  return MYR_OK;
+}
+
+extern "C" int myr_fit_gn(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                          const double* wt, const double* params, int32_t params_stride, double* loss, double* grad, double* gn,
+                          int32_t out_stride, int32_t mem) {
+  const char* who = "myr_fit_gn";
+  if (!h || !xs_obs || !us || !gn) return fail(MYR_E_ARG, "myr_fit_gn: null handle, xs_obs, us or gn");
+  if (B < 0 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_gn: bad sizes");
+  if (int rc = check_row_stride(h, who, "out_stride", out_stride, ROW_SUM_BATCH, "trajectory")) return rc;
+  if (int rc = check_stride(h, who, params, params_stride)) return rc;
+  if (int rc = check_mem(who, mem)) return rc;
+  if (int rc = check_fit_gn_system(h, who)) return rc;
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t np = (size_t)dm.np, nout = out_stride ? (size_t)B : 1;
+  FitArgs a{1, B, 0, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, params && params_stride != 0, nullptr, nullptr, nullptr};      // one set
+  DevStage st = call_stage(h, mem);
+  st.in(a.xs_obs, xs_obs, (size_t)B * (num_steps + 1) * dm.ns);
+  st.in(a.us, us, (size_t)B * u_rows * dm.nu);
+  st.in(a.wt, wt, (size_t)num_steps + 1);
+  st.in(a.params, params, n_params(h, params, params_stride, B));
+  st.out(a.loss, loss, (size_t)B);
+  st.out(a.grad, grad, nout * np);
+  st.out(a.gn, gn, nout * np * np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_fit(h, a, out_stride)) return rc;
+  return st.finish();
+}
+
+extern "C" int myr_fit_gn_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                               int32_t data_shared, const double* wt, const double* params, double* loss, double* grad, double* gn,
+                               int32_t out_stride, int32_t mem) {
+  const char* who = "myr_fit_gn_sets";
+  if (!h || !xs_obs || !us || !gn || !params) return fail(MYR_E_ARG, "myr_fit_gn_sets: null handle, xs_obs, us, gn or params");
+  if (E < 0 || R < 1 || num_steps < 1 || u_rows < 1 || (long)E * R > 0x7fffffffL) return fail(MYR_E_ARG, "myr_fit_gn_sets: bad sizes");
+  if (int rc = check_row_stride(h, who, "out_stride", out_stride, "a row per set: the sum over its trajectories", "trajectory")) return rc;
+  if (data_shared != 0 && data_shared != 1) return fail(MYR_E_ARG, "myr_fit_gn_sets: data_shared must be 0 (data per set) or 1 (one set of data, read by every set)");
+  if (int rc = check_mem(who, mem)) return rc;
+  if (int rc = check_fit_gn_system(h, who)) return rc;
+  if (E == 0) return MYR_OK;                          // (nothing is written)
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t np = (size_t)dm.np, rows = (size_t)E * R, drows = data_shared ? (size_t)R : rows, nout = out_stride ? rows : (size_t)E;
+  FitArgs a{E, R, data_shared, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+  DevStage st = call_stage(h, mem);
+  st.in(a.xs_obs, xs_obs, drows * (num_steps + 1) * dm.ns);
+  st.in(a.us, us, drows * u_rows * dm.nu);
+  st.in(a.wt, wt, (size_t)num_steps + 1);
+  st.in(a.params, params, (size_t)E * np);
+  st.out(a.loss, loss, rows);
+  st.out(a.grad, grad, nout * np);
+  st.out(a.gn, gn, nout * np * np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_fit(h, a, out_stride)) return rc;
   return st.finish();
 }
 

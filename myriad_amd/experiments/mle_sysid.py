@@ -3,7 +3,11 @@
 The reference integrates a batch of recorded control sequences with `parametrized_dynamics`, takes the (discounted) mean squared
 distance to the recorded states and descends jax.grad(loss) with optax.adam(1e-3).  Here loss and gradient are ONE device call
 (myr_fit_grad, csrc/fit.h) and Adam runs in numpy on the host.  No plotting, pickling or CSV; the planning comparison that follows the fit
-in the reference (:226-) is `useful_scripts.plan_with_params`' business."""
+in the reference (:226-) is `useful_scripts.plan_with_params`' business.
+
+Beside the reference's recipe: the fit is a least-squares problem in a handful of unknowns, and myr_fit_gn (csrc/fit_gn.h) returns its Gauss-Newton
+matrix with the loss and gradient -- run_mle_sysid_gn / run_mle_sysid_gn_sets fit the same keys by Levenberg-Marquardt in tens of device calls and
+report the parameter covariance."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -78,6 +82,203 @@ class FitLoss:
       g = row * sign
       grads.append({k: float(g[names.index(k)]) for k in params})
     return values, grads
+
+
+  # ---- with the Gauss-Newton matrix (myr_fit_gn, csrc/fit_gn.h) ---------------------------------------------------------------
+  def _in_keys(self, params, sign, loss, grad, gn):
+    """(value, grad mapping, gn [K,K]) in the keys of `params`, in their order: split_params' sign rule is d|p|/dp = sign on grad and
+    sign_i sign_j on gn; the parameters that are not fitted drop out."""
+    names = self.system.param_names
+    idx = [names.index(k) for k in params]
+    g = (grad * sign)[idx]
+    G = (gn * np.outer(sign, sign))[np.ix_(idx, idx)]
+    return float(loss.sum()), {k: float(v) for k, v in zip(params, g)}, G
+
+  def value_grad_gn(self, params: Dict[str, float], dataset, epoch=0):
+    """(loss, its gradient as a mapping, its Gauss-Newton matrix [K,K]) in the K keys of `params`, rows and columns in their order: one
+    myr_fit_gn call.  loss(params + d) ~ loss + grad . d + d . gn d / 2."""
+    ns = self.hp.state_size
+    dataset = np.asarray(dataset, dtype=np.float64)
+    p, sign = split_params(self.system, params)
+    out = self.engine.fit_gn(dataset[:, :, :ns], dataset[:, :, ns:], params=p, wt=loss_weights(self.hp, dataset.shape[0], epoch), reduce=True)
+    return self._in_keys(params, sign, out["loss"], out["grad"], out["gn"])
+
+  def values_grads_gns(self, params_sets, datasets, epoch=0):
+    """value_grad_gn for E parameter mappings at once (one myr_fit_gn_sets call): datasets [E,M,S+1,ns+nu], or [M,S+1,ns+nu] read by every
+    set.  Returns (values, grads, gns): E floats, E mappings, E matrices; entry e is value_grad_gn(params_sets[e], datasets[e], epoch) to the bit."""
+    ns = self.hp.state_size
+    datasets = np.asarray(datasets, dtype=np.float64)
+    split = [split_params(self.system, params) for params in params_sets]
+    out = self.engine.fit_gn_sets(datasets[..., :ns], datasets[..., ns:], np.stack([p for p, _ in split]),
+                                  wt=loss_weights(self.hp, datasets.shape[-3], epoch), reduce=True)
+    rows = [self._in_keys(params, sign, out["loss"][e], out["grad"][e], out["gn"][e]) for e, (params, (_, sign)) in enumerate(zip(params_sets, split))]
+    return [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
+
+
+class LevenbergMarquardt:
+  """Levenberg-Marquardt on a mapping of floats, driven from outside so that many fits can run in lockstep:
+    begin(value, grad, gn) at the start point; then, until `done`, p = trial() and end(value, grad, gn) with the evaluation at p.
+  A trial point is params + d with (G + lam diag(G)) d = -g on the keys whose diagonal entry of G is positive (a key the data do not move stays).
+  It is accepted only if its loss is lower -- the evaluation is then the next iteration's: one call per iteration --, lam / 3 on acceptance, lam * 4
+  on rejection, lam = 1e-3 at the start.  Stops on an accepted relative decrease of the loss below `rtol`, at `max_iter` trial points, or once the
+  loss is below `ftol` times the loss at the start (residuals at the rounding level of the rollout: a decrease there is noise)."""
+
+  def __init__(self, params: Dict[str, float], lam=1e-3, rtol=1e-12, max_iter=50, ftol=1e-24):
+    self.params = dict(params)
+    self.keys = list(params)
+    self.lam, self.rtol, self.max_iter, self.ftol = float(lam), rtol, max_iter, ftol
+    self.iterations, self.done = 0, False
+    self.loss = self.loss0 = None
+    self.grad = self.gn = self._trial = None
+
+  def begin(self, value, grad, gn):
+    self.loss = self.loss0 = float(value)
+    self.grad, self.gn = np.array([grad[k] for k in self.keys], dtype=np.float64), np.array(gn, dtype=np.float64)
+    self.done = self.max_iter < 1 or not self.loss > 0.0
+
+  def step(self) -> np.ndarray:
+    """d [K] of the current point, gradient, matrix and lam"""
+    d = np.zeros(len(self.keys))
+    diag = np.diag(self.gn)
+    on = np.flatnonzero(diag > 0.0)
+    if on.size:
+      A = self.gn[np.ix_(on, on)] + self.lam * np.diag(diag[on])
+      try:
+        d[on] = np.linalg.solve(A, -self.grad[on])
+      except np.linalg.LinAlgError:
+        d[on] = np.linalg.lstsq(A, -self.grad[on], rcond=None)[0]
+    return d
+
+  def trial(self) -> Dict[str, float]:
+    d = self.step()
+    self._trial = {k: float(self.params[k] + d[i]) for i, k in enumerate(self.keys)}
+    return dict(self._trial)
+
+  def end(self, value, grad, gn) -> bool:
+    """the evaluation at the last trial point; True: the point was accepted"""
+    self.iterations += 1
+    value = float(value)
+    accepted = value < self.loss
+    if accepted:
+      decrease = (self.loss - value) / self.loss
+      self.params, self.loss = self._trial, value
+      self.grad, self.gn = np.array([grad[k] for k in self.keys], dtype=np.float64), np.array(gn, dtype=np.float64)
+      self.lam /= 3.0
+      if decrease < self.rtol or value <= self.ftol * self.loss0:
+        self.done = True
+    else:
+      self.lam *= 4.0
+    if self.iterations >= self.max_iter:
+      self.done = True
+    return accepted
+
+
+def parameter_covariance(gn, loss, n_residuals):
+  """Covariance of the fitted parameters, sigma^2 (gn / 2)^+ with sigma^2 = loss / (n_residuals - rank): gn / 2 = J^T W J is the Fisher
+  information of the fit up to the noise variance, which the residuals estimate.  The pseudo-inverse runs over the keys with a positive diagonal
+  entry (the others get rows and columns of 0: the data say nothing about them); rank is that block's."""
+  gn = np.asarray(gn, dtype=np.float64)
+  cov = np.zeros_like(gn)
+  on = np.flatnonzero(np.diag(gn) > 0.0)
+  rank = 0
+  if on.size:
+    F = 0.5 * gn[np.ix_(on, on)]
+    rank = int(np.linalg.matrix_rank(F, hermitian=True))
+    dof = n_residuals - rank
+    sigma2 = float(loss) / dof if dof > 0 else float("nan")
+    cov[np.ix_(on, on)] = sigma2 * np.linalg.pinv(F, hermitian=True)
+  return cov
+
+
+def _gn_result(hp, lm, record, best_params, n_train):
+  out = dict(record)
+  out.update({"params": best_params, "last_params": dict(lm.params), "iterations": lm.iterations, "gn": lm.gn,
+              "covariance": parameter_covariance(lm.gn, lm.loss, n_train * hp.num_steps * hp.state_size)})
+  return out
+
+
+def run_mle_sysid_gn(hp: HParams, cfg: Config, dataset=None, max_iter: int = 50, rtol: float = 1e-12, fit=None, guess=None) -> dict:
+  """run_mle_sysid's fit by Levenberg-Marquardt on the Gauss-Newton matrix (myr_fit_gn): the same keys from the same start, the reference's loss at
+  epoch 0 (fixed discount weights), tens of device calls where Adam makes hp.num_epochs * 10.  Train and validation loss are recorded at the start
+  and after every accepted step ("epochs": the iteration it was accepted in); "params" are those with the lowest validation loss.  Returns
+  run_mle_sysid's dictionary plus "iterations" (trial points evaluated), "gn" (at the last parameters, in the order of their keys) and "covariance"
+  (parameter_covariance).  fit: a FitLoss to run on (tests: one with a host stand-in for the engine); it is left open.  guess: the starting
+  mapping, whose keys are fitted (default: defaults.param_guesses[hp.system])."""
+  if dataset is None:
+    dataset = generate_dataset(hp, cfg)
+  dataset = np.asarray(dataset, dtype=np.float64)
+  train_set, val_set = dataset[:hp.train_size], dataset[hp.train_size:dataset.shape[0] - hp.test_size]
+  own_fit = fit is None
+  if own_fit:
+    fit = FitLoss(hp)
+  lm = LevenbergMarquardt(param_guesses[hp.system] if guess is None else guess, rtol=rtol, max_iter=max_iter)
+  record = {"epochs": [], "train_losses": [], "val_losses": []}
+  best = [None, None]                                             # lowest validation loss, its parameters
+
+  def note(epoch):
+    val_loss = fit(lm.params, val_set, 0) if val_set.shape[0] else lm.loss
+    record["epochs"].append(epoch); record["train_losses"].append(lm.loss); record["val_losses"].append(val_loss)
+    if cfg.verbose:
+      print("loss", lm.loss, "val loss", val_loss, "lambda", lm.lam)
+    if np.isnan(lm.loss):
+      raise FloatingPointError(f"mle_sysid: the loss is NaN at params {lm.params}")
+    if best[0] is None or val_loss < best[0]:
+      best[0], best[1] = val_loss, dict(lm.params)
+
+  lm.begin(*fit.value_grad_gn(lm.params, train_set, 0))
+  note(0)
+  while not lm.done:
+    if lm.end(*fit.value_grad_gn(lm.trial(), train_set, 0)):
+      note(lm.iterations)
+  if own_fit:
+    fit.engine.close()
+  return _gn_result(hp, lm, record, best[1], train_set.shape[0])
+
+
+def run_mle_sysid_gn_sets(hp: HParams, cfg: Config, datasets, guesses=None, max_iter: int = 50, rtol: float = 1e-12, fit=None) -> list:
+  """run_mle_sysid_gn for E datasets [E][train+val+test][S+1][ns+nu] at once (`guesses`: E starting mappings, default
+  defaults.param_guesses[hp.system] for every set): the fits run in lockstep, every iteration of all of them in one myr_fit_gn_sets call.  Each set
+  has its own lambda, record and stopping state, and leaves the later calls once it has stopped.  Returns E dictionaries; entry e is what
+  run_mle_sysid_gn(hp, cfg, datasets[e]) returns (from guesses[e]): the same arithmetic, equal values."""
+  datasets = np.asarray(datasets, dtype=np.float64)
+  E = datasets.shape[0]
+  train_sets, val_sets = datasets[:, :hp.train_size], datasets[:, hp.train_size:datasets.shape[1] - hp.test_size]
+  own_fit = fit is None
+  if own_fit:
+    fit = FitLoss(hp)
+  lms = [LevenbergMarquardt(param_guesses[hp.system] if guesses is None else guesses[e], rtol=rtol, max_iter=max_iter) for e in range(E)]
+  records = [{"epochs": [], "train_losses": [], "val_losses": []} for _ in range(E)]
+  best = [[None, None] for _ in range(E)]
+
+  def note(sets):
+    if not sets:
+      return
+    if val_sets.shape[1]:
+      val_losses = fit.values_and_grads([lms[e].params for e in sets], val_sets[sets], 0, want_grad=False)[0]
+    else:
+      val_losses = [lms[e].loss for e in sets]
+    for e, val_loss in zip(sets, val_losses):
+      lm, r = lms[e], records[e]
+      r["epochs"].append(lm.iterations); r["train_losses"].append(lm.loss); r["val_losses"].append(val_loss)
+      if cfg.verbose:
+        print(e, "loss", lm.loss, "val loss", val_loss, "lambda", lm.lam)
+      if np.isnan(lm.loss):
+        raise FloatingPointError(f"mle_sysid: the loss of set {e} is NaN at params {lm.params}")
+      if best[e][0] is None or val_loss < best[e][0]:
+        best[e][0], best[e][1] = val_loss, dict(lm.params)
+
+  live = list(range(E))
+  for e, value, grad, gn in zip(live, *fit.values_grads_gns([lm.params for lm in lms], train_sets, 0)):
+    lms[e].begin(value, grad, gn)
+  note(live)
+  live = [e for e in live if not lms[e].done]
+  while live:
+    evals = fit.values_grads_gns([lms[e].trial() for e in live], train_sets[live], 0)
+    note([e for e, value, grad, gn in zip(live, *evals) if lms[e].end(value, grad, gn)])
+    live = [e for e in live if not lms[e].done]
+  if own_fit:
+    fit.engine.close()
+  return [_gn_result(hp, lms[e], records[e], best[e][1], train_sets.shape[1]) for e in range(E)]
 
 
 class Adam:
