@@ -319,68 +319,20 @@ class Engine:
                               _addr(xs), _addr(cost), MEM_HOST), "myr_rollout")
     return xs, cost
 
-  def fit_grad(self, xs_obs, us, params=None, wt=None, reduce=False):
-    """myr_fit_grad: trajectory-matching loss and its gradient in the model parameters.  xs_obs [B,S+1,ns] (recorded states; the
-    rollout starts from xs_obs[:,0]), us [B,u_rows,nu], params [np] (shared) or [B,np] (None: the system's defaults), wt [S+1]
-    (None: 1).  Returns {"loss" [B], "grad" [B,np], or [np] = the sum over the batch with reduce=True}."""
-    xs_obs = _f64(xs_obs)
-    us = _f64(us)
-    if xs_obs.ndim == 2:
-      xs_obs = xs_obs[None]
-    if us.ndim == 2:
-      us = us[None]
-    B, S = xs_obs.shape[0], xs_obs.shape[1] - 1
-    if xs_obs.ndim != 3 or xs_obs.shape[2] != self.ns or S < 1:
-      raise ValueError(f"xs_obs must be [B,S+1,{self.ns}] with S >= 1")
-    if us.ndim != 3 or us.shape[0] != B or us.shape[2] != self.nu:
-      raise ValueError(f"us must be [B,u_rows,{self.nu}]")
-    p, ps = self._params(params, B)
-    w = None if wt is None else _f64(wt, (S + 1,))
-    loss = np.empty(B)
-    grad = np.empty(self.np) if reduce else np.empty((B, self.np))
-    _chk(self.lib.myr_fit_grad(self._h, B, S, int(us.shape[1]), _addr(xs_obs), _addr(us), _addr(w), _addr(p), ps, _addr(loss),
-                               _addr(grad), 0 if reduce else self.np, MEM_HOST), "myr_fit_grad")
-    return {"loss": loss, "grad": grad}
+  # ---- trajectory-matching fit: myr_fit_grad, myr_fit_gn and their _sets forms ------------------------------------
+  def _fit_call(self, call, mem, B, num_steps, u_rows, xs_obs, us, wt, params, params_stride, outs, row_stride):
+    """the C call of the single-set pair: `outs` is (loss, grad) for myr_fit_grad, (loss, grad, gn) for myr_fit_gn; the arrays are host or device
+    ones, as `mem` says"""
+    _chk(getattr(self.lib, call)(self._h, int(B), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), _addr(wt), _addr(params), int(params_stride),
+                                 *map(_addr, outs), int(row_stride), mem), call)
 
-  def fit_grad_device(self, B, num_steps, u_rows, xs_obs, us, grad, grad_stride, params=None, params_stride=0, wt=None, loss=None):
-    """Zero-copy variant of fit_grad: every array is a device tensor on this handle's device."""
-    _chk(self.lib.myr_fit_grad(self._h, int(B), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), _addr(wt), _addr(params),
-                               int(params_stride), _addr(loss), _addr(grad), int(grad_stride), MEM_DEVICE), "myr_fit_grad")
+  def _fit_sets_call(self, call, mem, E, R, num_steps, u_rows, xs_obs, us, data_shared, wt, params, outs, row_stride):
+    """... and of the sets pair (myr_fit_grad_sets, myr_fit_gn_sets)"""
+    _chk(getattr(self.lib, call)(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
+                                 _addr(params), *map(_addr, outs), int(row_stride), mem), call)
 
-  def fit_grad_sets(self, xs_obs, us, params, wt=None, reduce=False, want_grad=True):
-    """myr_fit_grad_sets: fit_grad for E independent parameter sets of R trajectories each in one call.  params [E,np]; xs_obs [E,R,S+1,ns] and
-    us [E,R,u_rows,nu], or [R,S+1,ns] and [R,u_rows,nu]: one set of data that every parameter set reads; wt [S+1] (None: 1), shared by all sets.
-    Returns {"loss" [E,R], "grad" [E,R,np], or [E,np] = per set the sum over its trajectories with reduce=True}; want_grad=False: the loss only
-    (no reverse sweep, no "grad").  Set e has the bits of fit_grad on that set alone."""
-    xs_obs, us, params = _f64(xs_obs), _f64(us), _f64(params)
-    if params.ndim != 2 or params.shape[1] != self.np:
-      raise ValueError(f"params must be [E,{self.np}]")
-    E = params.shape[0]
-    if xs_obs.ndim not in (3, 4) or us.ndim != xs_obs.ndim:
-      raise ValueError("xs_obs and us must both be [E,R,...] (data per set) or both [R,...] (data shared by the sets)")
-    shared = xs_obs.ndim == 3
-    lead = () if shared else (E,)
-    R, S = xs_obs.shape[-3], xs_obs.shape[-2] - 1
-    if xs_obs.shape[:-3] != lead or xs_obs.shape[-1] != self.ns or S < 1 or R < 1:
-      raise ValueError(f"xs_obs must be [{'' if shared else 'E,'}R,S+1,{self.ns}] with R >= 1, S >= 1 and E = {E} as in params")
-    if us.shape[:-2] != lead + (R,) or us.shape[-1] != self.nu or us.shape[-2] < 1:
-      raise ValueError(f"us must be [{'' if shared else 'E,'}R,u_rows,{self.nu}]")
-    w = None if wt is None else _f64(wt, (S + 1,))
-    loss = np.empty((E, R))
-    grad = (np.empty((E, self.np)) if reduce else np.empty((E, R, self.np))) if want_grad else None
-    _chk(self.lib.myr_fit_grad_sets(self._h, E, R, S, int(us.shape[-2]), _addr(xs_obs), _addr(us), int(shared), _addr(w), _addr(params), _addr(loss),
-                                    _addr(grad), 0 if reduce else self.np, MEM_HOST), "myr_fit_grad_sets")
-    return {"loss": loss, "grad": grad} if want_grad else {"loss": loss}
-
-  def fit_grad_sets_device(self, E, R, num_steps, u_rows, xs_obs, us, params, grad=None, grad_stride=0, data_shared=False, wt=None, loss=None):
-    """Zero-copy variant of fit_grad_sets: every array is a device tensor on this handle's device; grad=None: the loss only."""
-    _chk(self.lib.myr_fit_grad_sets(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
-                                    _addr(params), _addr(loss), _addr(grad), int(grad_stride), MEM_DEVICE), "myr_fit_grad_sets")
-
-  def fit_gn(self, xs_obs, us, params=None, wt=None, reduce=False):
-    """myr_fit_gn: fit_grad's loss and gradient with the Gauss-Newton matrix gn = 2 J^T W J of the fit (J: the sensitivity of the rolled-out
-    states in the parameters), by one forward pass.  Arguments as fit_grad.  Returns {"loss" [B], "grad" [B,np], "gn" [B,np,np]}; with
-    reduce=True "grad" [np] and "gn" [np,np] are the sums over the batch."""
+  def _fit(self, call, with_gn, xs_obs, us, params, wt, reduce):
+    """fit_grad and fit_gn: the shape rules they share, the result arrays and the call"""
     xs_obs = _f64(xs_obs)
     us = _f64(us)
     if xs_obs.ndim == 2:
@@ -395,20 +347,13 @@ class Engine:
     p, ps = self._params(params, B)
     w = None if wt is None else _f64(wt, (S + 1,))
     lead = () if reduce else (B,)
-    loss, grad, gn = np.empty(B), np.empty(lead + (self.np,)), np.empty(lead + (self.np, self.np))
-    _chk(self.lib.myr_fit_gn(self._h, B, S, int(us.shape[1]), _addr(xs_obs), _addr(us), _addr(w), _addr(p), ps, _addr(loss), _addr(grad), _addr(gn),
-                             0 if reduce else self.np, MEM_HOST), "myr_fit_gn")
-    return {"loss": loss, "grad": grad, "gn": gn}
+    loss, grad = np.empty(B), np.empty(lead + (self.np,))
+    gn = np.empty(lead + (self.np, self.np)) if with_gn else None
+    self._fit_call(call, MEM_HOST, B, S, us.shape[1], xs_obs, us, w, p, ps, (loss, grad, gn)[:3 if with_gn else 2], 0 if reduce else self.np)
+    return self._present(loss=loss, grad=grad, gn=gn)
 
-  def fit_gn_device(self, B, num_steps, u_rows, xs_obs, us, gn, out_stride, params=None, params_stride=0, wt=None, loss=None, grad=None):
-    """Zero-copy variant of fit_gn: every array is a device tensor on this handle's device (loss, grad may be None)."""
-    _chk(self.lib.myr_fit_gn(self._h, int(B), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), _addr(wt), _addr(params), int(params_stride),
-                             _addr(loss), _addr(grad), _addr(gn), int(out_stride), MEM_DEVICE), "myr_fit_gn")
-
-  def fit_gn_sets(self, xs_obs, us, params, wt=None, reduce=False):
-    """myr_fit_gn_sets: fit_gn for E independent parameter sets of R trajectories each in one call; arguments as fit_grad_sets.  Returns
-    {"loss" [E,R], "grad" [E,R,np], "gn" [E,R,np,np]}; with reduce=True "grad" [E,np] and "gn" [E,np,np] are, per set, the sums over its
-    trajectories.  Set e has the bits of fit_gn on that set alone."""
+  def _fit_sets(self, call, with_gn, xs_obs, us, params, wt, reduce, want_grad):
+    """fit_grad_sets and fit_gn_sets: the same for E parameter sets"""
     xs_obs, us, params = _f64(xs_obs), _f64(us), _f64(params)
     if params.ndim != 2 or params.shape[1] != self.np:
       raise ValueError(f"params must be [E,{self.np}]")
@@ -424,15 +369,53 @@ class Engine:
       raise ValueError(f"us must be [{'' if shared else 'E,'}R,u_rows,{self.nu}]")
     w = None if wt is None else _f64(wt, (S + 1,))
     out = (E,) if reduce else (E, R)
-    loss, grad, gn = np.empty((E, R)), np.empty(out + (self.np,)), np.empty(out + (self.np, self.np))
-    _chk(self.lib.myr_fit_gn_sets(self._h, E, R, S, int(us.shape[-2]), _addr(xs_obs), _addr(us), int(shared), _addr(w), _addr(params), _addr(loss),
-                                  _addr(grad), _addr(gn), 0 if reduce else self.np, MEM_HOST), "myr_fit_gn_sets")
-    return {"loss": loss, "grad": grad, "gn": gn}
+    loss = np.empty((E, R))
+    grad = np.empty(out + (self.np,)) if want_grad else None
+    gn = np.empty(out + (self.np, self.np)) if with_gn else None
+    self._fit_sets_call(call, MEM_HOST, E, R, S, us.shape[-2], xs_obs, us, shared, w, params, (loss, grad, gn)[:3 if with_gn else 2],
+                        0 if reduce else self.np)
+    return self._present(loss=loss, grad=grad, gn=gn)
+
+  def fit_grad(self, xs_obs, us, params=None, wt=None, reduce=False):
+    """myr_fit_grad: trajectory-matching loss and its gradient in the model parameters.  xs_obs [B,S+1,ns] (recorded states; the
+    rollout starts from xs_obs[:,0]), us [B,u_rows,nu], params [np] (shared) or [B,np] (None: the system's defaults), wt [S+1]
+    (None: 1).  Returns {"loss" [B], "grad" [B,np], or [np] = the sum over the batch with reduce=True}."""
+    return self._fit("myr_fit_grad", False, xs_obs, us, params, wt, reduce)
+
+  def fit_grad_device(self, B, num_steps, u_rows, xs_obs, us, grad, grad_stride, params=None, params_stride=0, wt=None, loss=None):
+    """Zero-copy variant of fit_grad: every array is a device tensor on this handle's device."""
+    self._fit_call("myr_fit_grad", MEM_DEVICE, B, num_steps, u_rows, xs_obs, us, wt, params, params_stride, (loss, grad), grad_stride)
+
+  def fit_grad_sets(self, xs_obs, us, params, wt=None, reduce=False, want_grad=True):
+    """myr_fit_grad_sets: fit_grad for E independent parameter sets of R trajectories each in one call.  params [E,np]; xs_obs [E,R,S+1,ns] and
+    us [E,R,u_rows,nu], or [R,S+1,ns] and [R,u_rows,nu]: one set of data that every parameter set reads; wt [S+1] (None: 1), shared by all sets.
+    Returns {"loss" [E,R], "grad" [E,R,np], or [E,np] = per set the sum over its trajectories with reduce=True}; want_grad=False: the loss only
+    (no reverse sweep, no "grad").  Set e has the bits of fit_grad on that set alone."""
+    return self._fit_sets("myr_fit_grad_sets", False, xs_obs, us, params, wt, reduce, want_grad)
+
+  def fit_grad_sets_device(self, E, R, num_steps, u_rows, xs_obs, us, params, grad=None, grad_stride=0, data_shared=False, wt=None, loss=None):
+    """Zero-copy variant of fit_grad_sets: every array is a device tensor on this handle's device; grad=None: the loss only."""
+    self._fit_sets_call("myr_fit_grad_sets", MEM_DEVICE, E, R, num_steps, u_rows, xs_obs, us, data_shared, wt, params, (loss, grad), grad_stride)
+
+  def fit_gn(self, xs_obs, us, params=None, wt=None, reduce=False):
+    """myr_fit_gn: fit_grad's loss and gradient with the Gauss-Newton matrix gn = 2 J^T W J of the fit (J: the sensitivity of the rolled-out
+    states in the parameters), by one forward pass.  Arguments as fit_grad.  Returns {"loss" [B], "grad" [B,np], "gn" [B,np,np]}; with
+    reduce=True "grad" [np] and "gn" [np,np] are the sums over the batch."""
+    return self._fit("myr_fit_gn", True, xs_obs, us, params, wt, reduce)
+
+  def fit_gn_device(self, B, num_steps, u_rows, xs_obs, us, gn, out_stride, params=None, params_stride=0, wt=None, loss=None, grad=None):
+    """Zero-copy variant of fit_gn: every array is a device tensor on this handle's device (loss, grad may be None)."""
+    self._fit_call("myr_fit_gn", MEM_DEVICE, B, num_steps, u_rows, xs_obs, us, wt, params, params_stride, (loss, grad, gn), out_stride)
+
+  def fit_gn_sets(self, xs_obs, us, params, wt=None, reduce=False):
+    """myr_fit_gn_sets: fit_gn for E independent parameter sets of R trajectories each in one call; arguments as fit_grad_sets.  Returns
+    {"loss" [E,R], "grad" [E,R,np], "gn" [E,R,np,np]}; with reduce=True "grad" [E,np] and "gn" [E,np,np] are, per set, the sums over its
+    trajectories.  Set e has the bits of fit_gn on that set alone."""
+    return self._fit_sets("myr_fit_gn_sets", True, xs_obs, us, params, wt, reduce, True)
 
   def fit_gn_sets_device(self, E, R, num_steps, u_rows, xs_obs, us, params, gn, out_stride=0, data_shared=False, wt=None, loss=None, grad=None):
     """Zero-copy variant of fit_gn_sets: every array is a device tensor on this handle's device (loss, grad may be None)."""
-    _chk(self.lib.myr_fit_gn_sets(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
-                                  _addr(params), _addr(loss), _addr(grad), _addr(gn), int(out_stride), MEM_DEVICE), "myr_fit_gn_sets")
+    self._fit_sets_call("myr_fit_gn_sets", MEM_DEVICE, E, R, num_steps, u_rows, xs_obs, us, data_shared, wt, params, (loss, grad, gn), out_stride)
 
   # ---- Lagrangian products / extragradient (collocation transcriptions) ------------------------
   def _batch2(self, a, width, name):

@@ -14,15 +14,28 @@
 
 namespace myriad {
 
+// The fixed-step rules, by `method` (0 Euler, 1 Heun, 2 midpoint, 3 RK4).  Every rule is X[0] = x, X[j+1] = x + a[j] h f(X[j], Uc[j]) and
+// x+ = x + h sum_j bw[j] f(X[j], Uc[j]):
+//   Euler     1 stage,  bw = {1}
+//   Heun      2 stages, a = {1}, bw = {1/2, 1/2}, controls u_s, u_{s+1}
+//   midpoint  2 stages, a = {1}, bw = {0, 1},     controls u_s, (u_s + u_{s+1}) / 2      (a full Euler predictor: Q11)
+//   RK4       4 stages, a = {1/2, 1/2, 1}, bw = {1/6, 1/3, 1/3, 1/6}, controls u_{2s}, u_{2s+1}, u_{2s+1}, u_{2s+2}   (Q5)
+// fit_stage_weights(method, a, bw) is that table as numbers, for the sweeps that differentiate a step (FitLane::run, FitGnLane::run; NodeFit::plan
+// keeps a copy): a[j] is the weight of stage j in the NEXT stage point X[j+1], bw[j] its weight in the step (four entries each: those from the last
+// stage on are not read; the number of stages is what FitLane::stages returns).  It writes the caller's arrays entry by entry and is always inlined:
+// so the callers' device code is that of the table written out in place (a table returned by value, or filled by a constructor, or a stage count
+// returned beside it, changed fit_lane_kernel and fit_gn_lane_kernel).
+MYR_HD inline __attribute__((always_inline)) void fit_stage_weights(int method, double* a, double* bw) {
+  a[0] = method == 3 ? 0.5 : 1.0; a[1] = 0.5; a[2] = 1.0; a[3] = 0.0;
+  bw[0] = method == 0 ? 1.0 : (method == 1 ? 0.5 : (method == 2 ? 0.0 : 1.0 / 6.0));
+  bw[1] = method == 1 ? 0.5 : (method == 2 ? 1.0 : 1.0 / 3.0); bw[2] = 1.0 / 3.0; bw[3] = 1.0 / 6.0;
+}
+
 template <class Sys>
 struct FitLane {
   static constexpr int NS = Sys::NS, NU = Sys::NU, NP = Sys::NP;
 
-  // Stage points of step s from its state x: every rule is X[0] = x, X[j+1] = x + a[j] h f(X[j], Uc[j]) and x+ = x + h sum_j bw[j] f(X[j], Uc[j]):
-  //   Euler     1 stage,  bw = {1}
-  //   Heun      2 stages, a = {1}, bw = {1/2, 1/2}, controls u_s, u_{s+1}
-  //   midpoint  2 stages, a = {1}, bw = {0, 1},     controls u_s, (u_s + u_{s+1}) / 2      (a full Euler predictor: Q11)
-  //   RK4       4 stages, a = {1/2, 1/2, 1}, bw = {1/6, 1/3, 1/3, 1/6}, controls u_{2s}, u_{2s+1}, u_{2s+1}, u_{2s+2}   (Q5)
+  // Stage points X[j] and controls Uc[j] of step s from its state x, by the table above fit_stage_weights.
   // With NEXT the state after the step replaces x, in the arithmetic of Rollout<Sys>::run.  Returns the number of stages.
   template <bool NEXT>
   MYR_HD static inline int stages(int method, int s, double h, int u_rows, const double* us, const double* p, double* x,
@@ -124,11 +137,8 @@ struct FitLane {
 #pragma unroll
       for (int i = 0; i < NS; ++i) x[i] = xh[((long)s * NS + i) * ld];
       const int nst = stages<false>(method, s, h, u_rows, us, p, x, X, Uc);
-      // a[j]: weight of stage j in the next stage point; bw[j]: its weight in the step
-      const double a0 = method == 3 ? 0.5 : 1.0, a1 = 0.5, a2 = 1.0;
-      const double b0 = method == 0 ? 1.0 : (method == 1 ? 0.5 : (method == 2 ? 0.0 : 1.0 / 6.0));
-      const double b1 = method == 1 ? 0.5 : (method == 2 ? 1.0 : 1.0 / 3.0), b2 = 1.0 / 3.0, b3 = 1.0 / 6.0;
-      const double av[4] = {a0, a1, a2, 0.0}, bv[4] = {b0, b1, b2, b3};
+      double av[4], bv[4];
+      fit_stage_weights(method, av, bv);
       double wx[NS], acc[NS];                                 // wx: cotangent of the stage point behind the current one
 #pragma unroll
       for (int i = 0; i < NS; ++i) { wx[i] = 0.0; acc[i] = 0.0; }
@@ -161,6 +171,18 @@ struct FitLane {
 };
 
 #if defined(__HIPCC__)
+// Where lane b of fit_lane_kernel / fit_gn_lane_kernel works (the rule is told below).  live: it has a trajectory of its own; t: the trajectory it
+// runs (the last one where it has none); d, prow: the rows of its data and of its parameters
+struct FitLaneAddr {
+  bool live; long t, d, prow;
+  __device__ FitLaneAddr(long b, int B, int R, int pdiv, int data_shared) {
+    live = b < B;
+    t = live ? b : (long)B - 1;
+    d = data_shared ? t % R : t;
+    prow = t / pdiv;
+  }
+};
+
 // One trajectory per lane: lane b of the launch is trajectory b mod R of parameter set b / R (B = E R lanes; myr_fit_grad is one set).  It reads
 // parameter row b / pdiv of `params` (pdiv = R: a row per set; pdiv = 1: a row per trajectory, myr_fit_grad with params_stride == np) and the data of
 // trajectory b, or of b mod R where every set reads the same R trajectories (data_shared).  Set boundaries fall inside wavefronts: a lane's arithmetic
@@ -173,15 +195,13 @@ void fit_lane_kernel(int B, int R, int pdiv, int data_shared, long Bp, int metho
                      const double* __restrict__ xs_obs, const double* __restrict__ us, const double* __restrict__ wt,
                      const double* __restrict__ params, double* __restrict__ xh, double* __restrict__ loss, double* __restrict__ grad) {
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;      // < Bp: the scratch has a column for every lane of the grid
-  const bool live = b < B;
-  const long bb = live ? b : (long)B - 1;
-  const long d = data_shared ? bb % R : bb;
+  const FitLaneAddr at(b, B, R, pdiv, data_shared);
   SysParams<Sys> pp;
-  pp.load(params, bb / pdiv, Sys::NP);
+  pp.load(params, at.prow, Sys::NP);
   double gp[Sys::NP];
-  const double l = FitLane<Sys>::run(method, num_steps, h, u_rows, xs_obs + d * (long)(num_steps + 1) * Sys::NS, us + d * (long)u_rows * Sys::NU,
+  const double l = FitLane<Sys>::run(method, num_steps, h, u_rows, xs_obs + at.d * (long)(num_steps + 1) * Sys::NS, us + at.d * (long)u_rows * Sys::NU,
                                      wt, pp.get(), xh + b, Bp, gp, grad != nullptr);
-  if (live) {
+  if (at.live) {
     if (loss) loss[b] = l;
     if (grad) {
 #pragma unroll
@@ -256,7 +276,8 @@ struct NodeFit {
     for (int c = 0; c < NS; ++c) ax[c] = wsum(wl[NM::L_W1 + c * H + lane] * e1);
   }
 
-  // stage controls and weights of step s (the table of FitLane::stages)
+  // stage controls and weights of step s.  The table of fit_stage_weights once more, in its index convention: a call of it here, in any of the forms
+  // tried, changed node_fit_kernel's instruction sequence
   __device__ static inline int plan(int method, int s, int u_rows, const double* us, double* uc, double* av, double* bv) {
     auto U = [&](int i) { return us[i < u_rows ? i : u_rows - 1]; };
     av[0] = method == 3 ? 0.5 : 1.0; av[1] = 0.5; av[2] = 1.0; av[3] = 0.0;

@@ -66,11 +66,8 @@ struct FitGnLane {
     for (int k = 0; k < NP; ++k) gp[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < NT; ++k) gu[k] = 0.0;
-    // a[j]: weight of stage j in the next stage point; bw[j]: its weight in the step (the table of FitLane::stages)
-    const double a0 = method == 3 ? 0.5 : 1.0, a1 = 0.5, a2 = 1.0;
-    const double b0 = method == 0 ? 1.0 : (method == 1 ? 0.5 : (method == 2 ? 0.0 : 1.0 / 6.0));
-    const double b1 = method == 1 ? 0.5 : (method == 2 ? 1.0 : 1.0 / 3.0), b2 = 1.0 / 3.0, b3 = 1.0 / 6.0;
-    const double av[4] = {0.0, a0, a1, a2}, bv[4] = {b0, b1, b2, b3};      // av[j]: the weight of stage j - 1 in stage point j
+    double av[4], bv[4];      // (fit.h: fit_stage_weights)
+    fit_stage_weights(method, av, bv);
     for (int s = 0; s < num_steps; ++s) {
       const int nst = FitLane<Sys>::template stages<true>(method, s, h, u_rows, us, p, x, X, Uc);
 #pragma unroll
@@ -81,7 +78,7 @@ struct FitGnLane {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j < nst) {                                      // (the same for every lane: the method is a kernel argument)
-          dstage(X[j], Uc[j], p, S, av[j] * h, dK);
+          dstage(X[j], Uc[j], p, S, (j == 0 ? 0.0 : av[j - 1]) * h, dK);      // (stage point j was made from stage j - 1)
 #pragma unroll
           for (int i = 0; i < NS; ++i) {
 #pragma unroll
@@ -156,15 +153,13 @@ void fit_gn_lane_kernel(int B, int R, int pdiv, int data_shared, int method, int
                         double* __restrict__ gn, long gn_ld) {
   using L = FitGnLane<Sys>;
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = b < B;
-  const long bb = live ? b : (long)B - 1;
-  const long d = data_shared ? bb % R : bb;
+  const FitLaneAddr at(b, B, R, pdiv, data_shared);
   SysParams<Sys> pp;
-  pp.load(params, bb / pdiv, Sys::NP);
+  pp.load(params, at.prow, Sys::NP);
   double gp[L::NP], gu[L::NT];
-  const double l = L::run(method, num_steps, h, u_rows, xs_obs + d * (long)(num_steps + 1) * Sys::NS, us + d * (long)u_rows * Sys::NU, wt, pp.get(),
-                          gp, gu, grad != nullptr);
-  if (live) {
+  const double l = L::run(method, num_steps, h, u_rows, xs_obs + at.d * (long)(num_steps + 1) * Sys::NS, us + at.d * (long)u_rows * Sys::NU, wt,
+                          pp.get(), gp, gu, grad != nullptr);
+  if (at.live) {
     if (loss) loss[b] = l;
     if (grad) {
 #pragma unroll

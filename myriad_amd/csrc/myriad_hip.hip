@@ -1145,6 +1145,10 @@ int rollout_for_system(myr_handle h, const RolloutArgs& a) {
 // ------------------------------------------------------------------------------------------------
 // trajectory-matching loss and its parameter gradient (fit.h: fit_lane_kernel, node_fit_kernel)
 // ------------------------------------------------------------------------------------------------
+// A system without generated parameter derivatives (the elastic twins): the one text for it.  The entry points refuse such a handle before anything is
+// launched (check_fit_has_derivatives); the two launchers below keep the branch because FitLane does not compile for such a system.
+static inline int fit_no_derivatives() { return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system"); }
+
 template <class Sys>
 int fit_for_system(myr_handle h, const FitArgs& a) {
   if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // a set of weights per workgroup (never per trajectory: myr_fit_grad has checked), one wavefront per trajectory
@@ -1153,7 +1157,7 @@ int fit_for_system(myr_handle h, const FitArgs& a) {
                        (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.xh, a.loss, a.grad);
     return MYR_OK;
   } else if constexpr (!SysDp<Sys>::SUPPORTED) {
-    return fail(MYR_E_UNSUPPORTED, std::string("myr_fit_grad: no parameter derivatives are generated for ") + Sys::NAME);
+    return fit_no_derivatives();
   } else {
     const long B = (long)a.E * a.R;
     hipLaunchKernelGGL(fit_lane_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, (int)B, a.R, a.per_row ? 1 : a.R, a.data_shared, a.Bp,
@@ -1163,12 +1167,11 @@ int fit_for_system(myr_handle h, const FitArgs& a) {
 }
 
 // ... and with the Gauss-Newton matrix, by forward sensitivities (fit_gn.h: fit_gn_lane_kernel).  myr_fit_gn* have refused the network system
+// (check_fit_gn_not_node), which has no SysDp either
 template <class Sys>
 int fit_gn_for_system(myr_handle h, const FitArgs& a) {
-  if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {
-    return fail(MYR_E_UNSUPPORTED, "myr_fit_gn: the network system's 4 804 x 4 804 matrix is not formed; use myr_fit_grad");
-  } else if constexpr (!SysDp<Sys>::SUPPORTED) {
-    return fail(MYR_E_UNSUPPORTED, std::string("myr_fit_grad: no parameter derivatives are generated for ") + Sys::NAME);
+  if constexpr (!SysDp<Sys>::SUPPORTED) {
+    return fit_no_derivatives();
   } else {
     const long B = (long)a.E * a.R;
     hipLaunchKernelGGL(fit_gn_lane_kernel<Sys>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, (int)B, a.R, a.per_row ? 1 : a.R, a.data_shared,
@@ -1688,6 +1691,33 @@ static int check_node_lds(myr_handle h, const char* who, int which) {
     what = "intervals too large for the LDS-resident reverse sweep beside the weight copy";
   }
   return lds > 160 * 1024 ? arg_fail(who, MYR_E_CAPACITY, what) : MYR_OK;
+}
+// ... and those of the fit family (myr_fit_grad, myr_fit_grad_sets, myr_fit_gn, myr_fit_gn_sets).  `sets`: E, or B for the single-set calls (which
+// pass R = 1 here); rows_an_int: E * R is bounded too (myr_fit_gn_sets only: its sibling never has been)
+static const char* const ROW_SUM_FIT_SETS = "a row per set: the sum over its trajectories";
+static int check_fit_sizes(const char* who, int sets, int R, int num_steps, int u_rows, bool rows_an_int = false) {
+  const bool bad = sets < 0 || R < 1 || num_steps < 1 || u_rows < 1 || (rows_an_int && (long)sets * R > 0x7fffffffL);
+  return bad ? arg_fail(who, MYR_E_ARG, "bad sizes") : MYR_OK;
+}
+static int check_data_shared(const char* who, int data_shared) {
+  return data_shared != 0 && data_shared != 1 ? arg_fail(who, MYR_E_ARG, "data_shared must be 0 (data per set) or 1 (one set of data, read by every set)") : MYR_OK;
+}
+// the systems no fit call serves.  A twin, and a system without derivatives, are answered in myr_fit_grad's name by all four
+static int check_fit_not_plant(myr_handle h, const char* who) { return h->d.system_id == MYR_SYS_INVASIVEPLANT ? no_such_path(h, who) : MYR_OK; }
+static int check_fit_not_twin(myr_handle h) {
+  return h->d.system_id >= 100 ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system") : MYR_OK;
+}
+static bool fit_supported(int id) {
+  return for_system(id, true, [](auto t) { using S = SYS_OF(t); return std::is_same<S, SysNODE_CARTPOLE>::value || SysDp<S>::SUPPORTED; }, [] { return false; });
+}
+static int check_fit_has_derivatives(myr_handle h, const char* who) {
+  if (fit_supported(h->d.system_id)) return MYR_OK;
+  SysInfo si;
+  return sys_info(h->d.system_id, &si) ? fit_no_derivatives() : no_such_path(h, who);
+}
+static int check_fit_gn_not_node(myr_handle h, const char* who) {
+  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE) return MYR_OK;
+  return arg_fail(who, MYR_E_UNSUPPORTED, "the network system's 4 804 x 4 804 Gauss-Newton matrix is not formed; use myr_fit_grad for its loss and gradient");
 }
 // doubles behind `params`: none, one shared set, or a set per instance
 static size_t n_params(myr_handle h, const double* params, int stride, int B) { return params ? (stride ? (size_t)B * h->dims.np : (size_t)h->dims.np) : 0; }
@@ -2400,11 +2430,6 @@ static __global__ __launch_bounds__(256) void fit_reduce_sets_kernel(int R, int 
   if (t == 0) out[e * np + k] = part[0];
 }
 
-static bool fit_supported(int id) {
-  return for_system(id, true, [](auto t) { using S = SYS_OF(t); return std::is_same<S, SysNODE_CARTPOLE>::value || SysDp<S>::SUPPORTED; }, [] { return false; });
-}
-static bool sys_known(int id) { SysInfo si; return sys_info(id, &si); }
-
 // parameter sets one launch of dispatch_fit takes: all of them, unless the per-set sums are asked for and the row scratch (E R np doubles) would pass
 // 1 GiB -- then whole sets, at least one; and never more than 2^30 trajectories (the kernels count them in an int)
 static int fit_sets_chunk(int E, int R, bool row_scratch, size_t width) {      // width: doubles of one trajectory's row (np; myr_fit_gn*: np + np^2)
@@ -2441,12 +2466,15 @@ static __global__ __launch_bounds__(256) void fit_gn_unpack_kernel(long n, int n
 // With a.gn (myr_fit_gn*) the forward-sensitivity kernel runs instead: no state scratch; a.gn is [E][R][np][np] beside a.grad (which may then be null
 // with either stride), or -- grad_stride == 0 -- [E][np][np] beside [E][np]: the lanes write packed rows [np + np^2], grad then gn, ONE reduction of
 // that width sums them per set in the same fixed order, and a copy takes the sums apart into the two arrays.
+static int launch_fit(myr_handle h, const FitArgs& a) {      // the kernel by a.gn
+  return for_system(h->d.system_id, true, [&](auto t) { return a.gn ? fit_gn_for_system<SYS_OF(t)>(h, a) : fit_for_system<SYS_OF(t)>(h, a); },
+                    [] { return (int)MYR_OK; });
+}
 static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
   const myr_dims& dm = h->dims;
   const bool gnm = a.gn != nullptr;
-  if (!fit_supported(h->d.system_id))                  // refused before anything is sized by the system's np, and before the timer starts: begin and end stay paired
-    return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
-                                     : no_such_path(h, gnm ? "myr_fit_gn" : "myr_fit_grad");
+  // refused before anything is sized by the system's np, and before the timer starts: begin and end stay paired
+  if (int rc = check_fit_has_derivatives(h, gnm ? "myr_fit_gn" : "myr_fit_grad")) return rc;
   const size_t np = (size_t)dm.np, width = gnm ? np + np * np : np;
   const bool sums = (a.grad || gnm) && !grad_stride;
   const int E = a.E, chunk = fit_sets_chunk(E, a.R, sums, width);
@@ -2468,157 +2496,120 @@ static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
     a.us = us + d0 * a.u_rows * dm.nu;
     a.params = params ? params + (size_t)e0 * dm.np : nullptr;      // (per_row: one set, e0 = 0)
     a.loss = loss ? loss + r0 : nullptr;
-    a.grad = sums ? rows : (out ? out + r0 * dm.np : nullptr);
-    if (gnm) {
-      a.gn = sums ? rows + np : out_gn + r0 * np * np;
-      a.grad_ld = (long)(sums ? width : np);
-      a.gn_ld = (long)(sums ? width : np * np);
-      rc = for_system(h->d.system_id, true, [&](auto t) { return fit_gn_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
-      if (!rc && sums) {
-        const long n = (long)a.E * (long)width;
-        hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)width * (unsigned)a.E), dim3(256), 0, h->stream, a.R, (int)width, (const double*)rows, packed);
-        hipLaunchKernelGGL(fit_gn_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, (int)np, (const double*)packed,
-                           out ? out + (size_t)e0 * np : nullptr, out_gn + (size_t)e0 * np * np);
-      }
-      continue;
+    a.grad = sums ? rows : (out ? out + r0 * np : nullptr);
+    a.gn = !gnm ? nullptr : (sums ? rows + np : out_gn + r0 * np * np);
+    a.grad_ld = (long)(sums ? width : np);               // (the two row lengths: read by the Gauss-Newton kernel only)
+    a.gn_ld = (long)(sums ? width : np * np);
+    rc = launch_fit(h, a);
+    if (!rc && sums)      // one reduction of a row's whole width; the Gauss-Newton sums come out packed ...
+      hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)width * (unsigned)a.E), dim3(256), 0, h->stream, a.R, (int)width, (const double*)rows,
+                         gnm ? packed : out + (size_t)e0 * np);
+    if (!rc && sums && gnm) {      // ... and a copy takes them apart
+      const long n = (long)a.E * (long)width;
+      hipLaunchKernelGGL(fit_gn_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, (int)np, (const double*)packed,
+                         out ? out + (size_t)e0 * np : nullptr, out_gn + (size_t)e0 * np * np);
     }
-    rc = for_system(h->d.system_id, true, [&](auto t) { return fit_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
-    if (!rc && sums)
-      hipLaunchKernelGGL(fit_reduce_sets_kernel, dim3((unsigned)dm.np * (unsigned)a.E), dim3(256), 0, h->stream, a.R, (int)dm.np, (const double*)rows,
-                         out + (size_t)e0 * dm.np);
   }
   const int rc_end = timed_end(h, MYR_K_FIT);          // on every path
   return rc ? rc : rc_end;
 }
 
+// What the four fit entry points do behind their checks: E parameter sets of R trajectories each (the single-set calls: E = 1, R = B).  params holds
+// n_par doubles -- [E][np], or for a single-set call whatever its stride says: nothing, one set, or with per_row a row per trajectory.  row_stride is
+// grad_stride / out_stride (np: a row of results per trajectory, 0: their sum per set); gn is null for myr_fit_grad*.
+static int run_fit(myr_handle h, int32_t mem, int E, int R, int data_shared, int num_steps, int u_rows, const double* xs_obs, const double* us,
+                   const double* wt, const double* params, size_t n_par, bool per_row, double* loss, double* grad, double* gn, int row_stride) {
+  HIPCHK(hipSetDevice(h->d.device));
+  const myr_dims& dm = h->dims;
+  const size_t np = (size_t)dm.np, rows = (size_t)E * R, drows = data_shared ? (size_t)R : rows, nout = row_stride ? rows : (size_t)E;
+  FitArgs a{};
+  a.E = E; a.R = R; a.data_shared = data_shared; a.num_steps = num_steps; a.u_rows = u_rows; a.per_row = per_row;
+  DevStage st = call_stage(h, mem);
+  st.in(a.xs_obs, xs_obs, drows * (num_steps + 1) * dm.ns);
+  st.in(a.us, us, drows * u_rows * dm.nu);
+  st.in(a.wt, wt, (size_t)num_steps + 1);
+  st.in(a.params, params, n_par);
+  st.out(a.loss, loss, rows);
+  st.out(a.grad, grad, nout * np);
+  st.out(a.gn, gn, nout * np * np);
+  if (int rc = st.commit()) return rc;
+  if (int rc = dispatch_fit(h, a, row_stride)) return rc;
+  return st.finish();
+}
+
+// The four entry points: each its checks, in its own order -- myr_fit_grad looks at the system before its sizes, the other three at every argument
+// first (tests/test_gpu_api.py holds the order of each, fault by fault) --, then run_fit.
 extern "C" int myr_fit_grad(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                             const double* wt, const double* params, int32_t params_stride, double* loss, double* grad,
                             int32_t grad_stride, int32_t mem) {
   const char* who = "myr_fit_grad";
-  if (!h || !xs_obs || !us || !grad) return fail(MYR_E_ARG, "myr_fit_grad: null handle, xs_obs, us or grad");
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
-  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
-  if (B < 0 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_grad: bad sizes");
+  if (!h || !xs_obs || !us || !grad) return arg_fail(who, MYR_E_ARG, "null handle, xs_obs, us or grad");
+  if (int rc = check_fit_not_plant(h, who)) return rc;
+  if (int rc = check_fit_not_twin(h)) return rc;
+  if (int rc = check_fit_sizes(who, B, 1, num_steps, u_rows)) return rc;
   if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_BATCH, "trajectory")) return rc;
   if (int rc = check_stride(h, who, params, params_stride)) return rc;
   if (int rc = check_node_weights(h, who, params)) return rc;
   if (h->d.system_id == MYR_SYS_NODE_CARTPOLE && params_stride != 0)
-    return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: a NODE system takes one shared set of weights (params_stride 0)");
+    return arg_fail(who, MYR_E_UNSUPPORTED, "a NODE system takes one shared set of weights (params_stride 0)");
   if (int rc = check_mem(who, mem)) return rc;
   if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  FitArgs a{1, B, 0, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, params && params_stride != 0, nullptr, nullptr, nullptr};      // one set
-  DevStage st = call_stage(h, mem);
-  st.in(a.xs_obs, xs_obs, (size_t)B * (num_steps + 1) * dm.ns);
-  st.in(a.us, us, (size_t)B * u_rows * dm.nu);
-  st.in(a.wt, wt, (size_t)num_steps + 1);
-  st.in(a.params, params, n_params(h, params, params_stride, B));
-  st.out(a.loss, loss, (size_t)B);
-  st.out(a.grad, grad, grad_stride ? (size_t)B * dm.np : (size_t)dm.np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_fit(h, a, grad_stride)) return rc;
-  return st.finish();
+  return run_fit(h, mem, 1, B, 0, num_steps, u_rows, xs_obs, us, wt, params, n_params(h, params, params_stride, B), params && params_stride != 0,
+                 loss, grad, nullptr, grad_stride);
 }
 
 extern "C" int myr_fit_grad_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                                  int32_t data_shared, const double* wt, const double* params, double* loss, double* grad, int32_t grad_stride,
                                  int32_t mem) {
   const char* who = "myr_fit_grad_sets";
-  if (!h || !xs_obs || !us || !params) return fail(MYR_E_ARG, "myr_fit_grad_sets: null handle, xs_obs, us or params");
-  if (!loss && !grad) return fail(MYR_E_ARG, "myr_fit_grad_sets: loss and grad are both null");
-  if (E < 0 || R < 1 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_grad_sets: bad sizes");
-  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, "a row per set: the sum over its trajectories", "trajectory")) return rc;
-  if (data_shared != 0 && data_shared != 1) return fail(MYR_E_ARG, "myr_fit_grad_sets: data_shared must be 0 (data per set) or 1 (one set of data, read by every set)");
+  if (!h || !xs_obs || !us || !params) return arg_fail(who, MYR_E_ARG, "null handle, xs_obs, us or params");
+  if (!loss && !grad) return arg_fail(who, MYR_E_ARG, "loss and grad are both null");
+  if (int rc = check_fit_sizes(who, E, R, num_steps, u_rows)) return rc;
+  if (int rc = check_row_stride(h, who, "grad_stride", grad_stride, ROW_SUM_FIT_SETS, "trajectory")) return rc;
+  if (int rc = check_data_shared(who, data_shared)) return rc;
   if (int rc = check_mem(who, mem)) return rc;
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
-  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
-  if (!fit_supported(h->d.system_id))
-    return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
-                                     : no_such_path(h, who);
+  if (int rc = check_fit_not_plant(h, who)) return rc;
+  if (int rc = check_fit_not_twin(h)) return rc;
+  if (int rc = check_fit_has_derivatives(h, who)) return rc;
   if (E == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t rows = (size_t)E * R, drows = data_shared ? (size_t)R : rows;
-  FitArgs a{E, R, data_shared, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-  DevStage st = call_stage(h, mem);
-  st.in(a.xs_obs, xs_obs, drows * (num_steps + 1) * dm.ns);
-  st.in(a.us, us, drows * u_rows * dm.nu);
-  st.in(a.wt, wt, (size_t)num_steps + 1);
-  st.in(a.params, params, (size_t)E * dm.np);
-  st.out(a.loss, loss, rows);
-  st.out(a.grad, grad, grad_stride ? rows * dm.np : (size_t)E * dm.np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_fit(h, a, grad_stride)) return rc;
-  return st.finish();
+  return run_fit(h, mem, E, R, data_shared, num_steps, u_rows, xs_obs, us, wt, params, (size_t)E * h->dims.np, false, loss, grad, nullptr, grad_stride);
 }
 
-// the refusals myr_fit_gn and myr_fit_gn_sets share, behind their argument checks: the network system, then myr_fit_grad's
+// the refusals myr_fit_gn and myr_fit_gn_sets share, behind their argument checks: the network system, then myr_fit_grad_sets's
 static int check_fit_gn_system(myr_handle h, const char* who) {
-  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
-    return arg_fail(who, MYR_E_UNSUPPORTED, "the network system's 4 804 x 4 804 Gauss-Newton matrix is not formed; use myr_fit_grad for its loss and gradient");
-  if (h->d.system_id >= 100) return fail(MYR_E_UNSUPPORTED, "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system");
-  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
-  if (!fit_supported(h->d.system_id))
-    return sys_known(h->d.system_id) ? fail(MYR_E_UNSUPPORTED, "myr_fit_grad: no parameter derivatives are generated for this system")
-                                     : no_such_path(h, who);
-  return MYR_OK;
+  if (int rc = check_fit_gn_not_node(h, who)) return rc;
+  if (int rc = check_fit_not_twin(h)) return rc;
+  if (int rc = check_fit_not_plant(h, who)) return rc;
+  return check_fit_has_derivatives(h, who);
 }
 
 extern "C" int myr_fit_gn(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                           const double* wt, const double* params, int32_t params_stride, double* loss, double* grad, double* gn,
                           int32_t out_stride, int32_t mem) {
   const char* who = "myr_fit_gn";
-  if (!h || !xs_obs || !us || !gn) return fail(MYR_E_ARG, "myr_fit_gn: null handle, xs_obs, us or gn");
-  if (B < 0 || num_steps < 1 || u_rows < 1) return fail(MYR_E_ARG, "myr_fit_gn: bad sizes");
+  if (!h || !xs_obs || !us || !gn) return arg_fail(who, MYR_E_ARG, "null handle, xs_obs, us or gn");
+  if (int rc = check_fit_sizes(who, B, 1, num_steps, u_rows)) return rc;
   if (int rc = check_row_stride(h, who, "out_stride", out_stride, ROW_SUM_BATCH, "trajectory")) return rc;
   if (int rc = check_stride(h, who, params, params_stride)) return rc;
   if (int rc = check_mem(who, mem)) return rc;
   if (int rc = check_fit_gn_system(h, who)) return rc;
   if (B == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t np = (size_t)dm.np, nout = out_stride ? (size_t)B : 1;
-  FitArgs a{1, B, 0, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, params && params_stride != 0, nullptr, nullptr, nullptr};      // one set
-  DevStage st = call_stage(h, mem);
-  st.in(a.xs_obs, xs_obs, (size_t)B * (num_steps + 1) * dm.ns);
-  st.in(a.us, us, (size_t)B * u_rows * dm.nu);
-  st.in(a.wt, wt, (size_t)num_steps + 1);
-  st.in(a.params, params, n_params(h, params, params_stride, B));
-  st.out(a.loss, loss, (size_t)B);
-  st.out(a.grad, grad, nout * np);
-  st.out(a.gn, gn, nout * np * np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_fit(h, a, out_stride)) return rc;
-  return st.finish();
+  return run_fit(h, mem, 1, B, 0, num_steps, u_rows, xs_obs, us, wt, params, n_params(h, params, params_stride, B), params && params_stride != 0,
+                 loss, grad, gn, out_stride);
 }
 
 extern "C" int myr_fit_gn_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                                int32_t data_shared, const double* wt, const double* params, double* loss, double* grad, double* gn,
                                int32_t out_stride, int32_t mem) {
   const char* who = "myr_fit_gn_sets";
-  if (!h || !xs_obs || !us || !gn || !params) return fail(MYR_E_ARG, "myr_fit_gn_sets: null handle, xs_obs, us, gn or params");
-  if (E < 0 || R < 1 || num_steps < 1 || u_rows < 1 || (long)E * R > 0x7fffffffL) return fail(MYR_E_ARG, "myr_fit_gn_sets: bad sizes");
-  if (int rc = check_row_stride(h, who, "out_stride", out_stride, "a row per set: the sum over its trajectories", "trajectory")) return rc;
-  if (data_shared != 0 && data_shared != 1) return fail(MYR_E_ARG, "myr_fit_gn_sets: data_shared must be 0 (data per set) or 1 (one set of data, read by every set)");
+  if (!h || !xs_obs || !us || !gn || !params) return arg_fail(who, MYR_E_ARG, "null handle, xs_obs, us, gn or params");
+  if (int rc = check_fit_sizes(who, E, R, num_steps, u_rows, true)) return rc;
+  if (int rc = check_row_stride(h, who, "out_stride", out_stride, ROW_SUM_FIT_SETS, "trajectory")) return rc;
+  if (int rc = check_data_shared(who, data_shared)) return rc;
   if (int rc = check_mem(who, mem)) return rc;
   if (int rc = check_fit_gn_system(h, who)) return rc;
   if (E == 0) return MYR_OK;                          // (nothing is written)
-  HIPCHK(hipSetDevice(h->d.device));
-  const myr_dims& dm = h->dims;
-  const size_t np = (size_t)dm.np, rows = (size_t)E * R, drows = data_shared ? (size_t)R : rows, nout = out_stride ? rows : (size_t)E;
-  FitArgs a{E, R, data_shared, 0, num_steps, u_rows, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
-  DevStage st = call_stage(h, mem);
-  st.in(a.xs_obs, xs_obs, drows * (num_steps + 1) * dm.ns);
-  st.in(a.us, us, drows * u_rows * dm.nu);
-  st.in(a.wt, wt, (size_t)num_steps + 1);
-  st.in(a.params, params, (size_t)E * np);
-  st.out(a.loss, loss, rows);
-  st.out(a.grad, grad, nout * np);
-  st.out(a.gn, gn, nout * np * np);
-  if (int rc = st.commit()) return rc;
-  if (int rc = dispatch_fit(h, a, out_stride)) return rc;
-  return st.finish();
+  return run_fit(h, mem, E, R, data_shared, num_steps, u_rows, xs_obs, us, wt, params, (size_t)E * h->dims.np, false, loss, grad, gn, out_stride);
 }
 
 // history of one instance of myr_exgd_grad*: x_s, x_bar_s, lam_s of every step and the final x (`per` doubles); the batch runs in chunks of the

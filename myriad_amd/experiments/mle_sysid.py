@@ -52,14 +52,37 @@ class FitLoss:
     self.engine = engine or _lib.Engine(self.system.name, "SHOOTING", 1, self.system.T, controls_per_interval=hp.num_steps,
                                         integration_method="HEUN")
 
-  def value_and_grad(self, params: Dict[str, float], dataset, epoch=0):
+  def _in_keys(self, params, sign, loss, grad=None, gn=None):
+    """(value, grad mapping, gn [K,K]) in the keys of `params`, in their order: split_params' sign rule is d|p|/dp = sign on grad and
+    sign_i sign_j on gn; the parameters that are not fitted drop out.  grad, gn: None where the call did not form them."""
+    names = self.system.param_names
+    idx = [names.index(k) for k in params]
+    g = None if grad is None else {k: float(v) for k, v in zip(params, (grad * sign)[idx])}
+    G = None if gn is None else (gn * np.outer(sign, sign))[np.ix_(idx, idx)]
+    return float(loss.sum()), g, G
+
+  def _one(self, fit, params, dataset, epoch):
+    """one mapping on one dataset through `fit` (the engine's fit_grad or fit_gn): (value, grad mapping, gn or None)"""
     ns = self.hp.state_size
     dataset = np.asarray(dataset, dtype=np.float64)
     p, sign = split_params(self.system, params)
-    out = self.engine.fit_grad(dataset[:, :, :ns], dataset[:, :, ns:], params=p, wt=loss_weights(self.hp, dataset.shape[0], epoch), reduce=True)
-    names = self.system.param_names
-    g = out["grad"] * sign
-    return float(out["loss"].sum()), {k: float(g[names.index(k)]) for k in params}
+    out = fit(dataset[:, :, :ns], dataset[:, :, ns:], params=p, wt=loss_weights(self.hp, dataset.shape[0], epoch), reduce=True)
+    return self._in_keys(params, sign, out["loss"], out["grad"], out.get("gn"))
+
+  def _sets(self, fit, params_sets, datasets, epoch, **kw):
+    """E mappings at once through `fit` (fit_grad_sets or fit_gn_sets), the sign rule per set: (values, grads, gns), E entries each (None where
+    the call did not form them)"""
+    ns = self.hp.state_size
+    datasets = np.asarray(datasets, dtype=np.float64)
+    split = [split_params(self.system, params) for params in params_sets]
+    out = fit(datasets[..., :ns], datasets[..., ns:], np.stack([p for p, _ in split]), wt=loss_weights(self.hp, datasets.shape[-3], epoch),
+              reduce=True, **kw)
+    at = lambda k, e: out[k][e] if k in out else None
+    rows = [self._in_keys(params, sign, out["loss"][e], at("grad", e), at("gn", e)) for e, (params, (_, sign)) in enumerate(zip(params_sets, split))]
+    return tuple([r[c] for r in rows] for c in range(3))
+
+  def value_and_grad(self, params: Dict[str, float], dataset, epoch=0):
+    return self._one(self.engine.fit_grad, params, dataset, epoch)[:2]
 
   def __call__(self, params, dataset, epoch=0) -> float:
     return self.value_and_grad(params, dataset, epoch)[0]
@@ -68,51 +91,19 @@ class FitLoss:
     """value_and_grad for E parameter mappings at once (one myr_fit_grad_sets call): datasets [E,M,S+1,ns+nu], or [M,S+1,ns+nu] read by every
     set.  The sign rule of split_params applies per set.  Returns (values: E floats, grads: E mappings); want_grad=False: (values, None), no
     reverse sweep.  Entry e is value_and_grad(params_sets[e], datasets[e], epoch) to the bit."""
-    ns = self.hp.state_size
-    datasets = np.asarray(datasets, dtype=np.float64)
-    split = [split_params(self.system, params) for params in params_sets]
-    out = self.engine.fit_grad_sets(datasets[..., :ns], datasets[..., ns:], np.stack([p for p, _ in split]),
-                                    wt=loss_weights(self.hp, datasets.shape[-3], epoch), reduce=True, want_grad=want_grad)
-    values = [float(row.sum()) for row in out["loss"]]
-    if not want_grad:
-      return values, None
-    names = self.system.param_names
-    grads = []
-    for params, (_, sign), row in zip(params_sets, split, out["grad"]):
-      g = row * sign
-      grads.append({k: float(g[names.index(k)]) for k in params})
-    return values, grads
-
+    values, grads, _ = self._sets(self.engine.fit_grad_sets, params_sets, datasets, epoch, want_grad=want_grad)
+    return values, (grads if want_grad else None)
 
   # ---- with the Gauss-Newton matrix (myr_fit_gn, csrc/fit_gn.h) ---------------------------------------------------------------
-  def _in_keys(self, params, sign, loss, grad, gn):
-    """(value, grad mapping, gn [K,K]) in the keys of `params`, in their order: split_params' sign rule is d|p|/dp = sign on grad and
-    sign_i sign_j on gn; the parameters that are not fitted drop out."""
-    names = self.system.param_names
-    idx = [names.index(k) for k in params]
-    g = (grad * sign)[idx]
-    G = (gn * np.outer(sign, sign))[np.ix_(idx, idx)]
-    return float(loss.sum()), {k: float(v) for k, v in zip(params, g)}, G
-
   def value_grad_gn(self, params: Dict[str, float], dataset, epoch=0):
     """(loss, its gradient as a mapping, its Gauss-Newton matrix [K,K]) in the K keys of `params`, rows and columns in their order: one
     myr_fit_gn call.  loss(params + d) ~ loss + grad . d + d . gn d / 2."""
-    ns = self.hp.state_size
-    dataset = np.asarray(dataset, dtype=np.float64)
-    p, sign = split_params(self.system, params)
-    out = self.engine.fit_gn(dataset[:, :, :ns], dataset[:, :, ns:], params=p, wt=loss_weights(self.hp, dataset.shape[0], epoch), reduce=True)
-    return self._in_keys(params, sign, out["loss"], out["grad"], out["gn"])
+    return self._one(self.engine.fit_gn, params, dataset, epoch)
 
   def values_grads_gns(self, params_sets, datasets, epoch=0):
     """value_grad_gn for E parameter mappings at once (one myr_fit_gn_sets call): datasets [E,M,S+1,ns+nu], or [M,S+1,ns+nu] read by every
     set.  Returns (values, grads, gns): E floats, E mappings, E matrices; entry e is value_grad_gn(params_sets[e], datasets[e], epoch) to the bit."""
-    ns = self.hp.state_size
-    datasets = np.asarray(datasets, dtype=np.float64)
-    split = [split_params(self.system, params) for params in params_sets]
-    out = self.engine.fit_gn_sets(datasets[..., :ns], datasets[..., ns:], np.stack([p for p, _ in split]),
-                                  wt=loss_weights(self.hp, datasets.shape[-3], epoch), reduce=True)
-    rows = [self._in_keys(params, sign, out["loss"][e], out["grad"][e], out["gn"][e]) for e, (params, (_, sign)) in enumerate(zip(params_sets, split))]
-    return [r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]
+    return self._sets(self.engine.fit_gn_sets, params_sets, datasets, epoch)
 
 
 class LevenbergMarquardt:

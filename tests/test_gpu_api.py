@@ -221,15 +221,19 @@ _ORDER.update({
   "myr_hvp_node": ("B", "z", "lam", "v", "params") + _HVP_TAIL,
   "myr_hvp_node_sets": ("E", "R", "z", "lam", "v", "params") + _HVP_TAIL,
   "myr_fit_grad_sets": ("E", "R", "num_steps", "u_rows", "xs_obs", "us", "data_shared", "wt", "params", "loss", "grad", "grad_stride", "mem"),
+  "myr_fit_gn": ("B", "num_steps", "u_rows", "xs_obs", "us", "wt", "params", "stride", "loss", "grad", "gn", "out_stride", "mem"),
+  "myr_fit_gn_sets": ("E", "R", "num_steps", "u_rows", "xs_obs", "us", "data_shared", "wt", "params", "loss", "grad", "gn", "out_stride", "mem"),
 })
 _EXGD_GRAD_EPS = ("myr_exgd_grad", "myr_exgd_grad_shoot", "myr_exgd_grad_node", "myr_exgd_grad_node_shoot", "myr_exgd_grad_node_sets")
 _HVP_EPS = ("myr_hvp", "myr_hvp_node", "myr_hvp_node_sets")
-_SETS_EPS = ("myr_exgd_grad_node_sets", "myr_hvp_node_sets", "myr_fit_grad_sets")
+_SETS_EPS = ("myr_exgd_grad_node_sets", "myr_hvp_node_sets", "myr_fit_grad_sets", "myr_fit_gn_sets")
+_FIT_EPS = ("myr_fit_grad", "myr_fit_grad_sets", "myr_fit_gn", "myr_fit_gn_sets")
 _OUTPUTS = {"myr_eval": ("f", "g", "c", "j"), "myr_vjp": ("out",), "myr_jvp": ("out",), "myr_exgd": ("z", "lam"), "myr_rollout": ("xs", "cost"),
             "myr_solve": ("z", "lam", "cost", "status", "iters", "kkt"), "myr_solve_x0": ("z", "lam", "cost", "status", "iters", "kkt"),
             "myr_fit_grad": ("loss", "grad"), "myr_fbsm": ("xs", "us", "adjs", "sweeps"), "myr_fit_grad_sets": ("loss", "grad")}
 _OUTPUTS.update({ep: ("grad", "dz0", "dlam0") for ep in _EXGD_GRAD_EPS})
 _OUTPUTS.update({ep: ("out_z", "out_p") for ep in _HVP_EPS})
+_OUTPUTS.update({"myr_fit_gn": ("loss", "grad", "gn"), "myr_fit_gn_sets": ("loss", "grad", "gn")})
 
 
 def _abi_call(ep, eng, a, handle=True):
@@ -390,6 +394,42 @@ def test_host_and_device_arrays_give_the_same_bits():
                                                wt=np.linspace(0.5, 1.5, S + 1) if with_wt else None, loss=_nan(*lead) if with_loss else None,
                                                grad=_nan(*rows) if with_grad else None, grad_stride=stride))
     eng.close()
+  # the fit family, two steps: B = 1 and 3 (E = 2 sets of R = 2), the row stride 0 and np, loss and grad present and null, data per set and shared, the
+  # three params forms of the single-set calls; closed form under RK4 (two control rows a step), the network under HEUN (the gradient calls only:
+  # myr_fit_gn* refuse it)
+  S = 2
+  cart_rk4 = lambda: _lib.Engine("CARTPOLE", "HERMITE_SIMPSON", 3, 2.0, integration_method="RK4")
+  node_heun = lambda: _lib.Engine("NODE_CARTPOLE", "HERMITE_SIMPSON", 3, 2.0, integration_method="HEUN")
+  for make, default, u_rows, eps in ((cart_rk4, np.array([9.81, 1.0, 0.3, 0.5]), 2 * S + 1, _FIT_EPS), (node_heun, None, S + 1, _FIT_EPS[:2])):
+    eng = make()
+    ns, nu, npar = eng.ns, eng.nu, eng.np
+    is_node = default is None
+    if is_node:
+      default = 0.1 * rng.standard_normal(npar)
+    for ep in eps:
+      sets, gn = ep in _SETS_EPS, "_gn" in ep
+      for lead in (((2, 2),) if sets else ((1,), (3,))):
+        B = int(np.prod(lead))
+        if sets:
+          sizes, forms = dict(E=2, R=2), [(np.stack([default * (1.0 + 0.01 * e) for e in range(2)]), None)]
+        else:
+          sizes, forms = dict(B=B), ([(default, 0)] if is_node else _params_forms(default, B))
+        for p, ps in forms:
+          for stride in (0, npar):
+            rows = (lead if stride else lead[:-1]) + (npar,)
+            for shared in ((0, 1) if sets else (None,)):
+              dlead = lead[1:] if shared else lead
+              for with_loss, with_grad in ((True, True), (False, True), (True, False), (False, False)):
+                if not with_grad and ep == "myr_fit_grad" or not (with_loss or with_grad or gn):      # (myr_fit_grad needs grad, its sets form one of the two)
+                  continue
+                a = dict(sizes, params=p, num_steps=S, u_rows=u_rows, xs_obs=0.1 * rng.standard_normal(dlead + (S + 1, ns)),
+                         us=0.2 * rng.standard_normal(dlead + (u_rows, nu)), wt=np.linspace(0.5, 1.5, S + 1) if with_loss else None,
+                         loss=_nan(*lead) if with_loss else None, grad=_nan(*rows) if with_grad else None)
+                a.update({} if sets else dict(stride=ps), **({"data_shared": shared} if sets else {}))
+                a.update(dict(gn=_nan(*rows, npar), out_stride=stride) if gn else dict(grad_stride=stride))
+                out = _same_bits(ep, eng, make, a)
+                assert all(np.isfinite(v).all() for v in out.values()), ep      # every array that was handed over has been written
+    eng.close()
 
 
 def _abi_defaults(ep, eng, B):
@@ -413,10 +453,14 @@ def _abi_defaults(ep, eng, B):
              cost=s(R), status=i32(R), iters=i32(R), kkt=s(R, 3))
   elif ep == "myr_fit_grad":
     a.update(num_steps=4, u_rows=5, xs_obs=np.zeros((R, 5, ns)), us=np.zeros((R, 5, nu)), wt=None, loss=s(R), grad=s(R, max(eng.np, 1)), grad_stride=eng.np)
+  elif ep == "myr_fit_gn":      # (the network system is refused: its gn is a token array, not 4 804 x 4 804 doubles)
+    npar = max(eng.np, 1)
+    a.update(num_steps=4, u_rows=5, xs_obs=np.zeros((R, 5, ns)), us=np.zeros((R, 5, nu)), wt=None, loss=s(R), grad=s(R, npar),
+             gn=s(R, npar, npar) if npar <= 64 else s(R, 1), out_stride=eng.np)
   elif ep == "myr_fbsm":
     a.update(N=4, x0=np.ones((R, ns)), adj_T=None, clip_lo=np.zeros(nu), clip_hi=np.ones(nu), bang=0.0, delta=1e-3, max_sweeps=5,
              xs=s(R, 5, ns), us=s(R, 5, nu), adjs=s(R, 5, ns), sweeps=i32(R))
-  elif ep in _EXGD_GRAD_EPS + _HVP_EPS + ("myr_fit_grad_sets",):      # (a sets call: B is its E, of two instances each)
+  elif ep in _EXGD_GRAD_EPS + _HVP_EPS + ("myr_fit_grad_sets", "myr_fit_gn_sets"):      # (a sets call: B is its E, of two instances each)
     sets, npar = ep in _SETS_EPS, max(eng.np, 1)
     lead = (R, 2) if sets else (R,)
     a.update(E=B, R=2)
@@ -430,6 +474,9 @@ def _abi_defaults(ep, eng, B):
     else:
       a.update(num_steps=4, u_rows=5, xs_obs=np.zeros(lead + (5, ns)), us=np.zeros(lead + (5, nu)), data_shared=0, wt=None, params=np.ones((R, npar)),
                loss=s(*lead), grad=s(*lead, npar), grad_stride=eng.np)
+      if ep == "myr_fit_gn_sets":      # (out_stride where its sibling has grad_stride; the network system's gn: as for myr_fit_gn)
+        del a["grad_stride"]
+        a.update(gn=s(*lead, npar, npar) if npar <= 64 else s(*lead, 1), out_stride=eng.np)
   return a
 
 
@@ -597,6 +644,115 @@ def _derivative_rows():
   return rows
 
 
+def _fit_rows():
+  """The rows of the fit family (myr_fit_grad, myr_fit_grad_sets, myr_fit_gn, myr_fit_gn_sets), written check by check from the entry points as
+  _derivative_rows() was (which has the first rows of myr_fit_grad_sets, as the test's own list has the first of myr_fit_grad): every refusal a
+  handle can reach, the empty calls, and two faults at once wherever two of the four look in a different order.  myr_fit_grad looks at the system
+  before its sizes, the other three at every argument first; a twin is answered in myr_fit_grad's name by all four."""
+  ARG, UNSUP = -1, -2
+  plant_text = "INVASIVEPLANT is a discrete-time system; only myr_fbsm is available for it"
+  twin = "myr_fit_grad: an elastic twin has no model of its own to fit; use the handle of its system"
+  node_gn = "the network system's 4 804 x 4 804 Gauss-Newton matrix is not formed; use myr_fit_grad for its loss and gradient"
+  node_stride = "a NODE system takes one shared set of weights (params_stride 0)"
+  row = lambda key, sets: (f"{key} must be 0 (a row per set: the sum over its trajectories) or np (a row per trajectory)" if sets else
+                           f"{key} must be 0 (one row: the sum over the batch) or np (a row per trajectory)")
+  shared_text = "data_shared must be 0 (data per set) or 1 (one set of data, read by every set)"
+  pstride_text = "params_stride must be 0 (shared) or np"
+  nulls = {"myr_fit_grad": (("xs_obs", "us", "grad"), "null handle, xs_obs, us or grad"),
+           "myr_fit_grad_sets": (("xs_obs", "us", "params"), "null handle, xs_obs, us or params"),
+           "myr_fit_gn": (("xs_obs", "us", "gn"), "null handle, xs_obs, us or gn"),
+           "myr_fit_gn_sets": (("xs_obs", "us", "gn", "params"), "null handle, xs_obs, us, gn or params")}
+  rows = []
+  def add(ep, which, B, change, code, text, null_handle=False):
+    rows.append((ep, which, B, change, null_handle, code, text if not text or text.startswith("myr_fit_grad: ") else f"{ep}: {text}"))
+  bad_pstride = lambda e: dict(params=np.ones((2, e.np)), stride=e.np + 2)
+  weights = lambda e: dict(params=np.zeros(e.np))
+  for ep in _FIT_EPS:
+    sets, gn = ep in _SETS_EPS, "_gn" in ep
+    key = "out_stride" if gn else "grad_stride"
+    off = lambda e, key=key: {key: e.np + 1}
+    batch = "E" if sets else "B"
+    names, null_text = nulls[ep]
+    # the null checks come first everywhere, whatever the handle is of
+    add(ep, "cart", 2, {}, ARG, null_text, null_handle=True)
+    add(ep, "cart", -1, {"num_steps": 0, "mem": 2}, ARG, null_text, null_handle=True)
+    for k in names:
+      add(ep, "cart", 2, {k: None}, ARG, null_text)
+      add(ep, "plant", -1, {k: None, "mem": 2}, ARG, null_text)
+      add(ep, "twin", -1, lambda e, k=k, key=key: {k: None, key: e.np + 1}, ARG, null_text)
+    # the sizes, one at a time and in front of the row stride, the params stride, data_shared and the memory kind
+    for change in ({batch: -1}, {"num_steps": 0}, {"u_rows": 0}) + (({"R": 0},) if sets else ()):
+      add(ep, "cart", 2, change, ARG, "bad sizes")
+    add(ep, "cart", -1, lambda e, key=key: {key: e.np + 1, "mem": 2, "u_rows": 0}, ARG, "bad sizes")
+    add(ep, "cart", 2, off, ARG, row(key, sets))
+    add(ep, "cart", 0, lambda e, key=key: {key: e.np + 1, "mem": 2}, ARG, row(key, sets))      # ... the row stride in front of the memory kind and the empty call
+    add(ep, "cart", 2, {"mem": 2}, ARG, "bad mem kind")
+    add(ep, "cart", 0, {"mem": 2}, ARG, "bad mem kind")      # the memory kind before the empty call returns
+    add(ep, "cart", 0, {}, 0, "")
+    add(ep, "cart", 0, {"loss": None}, 0, "")
+    if sets:
+      add(ep, "cart", 2, {"data_shared": 2}, ARG, shared_text)
+      add(ep, "cart", 0, {"data_shared": -1, "mem": 2}, ARG, shared_text)      # data_shared behind the row stride, in front of the memory kind
+      add(ep, "cart", 2, lambda e, key=key: {key: e.np + 1, "data_shared": 2}, ARG, row(key, sets))
+      add(ep, "cart", 0, {"data_shared": 1}, 0, "")
+      add(ep, "cart", 2, {"num_steps": 0, "data_shared": 2}, ARG, "bad sizes")      # the sizes in front of data_shared
+    else:
+      add(ep, "cart", 2, bad_pstride, ARG, pstride_text)
+      add(ep, "cart", 0, lambda e: dict(params=np.ones((1, e.np)), stride=e.np + 2, mem=2), ARG, pstride_text)      # the params stride in front of the memory kind
+      add(ep, "cart", 2, lambda e, key=key: dict(bad_pstride(e), **{key: e.np + 1}), ARG, row(key, sets))      # ... and behind the row stride
+      add(ep, "cart", 2, lambda e: dict(bad_pstride(e), u_rows=0), ARG, "bad sizes")      # ... and behind the sizes
+      add(ep, "cart", 0, lambda e: dict(params=np.ones(e.np)), 0, "")
+      add(ep, "cart", 0, lambda e: dict(params=np.ones((1, e.np)), stride=e.np), 0, "")
+    # the kind of system: myr_fit_grad in front of its sizes, the others behind every argument check and in front of the empty call
+    for which, text in (("plant", plant_text), ("twin", twin)):
+      add(ep, which, 2, {}, UNSUP, text)
+      add(ep, which, 0, {}, UNSUP, text)
+      first = ep == "myr_fit_grad"
+      add(ep, which, -1, {}, *((UNSUP, text) if first else (ARG, "bad sizes")))
+      add(ep, which, 2, {"num_steps": 0, "mem": 2}, *((UNSUP, text) if first else (ARG, "bad sizes")))
+      add(ep, which, 2, off, *((UNSUP, text) if first else (ARG, row(key, sets))))
+      add(ep, which, 0, {"mem": 2}, *((UNSUP, text) if first else (ARG, "bad mem kind")))
+      if sets:
+        add(ep, which, 2, {"data_shared": 2}, ARG, shared_text)
+  # myr_fit_grad on the network handle: the weights, then their stride, then the memory kind; the empty call with weights returns 0
+  ep = "myr_fit_grad"
+  add(ep, "node", 2, {"mem": 2}, ARG, "a NODE system needs its weights in `params`")
+  add(ep, "node", 2, lambda e: dict(params=np.ones((2, e.np)), stride=e.np, mem=2), UNSUP, node_stride)
+  add(ep, "node", 0, lambda e: dict(params=np.ones((1, e.np)), stride=e.np, mem=2), UNSUP, node_stride)
+  add(ep, "node", 2, lambda e: dict(params=np.ones((2, e.np)), stride=e.np + 2), ARG, pstride_text)
+  add(ep, "node", 2, lambda e: dict(weights(e), mem=2), ARG, "bad mem kind")
+  add(ep, "node", -1, {}, ARG, "bad sizes")      # (the network system is neither refused kind: the sizes come first)
+  add(ep, "node", 2, lambda e: dict(grad_stride=e.np + 1), ARG, row("grad_stride", False))
+  add(ep, "node", 0, weights, 0, "")
+  # myr_fit_grad_sets: loss and grad both null, behind the null checks and in front of the sizes; the network system is served
+  ep = "myr_fit_grad_sets"
+  add(ep, "cart", -1, {"loss": None, "grad": None, "R": 0}, ARG, "loss and grad are both null")
+  add(ep, "plant", 2, {"loss": None, "grad": None}, ARG, "loss and grad are both null")
+  add(ep, "cart", 2, {"loss": None, "grad": None, "us": None}, ARG, "null handle, xs_obs, us or params")
+  add(ep, "cart", 0, {"grad": None}, 0, "")
+  add(ep, "node", 2, {"mem": 2}, ARG, "bad mem kind")
+  add(ep, "node", 2, {"data_shared": 2}, ARG, shared_text)
+  # myr_fit_gn*: the network refusal behind the argument checks and in front of the empty call; loss and grad may both be null
+  for ep in ("myr_fit_gn", "myr_fit_gn_sets"):
+    sets = ep in _SETS_EPS
+    for B in (2, 0):
+      add(ep, "node", B, {}, UNSUP, node_gn)
+      add(ep, "node", B, {"loss": None, "grad": None}, UNSUP, node_gn)
+    add(ep, "node", 0, lambda e: dict(out_stride=e.np + 1), ARG, row("out_stride", sets))
+    add(ep, "node", 0, {"mem": 2}, ARG, "bad mem kind")
+    add(ep, "node", -1, {}, ARG, "bad sizes")
+    add(ep, "node", 2, {"gn": None}, ARG, nulls[ep][1])
+    add(ep, "cart", 0, {"loss": None, "grad": None}, 0, "")
+  add("myr_fit_gn", "node", 2, weights, UNSUP, node_gn)      # (no weights check of its own: the system is refused with its weights and, above, without)
+  add("myr_fit_gn", "node", 0, lambda e: dict(params=np.ones((1, e.np)), stride=e.np + 2), ARG, pstride_text)
+  add("myr_fit_gn_sets", "node", 2, {"data_shared": 2}, ARG, shared_text)
+  # myr_fit_gn_sets bounds E * R (an int: the lanes of one launch); no array is read.  (myr_fit_grad_sets has no such bound, and no row: it would launch.)
+  add("myr_fit_gn_sets", "cart", 2, {"E": 65536, "R": 65536}, ARG, "bad sizes")
+  add("myr_fit_gn_sets", "cart", 2, {"E": 65536, "R": 65536, "out_stride": 1, "data_shared": 2, "mem": 2}, ARG, "bad sizes")
+  add("myr_fit_gn_sets", "node", 2, {"E": 65536, "R": 65536}, ARG, "bad sizes")
+  return rows
+
+
 def test_argument_errors_keep_their_codes_and_texts():
   """(entry point, fault) -> (return code, text of myr_last_error), one call per row, as the entry points answer today -- the order of their checks included:
   myr_eval and myr_rollout return MYR_OK for an empty batch before they look at the stride, the products and myr_fit_grad look first.  No row reaches a kernel."""
@@ -658,7 +814,7 @@ def test_argument_errors_keep_their_codes_and_texts():
   for ep in ("myr_solve", "myr_solve_x0"):
     for kw in (dict(max_iter=-1), dict(tol_feas=0.0), dict(tol_stat=-1.0), dict(tol_compl=0.0), dict(mu_init=0.0)):
       rows.append((ep, "cart", 2, lambda e, kw=kw: dict(opts=_bad_opts(e, **kw)), False, ARG, f"{ep}: bad options"))
-  rows += _derivative_rows()
+  rows += _derivative_rows() + _fit_rows()
   try:
     for ep, which, B, change, null_handle, code, text in rows:
       eng = engines[which]

@@ -275,15 +275,7 @@ def test_errors():
   with pytest.raises(ValueError, match="weights"):
     eng.fit_grad(xs_obs, us)
   eng.close()
-  eng = _engine("CARTPOLE", "HEUN", 7)
-  grad = np.empty((3, 4))
-  rc = eng.lib.myr_fit_grad(eng._h, 3, 7, 8, xs_obs.ctypes.data, us.ctypes.data, None, None, 0, None, grad.ctypes.data, 3, _lib.MEM_HOST)
-  assert rc == -1 and b"grad_stride must be 0" in eng.lib.myr_last_error()
-  rc = eng.lib.myr_fit_grad(eng._h, 3, 0, 8, xs_obs.ctypes.data, us.ctypes.data, None, None, 0, None, grad.ctypes.data, 4, _lib.MEM_HOST)
-  assert rc == -1 and b"bad sizes" in eng.lib.myr_last_error()
-  rc = eng.lib.myr_fit_grad(eng._h, 3, 7, 8, xs_obs.ctypes.data, us.ctypes.data, None, None, 0, None, None, 4, _lib.MEM_HOST)
-  assert rc == -1
-  eng.close()
+  # (the argument checks of the C call, with their full texts and their order: tests/test_gpu_api.py)
 
 
 # ---- what the registers held before the launch does not reach the result --------------------------------------------------------

@@ -1,6 +1,7 @@
-"""The derivative methods of myriad_amd._lib.Engine (exgd_grad*, hvp* and their _device / _probe forms) against a recording fake of the library: which
+"""The derivative and fit methods of myriad_amd._lib.Engine (exgd_grad*, hvp*, fit_grad*, fit_gn* and their _device / _probe forms) against a recording fake of the library: which
 C function each calls, every scalar, which pointers are null, the shape of every array handed over, and the dict that comes back.  No library is
 loaded and no GPU is needed: the Engine is made without a handle, and _addr hands the arrays through instead of their addresses."""
+import re
 import types
 
 import numpy as np
@@ -24,6 +25,16 @@ ORDER = {
   "myr_hvp_node": ("B", "z", "lam", "v", "params") + _HVP_TAIL,
   "myr_hvp_node_sets": ("E", "R", "z", "lam", "v", "params") + _HVP_TAIL,
 }
+_FIT_SINGLE = ("B", "num_steps", "u_rows", "xs_obs", "us", "wt", "params", "stride", "loss", "grad")
+_FIT_SETS = ("E", "R", "num_steps", "u_rows", "xs_obs", "us", "data_shared", "wt", "params", "loss", "grad")
+ORDER.update({
+  "myr_fit_grad": _FIT_SINGLE + ("grad_stride", "mem"), "myr_fit_gn": _FIT_SINGLE + ("gn", "out_stride", "mem"),
+  "myr_fit_grad_sets": _FIT_SETS + ("grad_stride", "mem"), "myr_fit_gn_sets": _FIT_SETS + ("gn", "out_stride", "mem"),
+})
+# method -> (C function, parameter sets?, Gauss-Newton matrix?)
+FITS = {"fit_grad": ("myr_fit_grad", False, False), "fit_gn": ("myr_fit_gn", False, True),
+        "fit_grad_sets": ("myr_fit_grad_sets", True, False), "fit_gn_sets": ("myr_fit_gn_sets", True, True)}
+S, U, NP = 4, 6, 4      # steps, control rows and parameters of the fit calls
 # method -> (C function, network system?, weight sets?)
 GRADS = {"exgd_grad": ("myr_exgd_grad", False, False), "exgd_grad_shoot": ("myr_exgd_grad_shoot", False, False),
          "exgd_grad_node": ("myr_exgd_grad_node", True, False), "exgd_grad_node_shoot": ("myr_exgd_grad_node_shoot", True, False),
@@ -263,6 +274,150 @@ def test_device_forms_hand_their_arguments_through(engine):
       assert (c["with_cost"], c["p_stride"], c["mem"]) == ((0, 4804, DEVICE) if present else (1, 0, DEVICE))
       assert type(c["p_stride"]) is int
       assert c["out_z"] is (t["out_z"] if present else None) and c["out_p"] is (t["out_p"] if present else None)
+
+
+def _fit_checks(a, out, gn, stride_key, reduce, lead, want_grad=True):
+  """what the four host forms share: scalar types, the arrays made for the results and the dict that comes back"""
+  assert (a["num_steps"], a["u_rows"], a[stride_key], a["mem"]) == (S, U, 0 if reduce else NP, HOST)
+  assert all(type(a[k]) is int for k in ("num_steps", "u_rows", stride_key))
+  for k in ("xs_obs", "us"):
+    assert a[k].flags.c_contiguous and a[k].dtype == np.float64, k
+  rows = lead[:-1] if reduce else lead
+  assert a["loss"].shape == lead and _shape(a["grad"]) == (rows + (NP,) if want_grad else None)
+  assert set(out) == {"loss"} | ({"grad"} if want_grad else set()) | ({"gn"} if gn else set())
+  assert out["loss"] is a["loss"] and out.get("grad") is a["grad"]
+  if gn:
+    assert a["gn"].shape == rows + (NP, NP) and out["gn"] is a["gn"]
+
+
+@pytest.mark.parametrize("method", ["fit_grad", "fit_gn"])
+def test_fit_single_set_host_forms(engine, method):
+  fn, _, gn = FITS[method]
+  eng = engine(NP)
+  rng = np.random.default_rng(2)
+  stride_key = "out_stride" if gn else "grad_stride"
+  xs_obs, us = rng.standard_normal((B, S + 1, NS)), rng.standard_normal((B, U, NU))
+  for p, pshape, ps in ((None, None, 0), (np.ones(NP), (NP,), 0), (np.ones((B, NP)), (B, NP), NP)):
+    for wt in (None, np.linspace(0.5, 1.5, S + 1)):
+      for reduce in (False, True):
+        out = getattr(eng, method)(xs_obs, us, p, wt=wt, reduce=reduce)
+        a = _last(eng, fn)
+        assert a["B"] == B and a["stride"] == ps and _shape(a["params"]) == pshape and _shape(a["wt"]) == (None if wt is None else (S + 1,))
+        assert a["xs_obs"].shape == (B, S + 1, NS) and a["us"].shape == (B, U, NU)
+        assert np.array_equal(a["xs_obs"], xs_obs) and np.array_equal(a["us"], us)
+        _fit_checks(a, out, gn, stride_key, reduce, (B,))
+  # one trajectory [S+1,ns], [u_rows,nu] is a batch of one; either array may come alone in that form; anything array-like is taken as float64
+  for x, u in ((xs_obs[0], us[0]), (xs_obs[:1], us[0]), (xs_obs[0].astype(np.float32), us[0].tolist())):
+    for reduce in (False, True):
+      out = getattr(eng, method)(x, u, reduce=reduce)
+      a = _last(eng, fn)
+      assert a["B"] == 1 and a["xs_obs"].shape == (1, S + 1, NS) and a["us"].shape == (1, U, NU) and a["params"] is None and a["stride"] == 0
+      _fit_checks(a, out, gn, stride_key, reduce, (1,))
+
+
+@pytest.mark.parametrize("method", ["fit_grad_sets", "fit_gn_sets"])
+def test_fit_sets_host_forms(engine, method):
+  fn, _, gn = FITS[method]
+  eng = engine(NP)
+  rng = np.random.default_rng(3)
+  stride_key = "out_stride" if gn else "grad_stride"
+  params = rng.standard_normal((E, NP))
+  for shared in (False, True):
+    dlead = (R,) if shared else (E, R)
+    xs_obs, us = rng.standard_normal(dlead + (S + 1, NS)), rng.standard_normal(dlead + (U, NU))
+    for wt in (None, np.linspace(0.5, 1.5, S + 1)):
+      for reduce in (False, True):
+        for want_grad in ((True,) if gn else (True, False)):      # (fit_gn_sets always forms the gradient)
+          kw = {} if gn else dict(want_grad=want_grad)
+          out = getattr(eng, method)(xs_obs, us, params, wt=wt, reduce=reduce, **kw)
+          a = _last(eng, fn)
+          assert (a["E"], a["R"], a["data_shared"]) == (E, R, int(shared)) and type(a["data_shared"]) is int
+          assert a["params"].shape == (E, NP) and _shape(a["wt"]) == (None if wt is None else (S + 1,))
+          assert a["xs_obs"].shape == dlead + (S + 1, NS) and a["us"].shape == dlead + (U, NU)
+          _fit_checks(a, out, gn, stride_key, reduce, (E, R), want_grad)
+
+
+def test_fit_value_errors(engine):
+  eng = engine(NP)
+  m = lambda text: re.escape(text)
+  xs_obs, us = np.zeros((B, S + 1, NS)), np.zeros((B, U, NU))
+  for f in (eng.fit_grad, eng.fit_gn):
+    for bad in (np.zeros((B, S + 1, NS + 1)), np.zeros((B, 1, NS)), np.zeros((1, B, S + 1, NS))):
+      with pytest.raises(ValueError, match=m("xs_obs must be [B,S+1,4] with S >= 1")):
+        f(bad, us)
+    for bad in (np.zeros((B - 1, U, NU)), np.zeros((B, U, NU + 1)), np.zeros((1, B, U, NU))):
+      with pytest.raises(ValueError, match=m("us must be [B,u_rows,1]")):
+        f(xs_obs, bad)
+    with pytest.raises(ValueError, match="params must have np entries"):
+      f(xs_obs, us, np.ones(NP + 1))
+    with pytest.raises(ValueError, match=m("params must be [B,4]")):
+      f(xs_obs, us, np.ones((B - 1, NP)))
+    with pytest.raises(ValueError, match=m("expected shape (5,), got (4,)")):
+      f(xs_obs, us, wt=np.ones(S))
+  p = np.ones((E, NP))
+  xs4, us4, xs3, us3 = np.zeros((E, R, S + 1, NS)), np.zeros((E, R, U, NU)), np.zeros((R, S + 1, NS)), np.zeros((R, U, NU))
+  both = "xs_obs and us must both be [E,R,...] (data per set) or both [R,...] (data shared by the sets)"
+  for f in (eng.fit_grad_sets, eng.fit_gn_sets):
+    for bad in (np.ones(NP), np.ones((E, NP + 1)), np.ones((1, E, NP))):
+      with pytest.raises(ValueError, match=m("params must be [E,4]")):
+        f(xs4, us4, bad)
+    for x, u in ((xs4, us3), (xs3, us4), (xs3[0], us3[0]), (xs4[None], us4[None])):
+      with pytest.raises(ValueError, match=m(both)):
+        f(x, u, p)
+    for bad in (np.zeros((E + 1, R, S + 1, NS)), np.zeros((E, R, S + 1, NS + 1)), np.zeros((E, R, 1, NS)), np.zeros((E, 0, S + 1, NS))):
+      with pytest.raises(ValueError, match=m("xs_obs must be [E,R,S+1,4] with R >= 1, S >= 1 and E = 2 as in params")):
+        f(bad, us4, p)
+    for bad in (np.zeros((R, S + 1, NS + 1)), np.zeros((R, 1, NS)), np.zeros((0, S + 1, NS))):
+      with pytest.raises(ValueError, match=m("xs_obs must be [R,S+1,4] with R >= 1, S >= 1 and E = 2 as in params")):
+        f(bad, us3, p)
+    for bad in (np.zeros((E, R + 1, U, NU)), np.zeros((E + 1, R, U, NU)), np.zeros((E, R, U, NU + 1)), np.zeros((E, R, 0, NU))):
+      with pytest.raises(ValueError, match=m("us must be [E,R,u_rows,1]")):
+        f(xs4, bad, p)
+    for bad in (np.zeros((R + 1, U, NU)), np.zeros((R, U, NU + 1)), np.zeros((R, 0, NU))):
+      with pytest.raises(ValueError, match=m("us must be [R,u_rows,1]")):
+        f(xs3, bad, p)
+    with pytest.raises(ValueError, match=m("expected shape (5,), got (6,)")):
+      f(xs4, us4, p, wt=np.ones(S + 2))
+  assert not eng.lib.calls      # nothing reached the library
+
+
+def test_fit_device_forms_hand_their_arguments_through(engine):
+  """every array is whatever the caller gave (a device tensor), every size an int, MYR_MEM_DEVICE last; the optional arrays absent, then present"""
+  eng = engine(NP)
+  t = {k: object() for k in ("xs_obs", "us", "wt", "params", "loss", "grad", "gn")}
+  i = np.int64
+  for method, (fn, sets, gn) in FITS.items():
+    lead = (i(E), i(R)) if sets else (i(5),)
+    head = lead + (i(S), i(U), t["xs_obs"], t["us"])
+    stride_key = "out_stride" if gn else "grad_stride"
+    f = getattr(eng, method + "_device")
+    if not sets:
+      f(*head, t["gn"] if gn else t["grad"], i(NP))
+      a = _last(eng, fn)
+      f(*head, t["gn"] if gn else t["grad"], i(0), params=t["params"], params_stride=i(NP), wt=t["wt"], loss=t["loss"], **(dict(grad=t["grad"]) if gn else {}))
+      full = _last(eng, fn)
+      assert (a["stride"], full["stride"]) == (0, NP) and type(full["stride"]) is int
+      assert (a[stride_key], full[stride_key]) == (NP, 0)
+      absent = ("wt", "params", "loss") + (("grad",) if gn else ())
+    else:
+      f(*head, t["params"], *((t["gn"],) if gn else ()))
+      a = _last(eng, fn)
+      if gn:
+        f(*head, t["params"], t["gn"], out_stride=i(NP), data_shared=True, wt=t["wt"], loss=t["loss"], grad=t["grad"])
+      else:
+        f(*head, t["params"], grad=t["grad"], grad_stride=i(NP), data_shared=True, wt=t["wt"], loss=t["loss"])
+      full = _last(eng, fn)
+      assert (a["data_shared"], full["data_shared"]) == (0, 1) and type(full["data_shared"]) is int
+      assert (a[stride_key], full[stride_key]) == (0, NP)
+      absent = ("wt", "loss", "grad")
+    for c, present in ((a, False), (full, True)):
+      assert tuple(c[k] for k in (("E", "R") if sets else ("B",))) == tuple(int(v) for v in lead)
+      assert (c["num_steps"], c["u_rows"], c["mem"]) == (S, U, DEVICE)
+      assert all(type(c[k]) is int for k in (("E", "R") if sets else ("B",)) + ("num_steps", "u_rows", stride_key))
+      assert c["xs_obs"] is t["xs_obs"] and c["us"] is t["us"]
+      for k in t:
+        if k in c and k not in ("xs_obs", "us"):
+          assert c[k] is (None if k in absent and not present else t[k]), (method, k)
 
 
 def test_probes_make_the_empty_call(engine):
