@@ -100,7 +100,7 @@ def test_eval_full_size_properties():
   torch.cuda.synchronize()
   eng.eval_device(B, zt, f=f, gradf=g, c=c, jblk=j)
   assert np.array_equal(c.cpu().numpy(), host["c"]) and np.array_equal(j.cpu().numpy(), host["jblk"])
-  assert np.array_equal(f.cpu().numpy(), host["f"])
+  assert np.array_equal(f.cpu().numpy(), host["f"]) and g.cpu().numpy().tobytes() == host["gradf"].tobytes()
   # u = 0 -> objective and its gradient vanish (g = u^2)
   assert np.all(host["f"] == 0) and np.all(host["gradf"] == 0)
   # spot-check 3 instances against the oracle at full size
