@@ -32,6 +32,8 @@
  *                                                other; hp.num_experiments, seed sweeps)          myr_fit_grad_sets
  *   the Gauss-Newton matrix of that loss, 2 J^T W J (no call site in the reference: what a Levenberg-Marquardt fit and a
  *                                                parameter covariance ask for)                    myr_fit_gn, myr_fit_gn_sets
+ *   ... its product with a vector for the network system, matrix-free (no call site in the reference: the inner
+ *                                                conjugate-gradient solve of a Levenberg-Marquardt step)   myr_fit_gnvp, myr_fit_gnvp_sets
  *   many_steps_grad / the Lagrangian Hessian product of many independent networks at once (the reference's
  *                                                node_e2e_sysid.py loop trains one)               myr_exgd_grad_node_sets, myr_hvp_node_sets
  *
@@ -405,6 +407,41 @@ int myr_fit_gn(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const
 int myr_fit_gn_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
                     int32_t data_shared, const double* wt, const double* params,
                     double* loss, double* grad, double* gn, int32_t out_stride, int32_t mem);
+
+/*
+ * The Gauss-Newton product of the network fit, matrix-free (csrc/fit.h: node_fit_gnvp_kernel): what a conjugate-gradient Levenberg-Marquardt step
+ * multiplies with where myr_fit_gn's 4 804 x 4 804 matrix is not formed.  With S_b[t] = d xh_b[t] / d params [ns][np], the S of myr_fit_gn:
+ *   jv[b][t] = S_b[t] v                          [B][num_steps+1][ns], may be NULL; row t = 0 is exactly 0
+ *   out[b]   = 2 sum_t wt[t] S_b[t]^T S_b[t] v   myr_fit_gn's gn[b] times v, with the same factor 2
+ * by a forward tangent rollout and myr_fit_grad's reverse sweep with 2 wt[t] jv[b][t] in the place of the residual's cotangent.
+ *   xs_obs, us, wt: as in myr_fit_grad; xs_obs supplies only the start states xs_obs[b][0] (the product does not depend on the residuals: the
+ *   argument stays so that the call takes the arrays of the fit calls unchanged);
+ *   params [np], v [np]: both required;
+ *   out_stride == np: out [B][np]; out_stride == 0: out [np], the sum over the batch in myr_fit_grad's fixed order, without atomics;
+ *   out may be NULL: only the forward tangent runs.  jv and out must not both be NULL.
+ * Contract: the same bits for MYR_MEM_HOST and MYR_MEM_DEVICE, on every call, whatever ran on the handle before, with jv NULL or not; row b of a
+ * batched call has the bits of the call on trajectory b alone.  Timed on MYR_K_FIT.  Detected by the export: myr_version() is unchanged.
+ * Errors, in this order: MYR_E_ARG -- a null h, xs_obs, us, params or v; jv and out both NULL; B < 0, num_steps < 1, u_rows < 1; an out_stride
+ * other than 0 and np; a bad mem.  MYR_E_UNSUPPORTED -- every handle that is not the network system (use myr_fit_gn, which forms gn, and
+ * multiply).  B == 0 writes nothing and returns MYR_OK.
+ */
+int myr_fit_gnvp(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                 const double* wt, const double* params, const double* v, double* jv, double* out, int32_t out_stride, int32_t mem);
+
+/*
+ * myr_fit_gnvp for E independent weight sets of R trajectories each, in one call: the lockstep conjugate-gradient iterations of an ensemble.
+ *   data as in myr_fit_grad_sets (data_shared 0 / 1); params [E][np] and v [E][np] (one direction per set), both required;
+ *   jv [E][R][num_steps+1][ns] or NULL; out [E][R][np] if out_stride == np, [E][np] -- per set, the fixed-order sum over its R rows -- if
+ *   out_stride == 0, or NULL.
+ * Contract: set e has the bits of myr_fit_gnvp on that set alone.  When the rows behind the per-set sums (E * R * np doubles of scratch) would
+ * pass 1 GiB the call runs in chunks of whole sets with the same bits; MYRIAD_FIT_ROWS_BYTES lowers that bound (tests).
+ * Errors, in this order: MYR_E_ARG -- a null h, xs_obs, us, params or v; jv and out both NULL; E < 0, R < 1, num_steps < 1, u_rows < 1, E * R
+ * not an int; an out_stride other than 0 and np; a data_shared other than 0 and 1; a bad mem.  MYR_E_UNSUPPORTED as myr_fit_gnvp.  E == 0
+ * writes nothing and returns MYR_OK.
+ */
+int myr_fit_gnvp_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                      int32_t data_shared, const double* wt, const double* params, const double* v,
+                      double* jv, double* out, int32_t out_stride, int32_t mem);
 
 /*
  * Derivative of `nsteps` extragradient steps (myr_exgd) in the model parameters, by one reverse sweep through the steps on the device

@@ -73,6 +73,8 @@ _SIGNATURES = {
   "myr_fit_grad_sets": ([_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _i], C.c_int),
   "myr_fit_gn": ([_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i], C.c_int),
   "myr_fit_gn_sets": ([_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i], C.c_int),
+  "myr_fit_gnvp": ([_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i], C.c_int),
+  "myr_fit_gnvp_sets": ([_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i], C.c_int),
   "myr_set_var_scale": ([_p, _p], C.c_int),
   "myr_vjp": ([_p, _i, _p, _p, _p, _i, _p, _i, _i], C.c_int),
   "myr_jvp": ([_p, _i, _p, _p, _p, _i, _p, _i], C.c_int),
@@ -331,10 +333,9 @@ class Engine:
     _chk(getattr(self.lib, call)(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
                                  _addr(params), *map(_addr, outs), int(row_stride), mem), call)
 
-  def _fit(self, call, with_gn, xs_obs, us, params, wt, reduce):
-    """fit_grad and fit_gn: the shape rules they share, the result arrays and the call"""
-    xs_obs = _f64(xs_obs)
-    us = _f64(us)
+  def _fit_data(self, xs_obs, us):
+    """the data of a single-set fit call: (xs_obs [B,S+1,ns], us [B,u_rows,nu], B, S); one trajectory may come without its batch axis"""
+    xs_obs, us = _f64(xs_obs), _f64(us)
     if xs_obs.ndim == 2:
       xs_obs = xs_obs[None]
     if us.ndim == 2:
@@ -344,16 +345,10 @@ class Engine:
       raise ValueError(f"xs_obs must be [B,S+1,{self.ns}] with S >= 1")
     if us.ndim != 3 or us.shape[0] != B or us.shape[2] != self.nu:
       raise ValueError(f"us must be [B,u_rows,{self.nu}]")
-    p, ps = self._params(params, B)
-    w = None if wt is None else _f64(wt, (S + 1,))
-    lead = () if reduce else (B,)
-    loss, grad = np.empty(B), np.empty(lead + (self.np,))
-    gn = np.empty(lead + (self.np, self.np)) if with_gn else None
-    self._fit_call(call, MEM_HOST, B, S, us.shape[1], xs_obs, us, w, p, ps, (loss, grad, gn)[:3 if with_gn else 2], 0 if reduce else self.np)
-    return self._present(loss=loss, grad=grad, gn=gn)
+    return xs_obs, us, B, S
 
-  def _fit_sets(self, call, with_gn, xs_obs, us, params, wt, reduce, want_grad):
-    """fit_grad_sets and fit_gn_sets: the same for E parameter sets"""
+  def _fit_sets_data(self, xs_obs, us, params):
+    """... and of a sets call: (xs_obs, us, params [E,np], E, R, S, shared) -- the data [E,R,...], or [R,...] read by every set"""
     xs_obs, us, params = _f64(xs_obs), _f64(us), _f64(params)
     if params.ndim != 2 or params.shape[1] != self.np:
       raise ValueError(f"params must be [E,{self.np}]")
@@ -367,6 +362,22 @@ class Engine:
       raise ValueError(f"xs_obs must be [{'' if shared else 'E,'}R,S+1,{self.ns}] with R >= 1, S >= 1 and E = {E} as in params")
     if us.shape[:-2] != lead + (R,) or us.shape[-1] != self.nu or us.shape[-2] < 1:
       raise ValueError(f"us must be [{'' if shared else 'E,'}R,u_rows,{self.nu}]")
+    return xs_obs, us, params, E, R, S, shared
+
+  def _fit(self, call, with_gn, xs_obs, us, params, wt, reduce):
+    """fit_grad and fit_gn: the shape rules they share, the result arrays and the call"""
+    xs_obs, us, B, S = self._fit_data(xs_obs, us)
+    p, ps = self._params(params, B)
+    w = None if wt is None else _f64(wt, (S + 1,))
+    lead = () if reduce else (B,)
+    loss, grad = np.empty(B), np.empty(lead + (self.np,))
+    gn = np.empty(lead + (self.np, self.np)) if with_gn else None
+    self._fit_call(call, MEM_HOST, B, S, us.shape[1], xs_obs, us, w, p, ps, (loss, grad, gn)[:3 if with_gn else 2], 0 if reduce else self.np)
+    return self._present(loss=loss, grad=grad, gn=gn)
+
+  def _fit_sets(self, call, with_gn, xs_obs, us, params, wt, reduce, want_grad):
+    """fit_grad_sets and fit_gn_sets: the same for E parameter sets"""
+    xs_obs, us, params, E, R, S, shared = self._fit_sets_data(xs_obs, us, params)
     w = None if wt is None else _f64(wt, (S + 1,))
     out = (E,) if reduce else (E, R)
     loss = np.empty((E, R))
@@ -416,6 +427,44 @@ class Engine:
   def fit_gn_sets_device(self, E, R, num_steps, u_rows, xs_obs, us, params, gn, out_stride=0, data_shared=False, wt=None, loss=None, grad=None):
     """Zero-copy variant of fit_gn_sets: every array is a device tensor on this handle's device (loss, grad may be None)."""
     self._fit_sets_call("myr_fit_gn_sets", MEM_DEVICE, E, R, num_steps, u_rows, xs_obs, us, data_shared, wt, params, (loss, grad, gn), out_stride)
+
+  # ---- the Gauss-Newton product of the network fit: myr_fit_gnvp and its _sets form ------------------------------------------------
+  def fit_gnvp(self, xs_obs, us, params, v, wt=None, reduce=False, want_jv=False, want_out=True):
+    """myr_fit_gnvp: the Gauss-Newton matrix of the network fit times a direction, without the matrix.  xs_obs [B,S+1,ns] (only the start states
+    xs_obs[:,0] are read), us [B,u_rows,nu], params [np], v [np], wt [S+1] (None: 1).  Returns {"out" [B,np] = fit_gn's gn[b] @ v, or [np] = the
+    sum over the batch with reduce=True}; want_jv=True adds "jv" [B,S+1,ns], the tangent of the rolled-out states along v; want_out=False: the
+    forward tangent only (no "out")."""
+    xs_obs, us, B, S = self._fit_data(xs_obs, us)
+    params, v = _f64(params, (self.np,)), _f64(v, (self.np,))
+    w = None if wt is None else _f64(wt, (S + 1,))
+    jv = np.empty((B, S + 1, self.ns)) if want_jv else None
+    out = np.empty((() if reduce else (B,)) + (self.np,)) if want_out else None
+    self.fit_gnvp_device(B, S, us.shape[1], xs_obs, us, params, v, jv=jv, out=out, out_stride=0 if reduce else self.np, wt=w, mem=MEM_HOST)
+    return self._present(out=out, jv=jv)
+
+  def fit_gnvp_device(self, B, num_steps, u_rows, xs_obs, us, params, v, jv=None, out=None, out_stride=0, wt=None, mem=MEM_DEVICE):
+    """Zero-copy variant of fit_gnvp: every array is a device tensor on this handle's device (jv or out may be None, not both)."""
+    _chk(self.lib.myr_fit_gnvp(self._h, int(B), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), _addr(wt), _addr(params), _addr(v), _addr(jv),
+                               _addr(out), int(out_stride), mem), "myr_fit_gnvp")
+
+  def fit_gnvp_sets(self, xs_obs, us, params, v, wt=None, reduce=False, want_jv=False, want_out=True):
+    """myr_fit_gnvp_sets: fit_gnvp for E weight sets of R trajectories each in one call.  params [E,np], v [E,np] (a direction per set); xs_obs, us
+    as in fit_grad_sets ([E,R,...], or [R,...] read by every set).  Returns {"out" [E,R,np], or [E,np] with reduce=True; "jv" [E,R,S+1,ns] with
+    want_jv=True}.  Set e has the bits of fit_gnvp on that set alone."""
+    xs_obs, us, params, E, R, S, shared = self._fit_sets_data(xs_obs, us, params)
+    v = _f64(v, (E, self.np))
+    w = None if wt is None else _f64(wt, (S + 1,))
+    jv = np.empty((E, R, S + 1, self.ns)) if want_jv else None
+    out = np.empty(((E,) if reduce else (E, R)) + (self.np,)) if want_out else None
+    self.fit_gnvp_sets_device(E, R, S, us.shape[-2], xs_obs, us, params, v, jv=jv, out=out, out_stride=0 if reduce else self.np, data_shared=shared,
+                              wt=w, mem=MEM_HOST)
+    return self._present(out=out, jv=jv)
+
+  def fit_gnvp_sets_device(self, E, R, num_steps, u_rows, xs_obs, us, params, v, jv=None, out=None, out_stride=0, data_shared=False, wt=None,
+                           mem=MEM_DEVICE):
+    """Zero-copy variant of fit_gnvp_sets: every array is a device tensor on this handle's device (jv or out may be None, not both)."""
+    _chk(self.lib.myr_fit_gnvp_sets(self._h, int(E), int(R), int(num_steps), int(u_rows), _addr(xs_obs), _addr(us), int(data_shared), _addr(wt),
+                                    _addr(params), _addr(v), _addr(jv), _addr(out), int(out_stride), mem), "myr_fit_gnvp_sets")
 
   # ---- Lagrangian products / extragradient (collocation transcriptions) ------------------------
   def _batch2(self, a, width, name):

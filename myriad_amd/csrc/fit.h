@@ -246,6 +246,43 @@ struct NodeFit {
     for (int r = 0; r < NS; ++r) f[r] = wl[NM::L_B3 + r] + wsum(h2 * wl[NM::L_W3 + lane * NS + r]);
   }
 
+  // this lane's share of a direction v in the weights (node_fit_gnvp_kernel): column `lane` of V1 and V2, row `lane` of V3, entry `lane` of vb1 and
+  // vb2, and vb3 -- Acc's shape, read instead of accumulated.  Registers for the whole forward pass, as Acc is for the reverse sweep
+  struct Dir {
+    double w1[NW], b1, w2[H], b2, w3[NS], b3[NS];
+    __device__ inline void load(const double* v, int lane) {      // v [NP] in the parameter order of node_system.h
+#pragma unroll
+      for (int c = 0; c < NW; ++c) w1[c] = v[Sys::O_W1 + c * H + lane];
+      b1 = v[Sys::O_B1 + lane];
+#pragma unroll
+      for (int k = 0; k < H; ++k) w2[k] = v[Sys::O_W2 + k * H + lane];
+      b2 = v[Sys::O_B2 + lane];
+#pragma unroll
+      for (int r = 0; r < NS; ++r) { w3[r] = v[Sys::O_W3 + lane * NS + r]; b3[r] = v[Sys::O_B3 + r]; }
+    }
+  };
+
+  // tangent of fwd at the point w = [x; u] with activations (h1, h2): input tangent [dx; 0], weight tangent d.  df[NS] = (df/dx) dx + (df/dp) v, the
+  // same bits in every lane
+  __device__ static inline void tan(const double* wl, int lane, const Dir& d, const double* w, const double* dx, double h1, double h2, double* df) {
+    double a = d.b1;
+#pragma unroll
+    for (int c = 0; c < NS; ++c) a += dx[c] * wl[NM::L_W1 + c * H + lane];
+#pragma unroll
+    for (int c = 0; c < NW; ++c) a += w[c] * d.w1[c];
+    const double t1 = h1 * (1.0 - h1) * a;
+    a = d.b2;
+#pragma unroll
+    for (int i = 0; i < H; ++i) {                                // (unrolled: the direction is registers)
+      a += bcast(t1, i) * wl[NM::L_W2 + i * NM::LD2 + lane];
+      a += bcast(h1, i) * d.w2[i];
+      if ((i & 7) == 7) __builtin_amdgcn_sched_barrier(0);       // (as in bwd: eight pairs of broadcasts in flight)
+    }
+    const double t2 = h2 * (1.0 - h2) * a;
+#pragma unroll
+    for (int r = 0; r < NS; ++r) df[r] = d.b3[r] + wsum(t2 * wl[NM::L_W3 + lane * NS + r] + h2 * d.w3[r]);
+  }
+
   struct Acc {                // this lane's share of the weight gradient
     double w1[NW], b1, w2[H], b2, w3[NS], b3[NS];
   };
@@ -401,6 +438,136 @@ void node_fit_kernel(int R, int data_shared, long Bp, int method, int num_steps,
   }
   if (loss) loss[b] = l;
   double* gr = grad + b * (long)F::NP;                           // the parameter order of node_system.h
+  using S_ = typename F::Sys;
+#pragma unroll
+  for (int c = 0; c < NW; ++c) gr[S_::O_W1 + c * H + lane] = g.w1[c];
+  gr[S_::O_B1 + lane] = g.b1;
+#pragma unroll
+  for (int k = 0; k < H; ++k) gr[S_::O_W2 + k * H + lane] = g.w2[k];
+  gr[S_::O_B2 + lane] = g.b2;
+#pragma unroll
+  for (int r = 0; r < NS; ++r) { gr[S_::O_W3 + lane * NS + r] = g.w3[r]; gr[S_::O_B3 + r] = g.b3[r]; }
+}
+
+// Gauss-Newton product of the network fit (myr_fit_gnvp*; K9v in DESIGN.md): with S_b[t] = d xh_b[t] / d params, jv[b][t] = S_b[t] v and
+// out[b] = 2 sum_t wt[t] S_b[t]^T S_b[t] v -- myr_fit_gn's gn[b] times v, without the 4 804 x 4 804 matrix.  node_fit_kernel's mapping (grid, sets,
+// rows, LDS weights, one wavefront per trajectory, lane j = hidden unit j; every branch wave-uniform).  The forward pass carries the tangent dx = S v
+// beside the state through the same stage table (F::tan; this lane's share of v sits in registers, F::Dir), keeps xh AND dx per step in column-major
+// scratch (xh, dxh: [num_steps+1][NS][Bp] each) and writes dx to jv [E][R][num_steps+1][NS] when asked.  The reverse sweep is node_fit_kernel's with the
+// cotangent source 2 wt[s] dx[s] where that one has 2 wt[s] (xh[s] - xs_obs[s]): a copy, not a shared function -- node_fit_kernel's instruction
+// sequence is sensitive to how its body is cut up (see plan).  v: [E][NP], a direction per set.  out: [E][R][NP] rows, or null: the wavefront stops
+// behind the forward pass.  xs_obs gives the start state only.
+template <class F>
+__global__ __launch_bounds__(64 * F::WPB)
+void node_fit_gnvp_kernel(int R, int data_shared, long Bp, int method, int num_steps, double h, int u_rows, const double* __restrict__ xs_obs,
+                          const double* __restrict__ us, const double* __restrict__ wt, const double* __restrict__ params,
+                          const double* __restrict__ vdir, double* __restrict__ xh, double* __restrict__ dxh, double* __restrict__ jv,
+                          double* __restrict__ out) {
+  constexpr int NS = F::NS, NW = F::NW, H = F::H;
+  __shared__ double wl[NodeMfma64::L_N];
+  const int gps = (R + F::WPB - 1) / F::WPB;                     // workgroups per set
+  const int e = (int)(blockIdx.x / (unsigned)gps);
+  NodeMfma64::load_weights(params + (long)e * F::NP, wl, threadIdx.x, 64 * F::WPB);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int r = (int)(blockIdx.x - (unsigned)e * (unsigned)gps) * F::WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (r >= R) return;                                            // a whole wavefront, behind the only barrier
+  const long b = (long)e * R + r;
+  const long d = data_shared ? (long)r : b;
+  const double* xo = xs_obs + d * (long)(num_steps + 1) * NS;
+  const double* ub = us + d * (long)u_rows;
+  double* xc = xh + b;
+  double* dc = dxh + b;
+  double* jb = jv ? jv + b * (long)(num_steps + 1) * NS : nullptr;
+  __shared__ double stg[F::WPB][4][8 + 2 * H];                   // (node_fit_kernel: per wavefront and stage, no barrier)
+  double (*st)[8 + 2 * H] = stg[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+  double x[NS], dx[NS], w[NW], f[NS], uc[4], av[4], bv[4];
+  {
+    typename F::Dir dir;                                         // live in the forward pass only
+    dir.load(vdir + (long)e * F::NP, lane);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {                               // (wave-uniform values: every lane stores)
+      x[i] = xo[i]; dx[i] = 0.0;
+      xc[(long)i * Bp] = x[i]; dc[(long)i * Bp] = 0.0;
+      if (jb) jb[i] = 0.0;
+    }
+    for (int s = 0; s < num_steps; ++s) {
+      const int nst = F::plan(method, s, u_rows, ub, uc, av, bv);
+      double ks[NS], dks[NS], dw[NS], df[NS];                    // ks, dks: sum_j bw[j] f(X[j]) and its tangent, in node_fit_kernel's arithmetic
+#pragma unroll
+      for (int i = 0; i < NS; ++i) { w[i] = x[i]; dw[i] = dx[i]; ks[i] = 0.0; dks[i] = 0.0; }
+#pragma unroll 1
+      for (int j = 0; j < nst; ++j) {
+        double h1, h2;
+        w[NS] = uc[j];
+        F::fwd(wl, lane, w, h1, h2, f);
+        F::tan(wl, lane, dir, w, dw, h1, h2, df);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+          ks[i] = j == 0 ? f[i] : (method == 2 ? f[i] : (method == 1 || j == 3 ? ks[i] + f[i] : ks[i] + 2.0 * f[i]));
+          dks[i] = j == 0 ? df[i] : (method == 2 ? df[i] : (method == 1 || j == 3 ? dks[i] + df[i] : dks[i] + 2.0 * df[i]));
+          w[i] = x[i] + av[j] * h * f[i];
+          dw[i] = dx[i] + av[j] * h * df[i];
+        }
+      }
+      const double hs = method == 1 ? 0.5 * h : (method == 3 ? h / 6.0 : h);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        x[i] += hs * ks[i];
+        dx[i] += hs * dks[i];
+        xc[((long)(s + 1) * NS + i) * Bp] = x[i];
+        dc[((long)(s + 1) * NS + i) * Bp] = dx[i];
+        if (jb) jb[(long)(s + 1) * NS + i] = dx[i];
+      }
+    }
+  }
+  if (!out) return;                                              // (a kernel argument: the same for every wavefront)
+  typename F::Acc g;
+#pragma unroll
+  for (int c = 0; c < NW; ++c) g.w1[c] = 0.0;
+#pragma unroll
+  for (int k = 0; k < H; ++k) g.w2[k] = 0.0;
+#pragma unroll
+  for (int r = 0; r < NS; ++r) { g.w3[r] = 0.0; g.b3[r] = 0.0; }
+  g.b1 = 0.0; g.b2 = 0.0;
+  double lam[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) lam[i] = 2.0 * (wt ? wt[num_steps] : 1.0) * dx[i];
+  for (int s = num_steps - 1; s >= 0; --s) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) { x[i] = xc[((long)s * NS + i) * Bp]; dx[i] = dc[((long)s * NS + i) * Bp]; w[i] = x[i]; }
+    const int nst = F::plan(method, s, u_rows, ub, uc, av, bv);
+#pragma unroll 1
+    for (int j = 0; j < nst; ++j) {                              // the stage points and their activations, forward
+      double h1, h2;
+      w[NS] = uc[j];
+      F::fwd(wl, lane, w, h1, h2, f);
+#pragma unroll
+      for (int c = 0; c < NW; ++c) st[j][c] = w[c];
+      st[j][8 + lane] = h1;
+      st[j][8 + H + lane] = h2;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) w[i] = x[i] + av[j] * h * f[i];
+    }
+    double wx[NS], acc[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) { wx[i] = 0.0; acc[i] = 0.0; }
+#pragma unroll 1
+    for (int j = nst - 1; j >= 0; --j) {                         // the stage cotangents, backward
+      double v[NS];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) v[i] = bv[j] * h * lam[i] + av[j] * h * wx[i];
+#pragma unroll
+      for (int c = 0; c < NW; ++c) w[c] = st[j][c];
+      F::bwd(wl, lane, w, st[j][8 + lane], st[j][8 + H + lane], v, g, wx);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) acc[i] += wx[i];
+    }
+    const double ws = wt ? wt[s] : 1.0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) lam[i] += acc[i] + 2.0 * ws * dx[i];
+  }
+  double* gr = out + b * (long)F::NP;                            // the parameter order of node_system.h
   using S_ = typename F::Sys;
 #pragma unroll
   for (int c = 0; c < NW; ++c) gr[S_::O_W1 + c * H + lane] = g.w1[c];

@@ -333,7 +333,11 @@ struct FitArgs {      // E parameter sets of R trajectories each (myr_fit_grad: 
   // myr_fit_gn*: gn non-null -- [E][R][NP][NP], the Gauss-Newton matrices; fit_gn_lane_kernel runs, without xh.  grad_ld, gn_ld: doubles from one
   // trajectory's row to the next (dispatch_fit sets them)
   double* gn; long grad_ld, gn_ld;
+  // myr_fit_gnvp* (mode FIT_GNVP; the network system only): v [E][NP], a direction per set; jv [E][R][num_steps+1][NS] or null; grad is the product --
+  // rows, sums or null (the forward tangent only); dxh: the tangent's scratch, of xh's shape (dispatch_fit sets it); loss stays null
+  int mode; const double* v; double *jv, *dxh;
 };
+enum { FIT_GRAD = 0, FIT_GN = 1, FIT_GNVP = 2 };
 struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of one chunk of `chunk` instances; seed_lam, dz0, dlam0 may be null
   int B; const double *z, *lam, *lb, *ub, *params; int pstride; double eta_x, eta_v; int nsteps; const double *seed_z, *seed_lam;
   double *rows, *dz0, *dlam0, *hist; int chunk;
@@ -1153,8 +1157,13 @@ template <class Sys>
 int fit_for_system(myr_handle h, const FitArgs& a) {
   if constexpr (std::is_same<Sys, SysNODE_CARTPOLE>::value) {      // a set of weights per workgroup (never per trajectory: myr_fit_grad has checked), one wavefront per trajectory
     const unsigned per_set = (unsigned)((a.R + NodeFit::WPB - 1) / NodeFit::WPB);
-    hipLaunchKernelGGL(node_fit_kernel<NodeFit>, dim3((unsigned)a.E * per_set), dim3(64 * NodeFit::WPB), 0, h->stream, a.R, a.data_shared, a.Bp,
-                       (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.xh, a.loss, a.grad);
+    if (a.mode == FIT_GNVP)
+      hipLaunchKernelGGL(node_fit_gnvp_kernel<NodeFit>, dim3((unsigned)a.E * per_set), dim3(64 * NodeFit::WPB), 0, h->stream, a.R, a.data_shared, a.Bp,
+                         (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.v, a.xh, a.dxh, a.jv,
+                         a.grad);
+    else
+      hipLaunchKernelGGL(node_fit_kernel<NodeFit>, dim3((unsigned)a.E * per_set), dim3(64 * NodeFit::WPB), 0, h->stream, a.R, a.data_shared, a.Bp,
+                         (int)h->d.integration_method, a.num_steps, h->d.T / a.num_steps, a.u_rows, a.xs_obs, a.us, a.wt, a.params, a.xh, a.loss, a.grad);
     return MYR_OK;
   } else if constexpr (!SysDp<Sys>::SUPPORTED) {
     return fit_no_derivatives();
@@ -2466,24 +2475,27 @@ static __global__ __launch_bounds__(256) void fit_gn_unpack_kernel(long n, int n
 // With a.gn (myr_fit_gn*) the forward-sensitivity kernel runs instead: no state scratch; a.gn is [E][R][np][np] beside a.grad (which may then be null
 // with either stride), or -- grad_stride == 0 -- [E][np][np] beside [E][np]: the lanes write packed rows [np + np^2], grad then gn, ONE reduction of
 // that width sums them per set in the same fixed order, and a copy takes the sums apart into the two arrays.
-static int launch_fit(myr_handle h, const FitArgs& a) {      // the kernel by a.gn
-  return for_system(h->d.system_id, true, [&](auto t) { return a.gn ? fit_gn_for_system<SYS_OF(t)>(h, a) : fit_for_system<SYS_OF(t)>(h, a); },
+// With FIT_GNVP (myr_fit_gnvp*) a.grad is the product, with the strides and the reduction of the gradient; a second scratch of xh's shape (a.dxh) holds
+// the tangent, and a.v, a.jv advance with the sets of a chunk.
+static int launch_fit(myr_handle h, const FitArgs& a) {      // the kernel by a.mode
+  return for_system(h->d.system_id, true, [&](auto t) { return a.mode == FIT_GN ? fit_gn_for_system<SYS_OF(t)>(h, a) : fit_for_system<SYS_OF(t)>(h, a); },
                     [] { return (int)MYR_OK; });
 }
 static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
   const myr_dims& dm = h->dims;
-  const bool gnm = a.gn != nullptr;
+  const bool gnm = a.mode == FIT_GN, gnvp = a.mode == FIT_GNVP;
   // refused before anything is sized by the system's np, and before the timer starts: begin and end stay paired
   if (int rc = check_fit_has_derivatives(h, gnm ? "myr_fit_gn" : "myr_fit_grad")) return rc;
   const size_t np = (size_t)dm.np, width = gnm ? np + np * np : np;
   const bool sums = (a.grad || gnm) && !grad_stride;
   const int E = a.E, chunk = fit_sets_chunk(E, a.R, sums, width);
   const size_t S1 = (size_t)a.num_steps + 1;
-  const double *xs_obs = a.xs_obs, *us = a.us, *params = a.params;
-  double *const loss = a.loss, *const out = a.grad, *const out_gn = a.gn, *rows = nullptr, *packed = nullptr;
+  const double *xs_obs = a.xs_obs, *us = a.us, *params = a.params, *v = a.v;
+  double *const loss = a.loss, *const out = a.grad, *const out_gn = a.gn, *const jv = a.jv, *rows = nullptr, *packed = nullptr;
   a.Bp = padded_lanes((int)((long)chunk * a.R));
   DevStage st = scratch_stage(h, &h->sbuf, &h->sbuf_bytes);
   if (!gnm) st.scratch(a.xh, S1 * dm.ns * (size_t)a.Bp);
+  if (gnvp) st.scratch(a.dxh, S1 * dm.ns * (size_t)a.Bp);
   if (sums) st.scratch(rows, (size_t)chunk * a.R * width);
   if (sums && gnm) st.scratch(packed, (size_t)chunk * width);
   if (int rc = st.commit()) return rc;
@@ -2496,6 +2508,8 @@ static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
     a.us = us + d0 * a.u_rows * dm.nu;
     a.params = params ? params + (size_t)e0 * dm.np : nullptr;      // (per_row: one set, e0 = 0)
     a.loss = loss ? loss + r0 : nullptr;
+    a.v = v ? v + (size_t)e0 * dm.np : nullptr;
+    a.jv = jv ? jv + r0 * S1 * dm.ns : nullptr;
     a.grad = sums ? rows : (out ? out + r0 * np : nullptr);
     a.gn = !gnm ? nullptr : (sums ? rows + np : out_gn + r0 * np * np);
     a.grad_ld = (long)(sums ? width : np);               // (the two row lengths: read by the Gauss-Newton kernel only)
@@ -2517,21 +2531,26 @@ static int dispatch_fit(myr_handle h, FitArgs a, int grad_stride) {
 // What the four fit entry points do behind their checks: E parameter sets of R trajectories each (the single-set calls: E = 1, R = B).  params holds
 // n_par doubles -- [E][np], or for a single-set call whatever its stride says: nothing, one set, or with per_row a row per trajectory.  row_stride is
 // grad_stride / out_stride (np: a row of results per trajectory, 0: their sum per set); gn is null for myr_fit_grad*.
+// myr_fit_gnvp*: v ([E][np], non-null: the mode) and jv ([E][R][num_steps+1][ns] or null) beside them; grad is then the product and may be null.
 static int run_fit(myr_handle h, int32_t mem, int E, int R, int data_shared, int num_steps, int u_rows, const double* xs_obs, const double* us,
-                   const double* wt, const double* params, size_t n_par, bool per_row, double* loss, double* grad, double* gn, int row_stride) {
+                   const double* wt, const double* params, size_t n_par, bool per_row, double* loss, double* grad, double* gn, int row_stride,
+                   const double* v = nullptr, double* jv = nullptr) {
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
   const size_t np = (size_t)dm.np, rows = (size_t)E * R, drows = data_shared ? (size_t)R : rows, nout = row_stride ? rows : (size_t)E;
   FitArgs a{};
   a.E = E; a.R = R; a.data_shared = data_shared; a.num_steps = num_steps; a.u_rows = u_rows; a.per_row = per_row;
+  a.mode = v ? FIT_GNVP : (gn ? FIT_GN : FIT_GRAD);
   DevStage st = call_stage(h, mem);
   st.in(a.xs_obs, xs_obs, drows * (num_steps + 1) * dm.ns);
   st.in(a.us, us, drows * u_rows * dm.nu);
   st.in(a.wt, wt, (size_t)num_steps + 1);
   st.in(a.params, params, n_par);
+  st.in(a.v, v, (size_t)E * np);
   st.out(a.loss, loss, rows);
   st.out(a.grad, grad, nout * np);
   st.out(a.gn, gn, nout * np * np);
+  st.out(a.jv, jv, rows * (num_steps + 1) * dm.ns);
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_fit(h, a, row_stride)) return rc;
   return st.finish();
@@ -2610,6 +2629,39 @@ extern "C" int myr_fit_gn_sets(myr_handle h, int32_t E, int32_t R, int32_t num_s
   if (int rc = check_fit_gn_system(h, who)) return rc;
   if (E == 0) return MYR_OK;                          // (nothing is written)
   return run_fit(h, mem, E, R, data_shared, num_steps, u_rows, xs_obs, us, wt, params, (size_t)E * h->dims.np, false, loss, grad, gn, out_stride);
+}
+
+// The Gauss-Newton product of the network fit (fit.h: node_fit_gnvp_kernel).  The checks the two calls share, in the order the header gives: the
+// arguments, then the system -- every handle but the network's is sent to myr_fit_gn, where gn is formed and the caller can multiply.
+static int check_fit_gnvp(myr_handle h, const char* who, const void* xs_obs, const void* us, const void* params, const void* v, const void* jv,
+                          const void* out, int sets, int R, int num_steps, int u_rows, int out_stride, const char* zero, int data_shared, int mem) {
+  if (!h || !xs_obs || !us || !params || !v) return arg_fail(who, MYR_E_ARG, "null handle, xs_obs, us, params or v");
+  if (!jv && !out) return arg_fail(who, MYR_E_ARG, "jv and out are both null");
+  if (int rc = check_fit_sizes(who, sets, R, num_steps, u_rows, true)) return rc;
+  if (int rc = check_row_stride(h, who, "out_stride", out_stride, zero, "trajectory")) return rc;
+  if (int rc = check_data_shared(who, data_shared)) return rc;
+  if (int rc = check_mem(who, mem)) return rc;
+  if (h->d.system_id != MYR_SYS_NODE_CARTPOLE)
+    return arg_fail(who, MYR_E_UNSUPPORTED, "the network system only: the matrix-free product lives here because its 4 804 x 4 804 matrix is not formed.  "
+                                            "For a closed-form system use myr_fit_gn, which forms gn, and multiply");
+  return MYR_OK;
+}
+
+extern "C" int myr_fit_gnvp(myr_handle h, int32_t B, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us, const double* wt,
+                            const double* params, const double* v, double* jv, double* out, int32_t out_stride, int32_t mem) {
+  const char* who = "myr_fit_gnvp";
+  if (int rc = check_fit_gnvp(h, who, xs_obs, us, params, v, jv, out, B, 1, num_steps, u_rows, out_stride, ROW_SUM_BATCH, 0, mem)) return rc;
+  if (B == 0) return MYR_OK;                          // (nothing is written)
+  return run_fit(h, mem, 1, B, 0, num_steps, u_rows, xs_obs, us, wt, params, (size_t)h->dims.np, false, nullptr, out, nullptr, out_stride, v, jv);
+}
+
+extern "C" int myr_fit_gnvp_sets(myr_handle h, int32_t E, int32_t R, int32_t num_steps, int32_t u_rows, const double* xs_obs, const double* us,
+                                 int32_t data_shared, const double* wt, const double* params, const double* v, double* jv, double* out,
+                                 int32_t out_stride, int32_t mem) {
+  const char* who = "myr_fit_gnvp_sets";
+  if (int rc = check_fit_gnvp(h, who, xs_obs, us, params, v, jv, out, E, R, num_steps, u_rows, out_stride, ROW_SUM_FIT_SETS, data_shared, mem)) return rc;
+  if (E == 0) return MYR_OK;                          // (nothing is written)
+  return run_fit(h, mem, E, R, data_shared, num_steps, u_rows, xs_obs, us, wt, params, (size_t)E * h->dims.np, false, nullptr, out, nullptr, out_stride, v, jv);
 }
 
 // history of one instance of myr_exgd_grad*: x_s, x_bar_s, lam_s of every step and the final x (`per` doubles); the batch runs in chunks of the

@@ -106,6 +106,16 @@ class FitLoss:
     return self._sets(self.engine.fit_gn_sets, params_sets, datasets, epoch)
 
 
+def lm_accepts(value, loss) -> bool:
+  """the project's one rule for a Levenberg-Marquardt trial point: it is taken only if its loss is lower"""
+  return float(value) < float(loss)
+
+
+def lm_next_lambda(lam, accepted):
+  """... and for the damping: a third on acceptance, four times on rejection (LevenbergMarquardt below, node_training.LevenbergMarquardtCG)"""
+  return lam / 3.0 if accepted else lam * 4.0
+
+
 class LevenbergMarquardt:
   """Levenberg-Marquardt on a mapping of floats, driven from outside so that many fits can run in lockstep:
     begin(value, grad, gn) at the start point; then, until `done`, p = trial() and end(value, grad, gn) with the evaluation at p.
@@ -149,16 +159,14 @@ class LevenbergMarquardt:
     """the evaluation at the last trial point; True: the point was accepted"""
     self.iterations += 1
     value = float(value)
-    accepted = value < self.loss
+    accepted = lm_accepts(value, self.loss)
     if accepted:
       decrease = (self.loss - value) / self.loss
       self.params, self.loss = self._trial, value
       self.grad, self.gn = np.array([grad[k] for k in self.keys], dtype=np.float64), np.array(gn, dtype=np.float64)
-      self.lam /= 3.0
       if decrease < self.rtol or value <= self.ftol * self.loss0:
         self.done = True
-    else:
-      self.lam *= 4.0
+    self.lam = lm_next_lambda(self.lam, accepted)
     if self.iterations >= self.max_iter:
       self.done = True
     return accepted

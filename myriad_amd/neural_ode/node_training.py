@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from myriad_amd import _lib
-from myriad_amd.experiments.mle_sysid import Adam
+from myriad_amd.experiments.mle_sysid import Adam, lm_accepts, lm_next_lambda
 from myriad_amd.systems.neural_ode import flat_from_mapping, mapping_from_flat
 from myriad_amd.utils import yield_minibatches
 
@@ -45,6 +45,24 @@ class NodeFitLoss:
 
   def values(self, params_sets, minibatches):
     return self.values_and_grads(params_sets, minibatches, want_grad=False)[0]
+
+  def gn_product(self, params, v, minibatch):
+    """G v [4804] for the Gauss-Newton matrix G = 2 J^T W J of this loss at `params` (a mapping or flat), v flat: one myr_fit_gnvp call, no matrix.
+    loss(params + d) ~ loss + grad . d + d . G d / 2 with value_and_grad's loss and gradient."""
+    ns = self.hp.state_size
+    mb = np.asarray(minibatch, dtype=np.float64)
+    wt = np.full(mb.shape[1], 1.0 / (mb.shape[0] * mb.shape[1] * ns))
+    p = params if isinstance(params, np.ndarray) else flat_from_mapping(params)
+    return self.engine.fit_gnvp(mb[:, :, :ns], mb[:, :, ns:], p, v, wt=wt, reduce=True)["out"]
+
+  def gn_products(self, params_sets, vs, minibatches):
+    """gn_product for E weight sets at once (one myr_fit_gnvp_sets call): params_sets, vs [E,4804]; minibatches as in values_and_grads.  Row e is
+    gn_product(params_sets[e], vs[e], minibatches[e]) to the bit."""
+    ns = self.hp.state_size
+    mb = np.asarray(minibatches, dtype=np.float64)
+    wt = np.full(mb.shape[-2], 1.0 / (mb.shape[-3] * mb.shape[-2] * ns))
+    return self.engine.fit_gnvp_sets(mb[..., :ns], mb[..., ns:], np.asarray(params_sets, dtype=np.float64), np.asarray(vs, dtype=np.float64), wt=wt,
+                                     reduce=True)["out"]
 
 
 def loss(params, minibatch, *, hp, T, engine=None) -> float:
@@ -166,3 +184,204 @@ def train_ensemble(hp, T, params_sets, train_data, val_data, rngs=None, fit=None
   if own_fit:
     fit.engine.close()
   return [(best_params[e], last_epoch[e], records[e]) for e in range(E)]
+
+
+# ---- second-order training: Levenberg-Marquardt with a conjugate-gradient inner solve on the matrix-free Gauss-Newton product (myr_fit_gnvp) --------
+class ConjugateGradient:
+  """Conjugate gradients for A d = b from d = 0, A symmetric positive definite and known by its products only.  Driven from outside, so that many
+  solves can share one device call per product:  while not cg.done: cg.feed(A @ cg.p).
+  Truncated: it stops after `iters` products, once |b - A d| <= tol |b| (the recurrence's residual), or at a direction without positive curvature
+  (A is positive definite: rounding).  d is `x`; `products` counts the feeds; `residual` is |b - A d| / |b|."""
+
+  def __init__(self, b, iters, tol):
+    b = np.array(b, dtype=np.float64)
+    self.x, self.r, self.p = np.zeros_like(b), b.copy(), b.copy()
+    self.rs = self.b2 = float(b @ b)
+    self.iters, self.tol, self.products = int(iters), float(tol), 0
+    self.done = self.iters < 1 or not self.rs > 0.0
+
+  @property
+  def residual(self) -> float:
+    return float(np.sqrt(self.rs / self.b2)) if self.b2 > 0.0 else 0.0
+
+  def feed(self, Ap):
+    self.products += 1
+    pAp = float(self.p @ Ap)
+    if not pAp > 0.0:
+      self.done = True
+      return
+    alpha = self.rs / pAp
+    self.x = self.x + alpha * self.p
+    self.r = self.r - alpha * Ap
+    rs = float(self.r @ self.r)
+    if rs <= self.tol * self.tol * self.b2 or self.products >= self.iters:
+      self.done = True
+    else:
+      self.p = self.r + (rs / self.rs) * self.p
+    self.rs = rs
+
+
+def conjugate_gradient(op, b, iters, tol):
+  """ConjugateGradient run on an operator callable op(v) = A v: (d, products made, |b - A d| / |b|)"""
+  cg = ConjugateGradient(b, iters, tol)
+  while not cg.done:
+    cg.feed(op(cg.p))
+  return cg.x, cg.products, cg.residual
+
+
+class LevenbergMarquardtCG:
+  """Levenberg-Marquardt on a flat parameter vector with the step from a truncated conjugate-gradient solve of (G + lam I) d = -g, G known by its
+  products only.  Driven from outside, as mle_sysid.LevenbergMarquardt is:
+    begin(value, grad) at the start point; then, until `done`:  while solving: feed(G @ direction());  then end(value, grad) with the evaluation at trial().
+  Acceptance and the damping follow mle_sysid's rule (lm_accepts, lm_next_lambda; lam = 1e-3 at the start): the evaluation at an accepted trial point
+  is the next iteration's, a rejected one is solved again from the same gradient with the larger lam.  Stops as LevenbergMarquardt does: on an accepted
+  relative decrease below `rtol`, at `max_iter` trial points, or below `ftol` times the loss at the start.  `last`: the record of the last trial."""
+
+  def __init__(self, params, lam=1e-3, cg_iters=20, cg_tol=1e-2, rtol=1e-12, max_iter=50, ftol=1e-24):
+    self.params = np.array(params, dtype=np.float64)
+    self.lam, self.cg_iters, self.cg_tol, self.rtol, self.max_iter, self.ftol = float(lam), cg_iters, cg_tol, rtol, max_iter, ftol
+    self.iterations, self.done = 0, False
+    self.loss = self.loss0 = self.grad = self.cg = self.last = None
+
+  def begin(self, value, grad):
+    self.loss = self.loss0 = float(value)
+    self.grad = np.array(grad, dtype=np.float64)
+    self.done = self.max_iter < 1 or not self.loss > 0.0
+    self.cg = ConjugateGradient(-self.grad, self.cg_iters, self.cg_tol)
+
+  @property
+  def solving(self) -> bool:
+    return not self.done and not self.cg.done
+
+  def direction(self) -> np.ndarray:
+    """the vector whose product the solve waits for; 0 where it waits for none (a model that rides along in a lockstep call)"""
+    return self.cg.p if self.solving else np.zeros_like(self.params)
+
+  def feed(self, Gv):
+    self.cg.feed(np.asarray(Gv, dtype=np.float64) + self.lam * self.cg.p)
+
+  def trial(self) -> np.ndarray:
+    return self.params + self.cg.x
+
+  def end(self, value, grad) -> bool:
+    """the evaluation at trial(); True: the point was accepted"""
+    self.iterations += 1
+    value = float(value)
+    accepted = lm_accepts(value, self.loss)
+    self.last = {"params": self.params, "grad": self.grad, "lam": self.lam, "d": self.cg.x, "cg_products": self.cg.products,
+                 "cg_residual": self.cg.residual, "loss": self.loss, "trial_loss": value, "accepted": accepted}
+    if accepted:
+      decrease = (self.loss - value) / self.loss
+      self.params, self.loss, self.grad = self.trial(), value, np.array(grad, dtype=np.float64)
+      if decrease < self.rtol or value <= self.ftol * self.loss0:
+        self.done = True
+    self.lam = lm_next_lambda(self.lam, accepted)
+    if self.iterations >= self.max_iter:
+      self.done = True
+    self.cg = ConjugateGradient(-self.grad, self.cg_iters, self.cg_tol)
+    return accepted
+
+
+def _gn_lockstep(hp, lms, value_grads, products, val_losses, verbose, histories):
+  """The loop train_gn and train_ensemble_gn share: the models `lms` (LevenbergMarquardtCG, at their start points) in lockstep.  An outer step -- one
+  trial point -- is an epoch of train's bookkeeping: validation loss every hp.early_stop_check_frequency steps, the best parameters and the early-stop
+  counter as train keeps them; the point a model ends at is checked too.  value_grads(sets, P) -> (values, grads); products(sets, P, V) -> [n,4804];
+  val_losses(sets, P) -> values: the device calls, for the listed models.  Returns [(best_params, last step, record)]."""
+  E = len(lms)
+  best_val_loss, best_params, count, last_epoch = [10e10] * E, [None] * E, [0] * E, [None] * E
+  records = [[] for _ in range(E)]
+  live = list(range(E))
+
+  def note(sets, epoch, check):
+    new = [e for e in sets if not (records[e] and records[e][-1][0] == epoch)]      # (one record per model and epoch)
+    if new:
+      for e, validation_loss in zip(new, val_losses(new, np.stack([lms[e].params for e in new]))):
+        records[e].append((epoch, lms[e].loss, validation_loss))
+        if verbose:
+          print(e, epoch, lms[e].loss, validation_loss, lms[e].lam)
+    for e in sets if check else ():
+      validation_loss = records[e][-1][2]
+      if count[e] >= hp.early_stop_threshold:
+        lms[e].done = True
+      elif validation_loss >= best_val_loss[e]:
+        count[e] += hp.early_stop_check_frequency
+      else:
+        best_val_loss[e], best_params[e], count[e] = validation_loss, mapping_from_flat(lms[e].params), 0
+
+  if live:
+    values, grads = value_grads(live, np.stack([lms[e].params for e in live]))
+    for i, e in enumerate(live):
+      lms[e].begin(values[i], grads[i])
+  epoch = 0
+  while live:
+    for e in live:
+      last_epoch[e] = epoch
+    check = epoch % hp.early_stop_check_frequency == 0
+    if check or epoch % hp.loss_recording_frequency == 0:
+      note(live, epoch, check)
+    ended = [e for e in live if lms[e].done]
+    live = [e for e in live if not lms[e].done]
+    if ended and not check:                            # the point a model ends at is recorded and compared too
+      note(ended, epoch, True)
+    if not live:
+      break
+    P = np.stack([lms[e].params for e in live])
+    while any(lms[e].solving for e in live):           # the inner solves: one product call for all models; a finished solve rides along with 0
+      Gv = products(live, P, np.stack([lms[e].direction() for e in live]))
+      for i, e in enumerate(live):
+        if lms[e].solving:
+          lms[e].feed(Gv[i])
+    values, grads = value_grads(live, np.stack([lms[e].trial() for e in live]))
+    for i, e in enumerate(live):
+      lms[e].end(values[i], grads[i])
+      if histories is not None:
+        histories[e].append(lms[e].last)
+    epoch += 1
+  return [(best_params[e], last_epoch[e], records[e]) for e in range(E)]
+
+
+def train_gn(hp, T, params, train_data, val_data, max_iter=50, cg_iters=20, cg_tol=1e-2, lam=1e-3, rtol=1e-12, verbose=False, fit=None, history=None):
+  """train's fit by Levenberg-Marquardt on the full training set (the first hp.train_size rows): per outer step one myr_fit_grad call (the loss and
+  gradient at the trial point) and at most `cg_iters` myr_fit_gnvp calls (the truncated conjugate-gradient solve of (G + lam I) d = -g to the relative
+  residual `cg_tol`); mle_sysid's rule for lam and for taking a step; train's validation and early-stop bookkeeping with an outer step as the epoch.
+  Returns train's (best_params, last step, [(step, train loss, validation loss)]).  history: a list that receives one record per trial point
+  (LevenbergMarquardtCG.last).  fit: the loss object to use (default: a NodeFitLoss of its own, closed at the end)."""
+  own_fit = fit is None
+  fit = NodeFitLoss(hp, T) if own_fit else fit
+  data = np.asarray(train_data, dtype=np.float64)[:hp.train_size]
+  val = np.asarray(val_data, dtype=np.float64)
+  p0 = params if isinstance(params, np.ndarray) else flat_from_mapping(params)
+  lm = LevenbergMarquardtCG(p0, lam=lam, cg_iters=cg_iters, cg_tol=cg_tol, rtol=rtol, max_iter=max_iter)
+
+  def value_grads(sets, P):
+    value, grad = fit.value_and_grad(mapping_from_flat(P[0]), data)
+    return [value], [flat_from_mapping(grad)]
+
+  out = _gn_lockstep(hp, [lm], value_grads, lambda sets, P, V: [fit.gn_product(P[0], V[0], data)], lambda sets, P: [fit(mapping_from_flat(P[0]), val)],
+                     verbose, None if history is None else [history])
+  if own_fit:
+    fit.engine.close()
+  return out[0]
+
+
+def train_ensemble_gn(hp, T, params_sets, train_data, val_data, max_iter=50, cg_iters=20, cg_tol=1e-2, lam=1e-3, rtol=1e-12, verbose=False, fit=None,
+                      histories=None):
+  """E independent train_gn runs in lockstep on the sets calls: every product of all inner solves is ONE myr_fit_gnvp_sets call, every trial point of
+  all models one myr_fit_grad_sets call.  Each model has its own lam and its own conjugate-gradient state; a model whose solve has ended rides along in
+  the product calls with the direction 0, one that has stopped leaves the later calls.  params_sets, train_data, val_data as in train_ensemble;
+  histories: E lists (train_gn's history).  Entry e of the result is what train_gn returns for that model alone: equal values."""
+  own_fit = fit is None
+  fit = NodeFitLoss(hp, T) if own_fit else fit
+  P0 = np.stack([np.asarray(p, dtype=np.float64) if isinstance(p, np.ndarray) else flat_from_mapping(p) for p in params_sets]) if len(params_sets) else np.empty((0, 4804))
+  E = P0.shape[0]
+  train_data, val_data = np.asarray(train_data, dtype=np.float64), np.asarray(val_data, dtype=np.float64)
+  shared_train, shared_val = train_data.ndim == 3, val_data.ndim == 3
+  if not shared_train and train_data.shape[0] != E or not shared_val and val_data.shape[0] != E:
+    raise ValueError(f"train_data and val_data must be [E = {E}][rows][S+1][ns+nu], or [rows][S+1][ns+nu] shared by all sets")
+  data_of = lambda sets: train_data[:hp.train_size] if shared_train else train_data[sets, :hp.train_size]
+  lms = [LevenbergMarquardtCG(P0[e], lam=lam, cg_iters=cg_iters, cg_tol=cg_tol, rtol=rtol, max_iter=max_iter) for e in range(E)]
+  out = _gn_lockstep(hp, lms, lambda sets, P: fit.values_and_grads(P, data_of(sets)), lambda sets, P, V: fit.gn_products(P, V, data_of(sets)),
+                     lambda sets, P: fit.values(P, val_data if shared_val else val_data[sets]), verbose, histories)
+  if own_fit:
+    fit.engine.close()
+  return out
