@@ -18,6 +18,7 @@
  *   step(x, lmbda) (extragradient iteration)     nlp_solvers/extra_gradient.py:25-33        myr_exgd
  *   FBSM(hp,cfg,system).solve()                  trajectory_optimizers/forward_backward_sweep.py:88-116   myr_fbsm
  *   many_steps_grad / lookahead_update           experiments/e2e_sysid.py:148-177, 209-218  myr_exgd_grad
+ *   many_steps_grad: dx/dp, dlam/dp themselves   experiments/e2e_sysid.py:148-177           myr_exgd_jac
  *   many_steps_grad / lookahead_update in the network weights
  *                                                experiments/node_e2e_sysid.py:139-166, 187-196  myr_exgd_grad_node
  *   many_steps_grad / lookahead_update under SHOOTING (the default hyperparameters)
@@ -463,6 +464,32 @@ int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const double* lam, c
                   const double* params, int32_t params_stride, double eta_x, double eta_v, int32_t nsteps,
                   const double* seed_z, const double* seed_lam, double* grad, int32_t grad_stride,
                   double* dz0, double* dlam0, int32_t mem);
+
+/*
+ * The Jacobian of `nsteps` extragradient steps (myr_exgd) in the model parameters itself, carried forward through the steps on the device as
+ * experiments/e2e_sysid.py:148-177 (many_steps_grad) carries dx/dp, dlam/dp: np tangent columns in one call, where myr_exgd_grad gives one
+ * seeded row.  No history is kept: the memory does not depend on nsteps.  With (z_n, lam_n) the iterate after `nsteps` steps from (z, lam):
+ *   jz[b][k] = d z_n / d params[k]  ([B][np][n]: parameter-major, each row in z's layout),   jlam[b][k] = d lam_n / d params[k]  ([B][np][m]).
+ * A variable that a half-step leaves on a bound (and a pinned one, lb == ub) has a zero row entry, as in myr_exgd_grad.
+ *   z [B][n], lam [B][m] (not modified); lb, ub [B][n]; params, params_stride, eta_x, eta_v, nsteps as in myr_exgd_grad;
+ *   jz0 [B][np][n], jlam0 [B][np][m] or NULL (= 0): the tangents of the starting point.  NULL holds the start fixed (many_steps_grad); with the
+ *   jz, jlam (and zn, lamn) of a previous call, a run of a + b steps splits into two calls with the bits of the one;
+ *   zn [B][n], lamn [B][m] or NULL: the advanced iterate, with the bits of myr_exgd on the same inputs;
+ *   jz, jlam: either may be NULL, not both.
+ * nsteps == 0 gives jz = jz0, jlam = jlam0 (or 0), zn = z, lamn = lam; B == 0 writes nothing.  The same bits for MYR_MEM_HOST and
+ * MYR_MEM_DEVICE, on every call, for an instance alone or in any batch, and with any subset of the optional outputs; no atomics.  Timed on
+ * MYR_K_PROD.  Detected by its export: myr_version() is unchanged.
+ * One wavefront per (instance, group of columns), iterate and columns in LDS (csrc/exgd_jac.h): the iterate's (2 n + m + x_rows ns) doubles and as
+ * many again per column.  The columns run in the fewest equal groups that fit the 160 KiB (MYRIAD_EXGD_JAC_LDS_BYTES, read at call time,
+ * lowers that budget); a column has the same bits in every grouping.
+ * Errors, in this order.  MYR_E_ARG: null h / z / lam / lb / ub; jz and jlam both NULL; B < 0; nsteps < 0; a params_stride other than 0 and
+ * np; a bad mem.  MYR_E_UNSUPPORTED: SHOOTING (myr_exgd_grad_shoot has seeded rows), the network system (myr_exgd_grad_node), the elastic
+ * twins, INVASIVEPLANT, a system without generated derivatives.  MYR_E_CAPACITY: the iterate and ONE column do not fit; nothing is written.
+ */
+int myr_exgd_jac(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub,
+                 const double* params, int32_t params_stride, double eta_x, double eta_v, int32_t nsteps,
+                 const double* jz0, const double* jlam0,
+                 double* zn, double* lamn, double* jz, double* jlam, int32_t mem);
 
 /*
  * myr_exgd_grad in the np = 4804 weights of the network system (experiments/node_e2e_sysid.py:139-166, 187-196; library version 0.5): the same

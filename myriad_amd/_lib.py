@@ -84,6 +84,7 @@ _SIGNATURES = {
   "myr_exgd_grad_node": ([_p, _i, _p, _p, _p, _p, _p] + _EXGD_GRAD_TAIL, C.c_int),
   "myr_exgd_grad_node_shoot": ([_p, _i, _p, _p, _p, _p, _p] + _EXGD_GRAD_TAIL, C.c_int),
   "myr_exgd_grad_node_sets": ([_p, _i, _i, _p, _p, _p, _p, _p] + _EXGD_GRAD_TAIL, C.c_int),
+  "myr_exgd_jac": ([_p, _i, _p, _p, _p, _p, _p, _i, _f, _f, _i, _p, _p, _p, _p, _p, _p, _i], C.c_int),
   "myr_hvp": ([_p, _i, _p, _p, _p, _p, _i] + _HVP_TAIL, C.c_int),
   "myr_hvp_node": ([_p, _i, _p, _p, _p, _p] + _HVP_TAIL, C.c_int),
   "myr_hvp_node_sets": ([_p, _i, _i, _p, _p, _p, _p] + _HVP_TAIL, C.c_int),
@@ -616,6 +617,37 @@ class Engine:
     """Zero-copy variant of exgd_grad: every array is a device tensor on this handle's device."""
     self._exgd_grad_call("myr_exgd_grad", MEM_DEVICE, (B,), z, lam, lb, ub, (params, params_stride), eta_x, eta_v, nsteps, seed_z, seed_lam, grad, grad_stride,
                          dz0, dlam0)
+
+  # myr_exgd_jac: the Jacobian of the same steps itself, forward mode (csrc/exgd_jac.h) -- closed-form systems, the collocation transcriptions
+  def exgd_jac(self, z, lam, lb, ub, eta_x, eta_v, nsteps, params=None, jz0=None, jlam0=None, want=("zn", "lamn", "jz", "jlam")):
+    """myr_exgd_jac: d z_n / d params and d lam_n / d params of `nsteps` extragradient steps from (z, lam), np tangent columns in one call.
+    jz0 [B,np,n], jlam0 [B,np,m] or None (= 0): the tangents of the start.  Returns the entries of `want` (at least one of "jz", "jlam"):
+    {"zn" [B,n], "lamn" [B,m] (the bits of exgd), "jz" [B,np,n], "jlam" [B,np,m]}."""
+    z = self._batch2(z, self.n, "z"); lam = self._batch2(lam, self.m, "lam")
+    B = z.shape[0]
+    if lam.shape[0] != B:
+      raise ValueError("z and lam must have the same batch size")
+    unknown = set(want) - {"zn", "lamn", "jz", "jlam"}
+    if unknown or not {"jz", "jlam"} & set(want):
+      raise ValueError(f"want: at least one of 'jz', 'jlam', beside 'zn', 'lamn' (got {tuple(want)})")
+    lb, ub = (np.ascontiguousarray(np.broadcast_to(_f64(a), z.shape)) for a in (lb, ub))
+    j0 = [None if a is None else np.ascontiguousarray(np.broadcast_to(_f64(a), (B, self.np, w))) for a, w in ((jz0, self.n), (jlam0, self.m))]
+    shapes = dict(zn=(B, self.n), lamn=(B, self.m), jz=(B, self.np, self.n), jlam=(B, self.np, self.m))
+    out = {k: np.empty(shapes[k]) if k in want else None for k in shapes}
+    p, ps = self._params(params, B)
+    self.exgd_jac_device(B, z, lam, lb, ub, eta_x, eta_v, nsteps, params=p, params_stride=ps, jz0=j0[0], jlam0=j0[1], mem=MEM_HOST, **out)
+    return self._present(**out)
+
+  def exgd_jac_probe(self):
+    """Raises the library's error when myr_exgd_jac is not built for this handle (an empty batch: the checks run, nothing else)."""
+    d = np.zeros(1)
+    self.exgd_jac_device(0, d, d, d, d, 0.0, 0.0, 0, jz=d, mem=MEM_HOST)
+
+  def exgd_jac_device(self, B, z, lam, lb, ub, eta_x, eta_v, nsteps, params=None, params_stride=0, jz0=None, jlam0=None, zn=None, lamn=None, jz=None,
+                      jlam=None, mem=MEM_DEVICE):
+    """Zero-copy variant of exgd_jac: every array is a device tensor on this handle's device (jz or jlam may be None, not both)."""
+    _chk(self.lib.myr_exgd_jac(self._h, int(B), _addr(z), _addr(lam), _addr(lb), _addr(ub), _addr(params), int(params_stride), float(eta_x), float(eta_v),
+                               int(nsteps), _addr(jz0), _addr(jlam0), _addr(zn), _addr(lamn), _addr(jz), _addr(jlam), mem), "myr_exgd_jac")
 
   # myr_exgd_grad_shoot: the same derivative on a SHOOTING handle (csrc/shoot_exgd_grad.h) -- the signatures, the return dict and the checks of the
   # three methods above; myr_exgd_grad itself keeps refusing SHOOTING

@@ -27,6 +27,7 @@
 #include "fit.h"
 #include "fit_gn.h"
 #include "exgd_grad.h"
+#include "exgd_jac.h"
 #include "node_exgd_grad.h"
 #include "colloc_hvp.h"
 #include "shoot_hvp.h"
@@ -343,6 +344,9 @@ struct ExgdGradArgs {      // rows: [B][NP] gradient rows; hist: the history of 
   double *rows, *dz0, *dlam0, *hist; int chunk;
   double* work; long Pp;      // SHOOTING (closed form) only: the scratch of one chunk (launch_shoot_exgd_grad carves it) and its pair columns
   int R, inst0;               // R: instances to a weight set (the network routes: params [B / R][NP], pstride 0; else B); inst0: the chunk's first instance
+  // myr_exgd_jac (route EXGD_JAC; no seeds, rows or history): the start's tangents jz0 [B][NP][n], jlam0 [B][NP][m] and the outputs zn [B][n],
+  // lamn [B][m], jz, jlam (the tangents' shapes); each may be null, jz and jlam not both
+  const double *jz0, *jlam0; double *zn, *lamn, *jz, *jlam;
 };
 struct HvpArgs {      // lam, out_z, rows ([B][NP] parameter rows) may be null; hist, side: shooting scratch, batch-minor with Pp columns (one per pair)
   int B; const double *z, *lam, *v, *params; int pstride, with_cost; double *out_z, *rows, *hist, *side; long Pp;
@@ -1238,6 +1242,40 @@ int exgd_grad_for_system(myr_handle h, const ExgdGradArgs& a) {
   return fail(MYR_E_UNSUPPORTED, "myr_exgd_grad: not built for this system and transcription");
 }
 
+// the forward-mode Jacobian of the same steps (exgd_jac.h: colloc_exgd_jac_kernel), one launch: a wavefront per (instance, group of columns).  The
+// columns run in the fewest groups of equal size whose LDS record -- the iterate's and one of the same size per column -- fits the budget: the
+// hardware's 160 KB, or less where MYRIAD_EXGD_JAC_LDS_BYTES says so (tests: the grouped path)
+template <class Sys, int SCHEME>
+static int launch_exgd_jac(myr_handle h, const ExgdGradArgs& a) {
+  const int N = h->d.intervals, NP = Sys::NP;
+  size_t budget = 160 * 1024;
+  if (const char* e = getenv("MYRIAD_EXGD_JAC_LDS_BYTES")) { const long long v = atoll(e); if (v > 0 && (size_t)v < budget) budget = (size_t)v; }
+  int cap = 0;
+  while (cap < NP && colloc_exgd_jac_lds_bytes<Sys, SCHEME>(N, cap + 1) <= budget) ++cap;
+  if (cap < 1)
+    return fail(MYR_E_CAPACITY, "myr_exgd_jac: the iterate and one tangent column do not fit in LDS (" +
+                                    std::to_string(colloc_exgd_jac_lds_bytes<Sys, SCHEME>(N, 1)) + " bytes of " + std::to_string(budget) +
+                                    "); use fewer intervals, or myr_exgd_grad for seeded rows");
+  const int groups = (NP + cap - 1) / cap, gcols = (NP + groups - 1) / groups;
+  auto kern = colloc_exgd_jac_kernel<Sys, SCHEME>;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  const size_t lds = colloc_exgd_jac_lds_bytes<Sys, SCHEME>(N, gcols);
+  hipLaunchKernelGGL(kern, dim3((unsigned)a.B, (unsigned)((NP + gcols - 1) / gcols)), dim3(64), lds, h->stream,
+                     a.B, N, h->d.T / N, a.z, a.lam, a.lb, a.ub, a.params, a.pstride, a.eta_x, a.eta_v, a.nsteps, a.jz0, a.jlam0, a.zn, a.lamn, a.jz,
+                     a.jlam, gcols);
+  return MYR_OK;
+}
+
+template <class Sys>
+int exgd_jac_for_system(myr_handle h, const ExgdGradArgs& a) {
+  // myr_exgd_jac has refused the twins, the network system and SHOOTING, each with its own message; the constexpr keeps their kernels out of the build
+  if constexpr (SysDpw<Sys>::SUPPORTED) {
+    if (h->d.transcription == MYR_TR_HERMITE_SIMPSON) return launch_exgd_jac<Sys, PROD_HS>(h, a);
+    if (h->d.transcription == MYR_TR_TRAPEZOIDAL) return launch_exgd_jac<Sys, PROD_TRAP>(h, a);
+  }
+  return fail(MYR_E_UNSUPPORTED, "myr_exgd_jac: not built for this system and transcription");
+}
+
 // the same derivative in the weights of the network system (node_exgd_grad.h: node_exgd_grad_kernel; myr_exgd_grad_node has checked system and transcription)
 template <int WPI>
 static int launch_node_exgd_grad(myr_handle h, const ExgdGradArgs& a) {
@@ -1432,6 +1470,7 @@ int hvp_node_shoot_for_system(myr_handle h, const HvpArgs& a) {
   LINK template int fit_gn_for_system<S>(myr_handle, const FitArgs&);         \
   LINK template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&); \
   LINK template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
+  LINK template int exgd_jac_for_system<S>(myr_handle, const ExgdGradArgs&);  \
   LINK template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
   LINK template int hvp_shoot_for_system<S>(myr_handle, const HvpArgs&);      \
   LINK template int exgd_grad_shoot_for_system<S>(myr_handle, const ExgdGradArgs&); \
@@ -1466,6 +1505,7 @@ template int solve_lane_colloc_for_system<myriad::MYR_TU_SYSTEM, 1>(myr_handle, 
   template int fit_gn_for_system<S>(myr_handle, const FitArgs&);              \
   template int exgd_grad_for_system<S>(myr_handle, const ExgdGradArgs&);      \
   template int exgd_grad_node_for_system<S>(myr_handle, const ExgdGradArgs&); \
+  template int exgd_jac_for_system<S>(myr_handle, const ExgdGradArgs&);       \
   template int hvp_colloc_for_system<S>(myr_handle, const HvpArgs&);          \
   template int hvp_node_colloc_for_system<S>(myr_handle, const HvpArgs&);     \
   template int launch_fbsm<S>(myr_handle, const FbsmArgs&);
@@ -2678,10 +2718,17 @@ static int exgd_grad_chunk(myr_handle h, int B, int nsteps, size_t* per) {
 // device pointers throughout (a.hist, a.chunk, under EXGD_GRAD_SHOOT a.work and a.Pp and, for the batch sum, a.rows are set here); grad: [B][np] rows
 // (grad_stride == np) or, per weight set of a.R instances, the sum of its rows in fit_reduce_sets_kernel's fixed order: [B / R][np] (the closed-form
 // routes and the single-set network calls have R = B: one row, the sum over the batch)
-enum { EXGD_GRAD_CLOSED_FORM = 0, EXGD_GRAD_NODE = 1, EXGD_GRAD_NODE_SHOOT = 2, EXGD_GRAD_SHOOT = 3 };      // which kernel family runs the sweep
+// EXGD_JAC (myr_exgd_jac: forward mode) has no history, rows or reduction: one launch between the timers
+enum { EXGD_GRAD_CLOSED_FORM = 0, EXGD_GRAD_NODE = 1, EXGD_GRAD_NODE_SHOOT = 2, EXGD_GRAD_SHOOT = 3, EXGD_JAC = 4 };      // which kernel family runs the sweep
 static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int grad_stride, int route) {
   const myr_dims& dm = h->dims;
   const long I = h->d.intervals;
+  if (route == EXGD_JAC) {
+    if (int rc = timed_begin(h, MYR_K_PROD)) return rc;
+    const int rc = for_system(h->d.system_id, true, [&](auto t) { return exgd_jac_for_system<SYS_OF(t)>(h, a); }, [] { return (int)MYR_OK; });
+    const int rc_end = timed_end(h, MYR_K_PROD);          // on every path
+    return rc ? rc : rc_end;
+  }
   if (route == EXGD_GRAD_SHOOT && (long)a.B * I > (1L << 30))
     return fail(MYR_E_CAPACITY, "myr_exgd_grad_shoot: more than 2^30 (instance, interval) pairs in one call");
   size_t per;
@@ -2709,11 +2756,13 @@ static int dispatch_exgd_grad(myr_handle h, ExgdGradArgs a, double* grad, int gr
   return rc ? rc : rc_end;
 }
 
-// what the five myr_exgd_grad* entry points share behind their own checks: the staging, the sweep of `route`, the copies back.
+// what the five myr_exgd_grad* entry points and myr_exgd_jac share behind their own checks: the staging, the sweep of `route`, the copies back.
 // n_param_doubles: what `params` holds (a row per instance, or one shared set; the network routes: a set for every R instances, B / R sets)
+// jac (route EXGD_JAC only; then seeds, grad, dz0, dlam0 are null): the caller's tangent inputs and outputs, staged like the rest
+struct ExgdJacIO { const double *jz0, *jlam0; double *zn, *lamn, *jz, *jlam; };
 static int run_exgd_grad(myr_handle h, int route, int mem, int B, int R, const double* z, const double* lam, const double* lb, const double* ub,
                          const double* params, size_t n_param_doubles, int pstride, double eta_x, double eta_v, int nsteps, const double* seed_z,
-                         const double* seed_lam, double* grad, int grad_stride, double* dz0, double* dlam0) {
+                         const double* seed_lam, double* grad, int grad_stride, double* dz0, double* dlam0, const ExgdJacIO* jac = nullptr) {
   if (B == 0) return MYR_OK;                          // (nothing is written)
   HIPCHK(hipSetDevice(h->d.device));
   const myr_dims& dm = h->dims;
@@ -2732,6 +2781,14 @@ static int run_exgd_grad(myr_handle h, int route, int mem, int B, int R, const d
   st.out(g, grad, grad_stride ? (size_t)B * dm.np : (size_t)(B / R) * dm.np);
   st.out(a.dz0, dz0, nz);
   st.out(a.dlam0, dlam0, nl);
+  if (jac) {
+    st.in(a.jz0, jac->jz0, nz * dm.np);
+    st.in(a.jlam0, jac->jlam0, nl * dm.np);
+    st.out(a.zn, jac->zn, nz);
+    st.out(a.lamn, jac->lamn, nl);
+    st.out(a.jz, jac->jz, nz * dm.np);
+    st.out(a.jlam, jac->jlam, nl * dm.np);
+  }
   if (int rc = st.commit()) return rc;
   if (int rc = dispatch_exgd_grad(h, a, g, grad_stride, route)) return rc;
   return st.finish();
@@ -2753,6 +2810,31 @@ extern "C" int myr_exgd_grad(myr_handle h, int32_t B, const double* z, const dou
   if (int rc = check_mem(who, mem)) return rc;
   return run_exgd_grad(h, EXGD_GRAD_CLOSED_FORM, mem, B, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps,
                        seed_z, seed_lam, grad, grad_stride, dz0, dlam0);
+}
+
+// the forward-mode Jacobian of the same steps (exgd_jac.h): every argument check first, then the refusals of myr_exgd_grad, then the LDS bound
+extern "C" int myr_exgd_jac(myr_handle h, int32_t B, const double* z, const double* lam, const double* lb, const double* ub, const double* params,
+                            int32_t params_stride, double eta_x, double eta_v, int32_t nsteps, const double* jz0, const double* jlam0, double* zn,
+                            double* lamn, double* jz, double* jlam, int32_t mem) {
+  const char* who = "myr_exgd_jac";
+  if (int rc = check_handle_and_arrays(who, h, z, lam, lb)) return rc;
+  if (int rc = check_ub(who, ub)) return rc;
+  if (!jz && !jlam) return arg_fail(who, MYR_E_ARG, "jz and jlam are both null");
+  if (int rc = check_batch(who, B)) return rc;
+  if (nsteps < 0) return arg_fail(who, MYR_E_ARG, "negative nsteps");
+  if (int rc = check_stride(h, who, params, params_stride)) return rc;
+  if (int rc = check_mem(who, mem)) return rc;
+  if (h->d.transcription == MYR_TR_SHOOTING && h->d.system_id != MYR_SYS_INVASIVEPLANT)
+    return arg_fail(who, MYR_E_UNSUPPORTED, "SHOOTING is not built; use myr_exgd_grad_shoot (myr_exgd_grad_node_shoot for the network system) for seeded rows, or a collocation transcription");
+  if (h->d.system_id == MYR_SYS_NODE_CARTPOLE)
+    return arg_fail(who, MYR_E_UNSUPPORTED, "the network system is not built (4 804 tangent columns are reverse mode's case); use myr_exgd_grad_node");
+  if (h->d.system_id >= 100) return arg_fail(who, MYR_E_UNSUPPORTED, "an elastic twin has no model of its own to differentiate; use the handle of its system");
+  if (h->d.system_id == MYR_SYS_INVASIVEPLANT) return no_such_path(h, who);
+  if (!for_system(h->d.system_id, false, [](auto t) { return (int)SysDpw<SYS_OF(t)>::SUPPORTED; }, [] { return 0; }))
+    return arg_fail(who, MYR_E_UNSUPPORTED, "this system has no generated parameter derivatives; myr_exgd and differences in the parameters remain");
+  const ExgdJacIO io{jz0, jlam0, zn, lamn, jz, jlam};
+  return run_exgd_grad(h, EXGD_JAC, mem, B, B, z, lam, lb, ub, params, n_params(h, params, params_stride, B), params_stride, eta_x, eta_v, nsteps, nullptr,
+                       nullptr, nullptr, h->dims.np, nullptr, nullptr, &io);
 }
 
 // the same call for the weights of the network system: one shared weight set (no params_stride), Hermite-Simpson

@@ -16,7 +16,11 @@ the mean over the batch and its gradient the batch sum of myr_exgd_grad (grad_st
 
 The reference's default hyperparameters select SHOOTING (intervals = 1, controls_per_interval = 100, HEUN).  That route is opt-in:
 `run_endtoend(..., shooting=True)` with a SHOOTING optimizer runs the same loop on myr_exgd_grad_shoot.  Without it myr_exgd_grad is asked, which
-refuses SHOOTING (NotImplementedError with its message) before anything is solved; the driver does not switch transcription on its own."""
+refuses SHOOTING (NotImplementedError with its message) before anything is solved; the driver does not switch transcription on its own.
+
+EXTENSION: `run_endtoend_gn` fits the same keys by Levenberg-Marquardt on the imitation loss.  Its Jacobian is what many_steps_grad carries forward
+before lookahead_update contracts it -- d x_n / d p itself, one myr_exgd_jac call (csrc/exgd_jac.h) per trial point, which also returns x_n --, and the
+driver is mle_sysid's LevenbergMarquardt.  Collocation transcriptions, closed-form systems; `run_endtoend` is unchanged."""
 from __future__ import annotations
 
 from typing import Optional
@@ -64,6 +68,83 @@ def lookahead_gradient(optimizer, params, xs_and_us, lmbdas, true_opt_us, epoch,
   g = call(xs_and_us, lmbdas, lb, ub, eta_x, eta_v, NUM_UNROLLED, dJ_dx, params=p, reduce=True, want_start=False)["grad"]
   g = g * sign / B
   return {k: float(g[system.param_names.index(k)]) for k in params}
+
+
+def imitation_normal_equations(keys, names, u_n, jz, true_opt_us, weights):
+  """(loss, gradient mapping, Gauss-Newton matrix [K,K], J^T J [K,K]) of the imitation loss sum_b r_b . r_b with r = sqrt(w) o (u_n - u_true), in
+  the LevenbergMarquardt convention (loss(p + d) ~ loss + grad . d + d . gn d / 2: grad = 2 J^T r, gn = 2 J^T J), summed over the batch.
+  u_n [B][rows nu]: the control part of the iterate; jz [B][np][n]: its Jacobian rows (myr_exgd_jac), of which the control part of the rows of
+  `keys` (`names`: the device order) is J^T; weights [rows]."""
+  B, width = u_n.shape
+  sw = np.sqrt(np.repeat(np.asarray(weights, dtype=np.float64), width // len(weights)))
+  r = sw * (u_n - np.reshape(true_opt_us, (B, width)))
+  Jt = jz[:, [names.index(k) for k in keys], jz.shape[2] - width:] * sw      # [B][K][rows nu]
+  jtr = np.einsum("bki,bi->k", Jt, r)
+  jtj = np.einsum("bki,bli->kl", Jt, Jt)
+  return float((r * r).sum()), {k: 2.0 * float(v) for k, v in zip(keys, jtr)}, 2.0 * jtj, jtj
+
+
+def fit_imitation_gn(evaluate, guess, max_iter=50, rtol=1e-12):
+  """Levenberg-Marquardt (mle_sysid.LevenbergMarquardt, the driver of run_mle_sysid_gn) on `evaluate(params) -> (loss, grad mapping, gn, jtj)`
+  from the mapping `guess`: one evaluation per trial point.  Returns {"params", "losses" (at the start and after every accepted step),
+  "device_calls", "iterations", "jtj" (J^T J at the last accepted point, in the order of the keys), "first" (the evaluation at the start)}."""
+  from myriad_amd.experiments.mle_sysid import LevenbergMarquardt
+  lm = LevenbergMarquardt(guess, rtol=rtol, max_iter=max_iter)
+  calls, jtj = 1, None
+  first = evaluate(lm.params)
+  lm.begin(*first[:3])
+  jtj, losses = first[3], [lm.loss]
+  while not lm.done:
+    ev = evaluate(lm.trial())
+    calls += 1
+    if lm.end(*ev[:3]):
+      jtj = ev[3]
+      losses.append(lm.loss)
+  return {"params": dict(lm.params), "losses": losses, "device_calls": calls, "iterations": lm.iterations, "jtj": jtj, "first": first}
+
+
+def run_endtoend_gn(hp: HParams, cfg: Config, nsteps: int = NUM_UNROLLED, max_iter: int = 50, start_states=None, rtol: float = 1e-12,
+                    true_opt_us=None, guess=None) -> Optional[dict]:
+  """The end-to-end fit by Levenberg-Marquardt instead of Adam: the keys of param_guesses[hp.system] (or of `guess`, the starting mapping) so that
+  `nsteps` extragradient steps from the optimizer's guess with lmbda = 0 reproduce the true optimal controls.  Residual
+  r(p) = sqrt(w) o (u_n(p) - u_true) with w = imitation_weights at epoch 0; its Jacobian is the control part of d z_n / d p, which the reference's
+  many_steps_grad carries forward (:148-177) and ONE myr_exgd_jac call per trial point gives together with u_n.  start_states [B][ns]: a batch of
+  instances, their normal equations summed.  true_opt_us: the controls to imitate ([rows][nu], [B][rows][nu] for a batch; default: the true
+  system's optimum, one solve).  Returns fit_imitation_gn's dictionary plus "true_opt_us"; None for a system without parameter guesses.
+  run_endtoend (Adam on the reverse-mode gradient, the reference's loop) is unchanged."""
+  if hp.system not in param_guesses and guess is None:
+    print("We do not currently support that kind of system for sysid. Exiting...")
+    return None
+  true_system = hp.system()
+  optimizer = get_optimizer(hp, cfg, true_system)
+  optimizer.engine.exgd_jac_probe()                        # the library's own refusal, before the true optimum is solved for
+  if start_states is not None:
+    x0s = np.asarray(start_states, dtype=np.float64)
+    if true_opt_us is None:
+      true_opt_us = optimizer.solve_batch(x0s=x0s)['u']
+    z0, lb, ub = optimizer.batch_inputs(x0s, true_system.device_params())
+  else:
+    if true_opt_us is None:
+      true_opt_us = optimizer.solve()['u']
+    z0, lb, ub = optimizer.guess[None], optimizer.bounds[None, :, 0], optimizer.bounds[None, :, 1]
+  z0 = np.array(z0, dtype=np.float64)
+  true_opt_us = np.asarray(true_opt_us, dtype=np.float64)
+  lam0 = np.zeros((z0.shape[0], optimizer.engine.m))
+  eta_x, eta_v = optimizer.step_sizes()
+  start = dict(param_guesses[hp.system] if guess is None else guess)
+  rows, nu = true_opt_us.shape[-2:]
+  weights = imitation_weights(hp, rows, nu, 0)
+
+  def evaluate(params):
+    out = optimizer.unrolled_jacobian(z0, lam0, params, nsteps, eta_x, eta_v, lb, ub, want=("zn", "jz"))
+    return imitation_normal_equations(list(start), true_system.param_names, out["zn"][:, z0.shape[1] - rows * nu:], out["jz"], true_opt_us, weights)
+
+  res = fit_imitation_gn(evaluate, start, max_iter=max_iter, rtol=rtol)
+  if cfg.verbose:
+    print("losses", res["losses"])
+    print("params", res["params"])
+  res["true_opt_us"] = true_opt_us
+  return res
 
 
 def run_endtoend(hp: HParams, cfg: Config, num_epochs: int = 10_000, start_states=None, save_and_reset_time: int = 1_000,

@@ -254,6 +254,29 @@ class TrajectoryOptimizer(object):
                ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, seed, params=p, reduce=reduce, want_start=False)["grad"] * sign
     return out[0] if single and not reduce else out
 
+  def unrolled_jacobian(self, variables, lmbdas, params, nsteps, eta_x=None, eta_v=None, lb=None, ub=None, jz0=None, jlam0=None,
+                        want=("zn", "lamn", "jz", "jlam")):
+    """d x_nsteps / d params and d lmbda_nsteps / d params themselves, carried forward through `nsteps` extragradient steps from (variables, lmbdas)
+    as the reference's many_steps_grad carries them (experiments/e2e_sysid.py:148-177): np columns in one device call (myr_exgd_jac), where
+    unrolled_grad gives one seeded row.  variables [n] or [B,n]; params: a parameter mapping (None: the system's own), with unrolled_grad's
+    name and sign mapping (split_params).  jz0 / jlam0: the tangents of the start, as a previous call's "jz" / "jlam" (None: a start held
+    fixed).  Returns the entries of `want`: "jz" [np,n] ([B,np,n] for a batch), "jlam" [np,m], rows in the device order of
+    system.param_names, and the advanced iterate "zn", "lamn" (the bits of extragradient_step)."""
+    from myriad_amd.experiments.mle_sysid import split_params
+    ex, ev = self.step_sizes()
+    single = np.ndim(variables) == 1
+    p, sign = (self.system.device_params(), np.ones(self.engine.np)) if params is None else split_params(self.system, params)
+    sign = np.asarray(sign, dtype=np.float64)[None, :, None]      # d|p|/dp = +-1 per row, on the way in and on the way out
+    start = [None if a is None else np.reshape(np.asarray(a, dtype=np.float64), (-1, self.engine.np, w)) * sign
+             for a, w in ((jz0, self.engine.n), (jlam0, self.engine.m))]
+    out = self.engine.exgd_jac(variables, lmbdas, self.bounds[:, 0] if lb is None else lb, self.bounds[:, 1] if ub is None else ub,
+                               ex if eta_x is None else eta_x, ev if eta_v is None else eta_v, nsteps, params=p, jz0=start[0], jlam0=start[1],
+                               want=want)
+    for k in ("jz", "jlam"):
+      if k in out:
+        out[k] = out[k] * sign
+    return {k: (v[0] if single else v) for k, v in out.items()}
+
   # ---- what stands in for IPOPT's restoration phase ---------------------------------------------------------------------
   # The batched SQP has no feasibility-restoration phase of its own.  An instance that ends without a KKT point goes through
   # an ELASTIC PHASE (the system's elastic twin, where the library carries one) and then through SECOND STARTS from excitation
